@@ -8,11 +8,13 @@ A "step" is one scan.  Inputs (map + raw scans) are in HBM before the timed regi
 so with N GPUs every rank registers its own K scans against its own replica of the map (weak scaling, no
 data-path collective).
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  A plain run sets up, warms up, times exactly --steps scans
+and prints the line; --full adds everything else the metric config measures or checks (pose check, latencies, upload-included leg, roofline,
+CPU baselines, parity legs, the other BASELINE configurations).  --dump-outputs DIR writes what the timed call returned as .npy files.
 """
 import os
 import sys
@@ -67,7 +69,7 @@ def main():
     ap.add_argument("--lru", type=int, default=100000, help="--config stream: iVox capacity in voxels (the reference's 100000, laserMapping.cpp:1063); 0 = never evict")
     ap.add_argument("--prior-t", type=float, default=0.3, help="prior error of a scan, metres (BASELINE: within 0.3 m)")
     ap.add_argument("--prior-deg", type=float, default=2.0, help="prior error of a scan, degrees (BASELINE: within 2 deg)")
-    ap.add_argument("--secondary", type=int, default=1, help="N = 1, --config metric: also run BASELINE config 2 (1e6-pt map) and a short config 3 "
+    ap.add_argument("--secondary", type=int, default=1, help="N = 1, --config metric --full: also run BASELINE config 2 (1e6-pt map) and a short config 3 "
                                                              "(streaming, map_incremental + LRU) after the timed region and report them under `configs`")
     ap.add_argument("--dry-run", action="store_true", help="everything up to the first HIP call, on the CPU: arguments, the torch.distributed rendezvous (gloo), the "
                                                            "sharding of the work over the ranks, the RCCL unique id exchange -- a launch check for multi-GPU runs on a box without GPUs")
@@ -79,9 +81,16 @@ def main():
     ap.add_argument("--full-line", action="store_true", help=argparse.SUPPRESS)  # the whole record on stdout (the metric config's children of the secondary legs)
     ap.add_argument("--upload-scans", type=int, default=-1, help="--config metric: scans of the upload-included leg (the pool from pinned host memory, copy overlapped "
                                                                   "with the rounds in flight); -1 = as many as the timed region, 0 = skip")
-    ap.add_argument("--min-seconds", type=float, default=5.0, help="the job list of --steps scans is repeated until the timed region lasts at least this long")
+    ap.add_argument("--min-seconds", type=float, default=None, help="the job list of --steps scans is repeated until the timed region lasts at least this long "
+                                                                     "(metric: default 0, exactly --steps scans are timed; merge: default 5)")
+    ap.add_argument("--full", action="store_true", help="metric config: beside the headline also the pose check, latencies, upload-included leg, roofline, "
+                                                        "CPU baselines, parity legs and (--secondary) the other BASELINE configurations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="metric config: after the timed region, write what it returned (final states and "
+                                                                         "counts of the last steps) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     set_full_line(args.full_line)
+    if args.dump_outputs and args.config != "metric":
+        raise SystemExit("bench.py: --dump-outputs is implemented for the metric config only")
 
     if args.config == "refparity":  # child process of the metric config's parity leg: CPU only
         return ref_parity_leg(args.parity_dir)

@@ -51,6 +51,17 @@ def emit(out, tag="metric"):
     sys.stdout.flush()
 
 
+def dump_outputs(out_dir, results, pool):
+    """--dump-outputs DIR: what the caller of the timed call receives (lio_scan_job's state_out, rc, n_ds, n_pass, n_knn_pass), float64 .npy files --
+    last_state / last_counts for the last timed step, pool_states / pool_counts for the last min(steps, pool) steps (every distinct scan of the pool once)"""
+    os.makedirs(out_dir, exist_ok=True)
+    tail = results[-min(len(results), pool):]
+    counts = np.array([[r["rc"], r["n_ds"], r["n_pass"], r["n_knn_pass"]] for r in tail], dtype=np.float64)
+    states = np.stack([np.asarray(r["state"], dtype=np.float64) for r in tail])
+    for name, a in (("last_state", states[-1]), ("last_counts", counts[-1]), ("pool_states", states), ("pool_counts", counts)):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 _VALU_PEAK = {}
 
 

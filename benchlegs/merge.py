@@ -12,7 +12,7 @@ def dry_run(args, dist, world, rank, local_rank):
     # what the real run binds and runs: cuda:<LOCAL_RANK> (torch.cuda.set_device(local_rank) in main), the secondary legs / CPU baselines / parity child on
     # a single-GPU run's rank 0 only (with N > 1 ranks no rank waits for them: nothing to time out at a barrier), one stdout line from rank 0
     info = {"rank": rank, "local_rank": local_rank, "device": f"cuda:{local_rank}", "prints_the_line": rank == 0,
-            "runs_secondary_legs": bool(rank == 0 and world == 1 and args.secondary and args.config == "metric")}
+            "runs_secondary_legs": bool(rank == 0 and world == 1 and args.full and args.secondary and args.config == "metric")}
     if args.config == "merge":
         plan = merge_plan(world, rank, seed=args.seed, n_keyframes=max(args.scan_pool, 16))
         info["sub_maps"] = plan["mine"]
@@ -120,7 +120,8 @@ def bench_merge(args, torch, dist, world, rank, local_rank, dev):
     c0 = time.perf_counter()
     lio.run_prepared(cal, batch=batch)
     torch.cuda.synchronize()
-    repeats = max(1, int(np.ceil(1.05 * min(args.min_seconds, 3.0) / max(time.perf_counter() - c0, 1e-6))))
+    min_seconds = 5.0 if args.min_seconds is None else args.min_seconds
+    repeats = max(1, int(np.ceil(1.05 * min(min_seconds, 3.0) / max(time.perf_counter() - c0, 1e-6))))
     if dist is not None:
         tr = torch.tensor([float(repeats)], device=dev, dtype=torch.float64)
         dist.all_reduce(tr, op=dist.ReduceOp.MAX)

@@ -1,11 +1,13 @@
 """bench.py (default configuration): the headline measurement and everything reported beside it."""
 from .common import *  # noqa: F401,F403  (argparse, json, os, sys, time, np, ROOT, BENCH_PY, the roofline constants, emit, usable_cpus ...)
+from .common import dump_outputs
 from .rccl import rccl_probe
 
 
 def bench_metric(args, torch, dist, world, rank, local_rank, dev):
-    """the metric configuration: 120 000-point scans against the 1e7-point map, the batched engine timed; on one GPU also the CPU baselines, the parity legs
-    and (--secondary) the other BASELINE configurations as child processes"""
+    """the metric configuration: 120 000-point scans against the 1e7-point map, the batched engine timed on exactly --steps scans.  --full: beside it the
+    pose check, the latencies, the upload-included leg, the roofline, the CPU baselines, the parity legs and (--secondary) the other BASELINE
+    configurations as child processes"""
     from lsd_amd import lio, synth
 
     # ---- synthetic workload (SURVEY.md section 8d, config 2 scaled to the metric's 1e7-point map) -------------
@@ -38,7 +40,7 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
         return pool
 
     scans = make_pool(args.scan_pool, args.spread, args.seed)           # the timed workload: poses all over the 200 m map
-    scans8 = make_pool(8, 4.0, args.seed + 500) if (rank == 0 and args.secondary) else []  # round 3's workload (8 scans within 4 m of one spot), timed beside it
+    scans8 = make_pool(8, 4.0, args.seed + 500) if (rank == 0 and args.full and args.secondary) else []  # round 3's workload (8 scans within 4 m of one spot), timed beside it
     n_raw = int(np.mean([len(s["raw"]) for s in scans]))
 
     the_map = lio.Map(resolution=0.5, stencil=19, max_points=max(args.map_points, 1_000_000), max_voxels=max(args.map_points // 4, 1_000_000),
@@ -46,7 +48,7 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
     # the map goes to HBM once; the raw scans live in torch tensors on the device (inputs resident before timing)
     torch.cuda.synchronize()
     the_map.add_device(d_map.data_ptr(), args.map_points)
-    map_pts = d_map.cpu().numpy() if (rank == 0 and world == 1 and (args.cpu_scans > 0 or args.ref_scans > 0)) else None  # the CPU baselines' copy
+    map_pts = d_map.cpu().numpy() if (args.full and rank == 0 and world == 1 and (args.cpu_scans > 0 or args.ref_scans > 0)) else None  # the CPU baselines' copy
     del d_map
     d_scans = [s["d"] for s in scans]
     torch.cuda.synchronize()
@@ -78,27 +80,34 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
     # Setup, untimed: push enough launches through every engine's stream for the HIP runtime to finish growing its
     # per-queue pools -- a one-off ~35 ms stall shows up after roughly 190 scans (~5 000 kernel launches) of a fresh
     # process and never again (tools/experiments/README.md); a service hits it once at start-up.
-    prime = [dict(dptr=d_scans[i % len(scans)].data_ptr(), n=len(scans[i % len(scans)]["raw"]), t=1.0 + 0.1 * i, state=scans[i % len(scans)]["guess"],
-                  cov=P0) for i in range(40 * n_streams)]
-    run_jobs(prime)
-    torch.cuda.synchronize()
-    for i in range(args.warmup):
-        step(i, engines[i % n_streams])
-    # pose check outside the timed region: every pooled scan must land on its true pose
-    pose_err, ang_err = 0.0, 0.0
-    for k in range(len(scans)):
-        step(k)
-        st = eng.get_state()
-        pose_err = max(pose_err, float(np.linalg.norm(st[:3] - scans[k]["pos"])))
-        ang_err = max(ang_err, float(synth.quat_angle(st[3:7], scans[k]["q"])))
+    # The batched engine's first calls instantiate a graph per round in flight: the setup pushes two full sets of rounds through it.
+    def job_of(i, pool=None):
+        s = (pool or scans)[i % len(pool or scans)]
+        return dict(dptr=s["d"].data_ptr(), n=len(s["raw"]), t=1.0 + 0.1 * i, state=s["guess"], cov=P0)
 
-    # single-stream latency of one scan (reported beside the throughput; not the timed region)
+    run_jobs([job_of(i) for i in range(max(40 * n_streams, 2 * args.slots * args.groups if batch is not None else 0))])
     torch.cuda.synchronize()
-    l0 = time.perf_counter()
-    for i in range(20):
-        step(i)
-    latency_ms = 1e3 * (time.perf_counter() - l0) / 20
-    if batch is None:
+    if args.warmup > 0:  # --warmup scans through the timed path itself
+        lio.run_prepared(lio.PreparedJobs([job_of(i) for i in range(args.warmup)]), engines=engines, batch=batch)
+        torch.cuda.synchronize()
+    pose_err, ang_err, latency_ms = 0.0, 0.0, None
+    if args.full:
+        for i in range(args.warmup):
+            step(i, engines[i % n_streams])
+        # pose check outside the timed region: every pooled scan must land on its true pose
+        for k in range(len(scans)):
+            step(k)
+            st = eng.get_state()
+            pose_err = max(pose_err, float(np.linalg.norm(st[:3] - scans[k]["pos"])))
+            ang_err = max(ang_err, float(synth.quat_angle(st[3:7], scans[k]["q"])))
+
+        # single-stream latency of one scan (reported beside the throughput; not the timed region)
+        torch.cuda.synchronize()
+        l0 = time.perf_counter()
+        for i in range(20):
+            step(i)
+        latency_ms = 1e3 * (time.perf_counter() - l0) / 20
+    if args.full and batch is None:
         for e in engines:
             e.scan.enable_kernel_timing(1)  # the dominant kernel only: two event records per kNN launch in the timed region
             e.scan.kernel_times(reset=True)
@@ -110,17 +119,12 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
         torch.cuda.synchronize()
 
     # the timed region is ONE C-ABI call: the K = --steps independent scans (each with its own initial state / covariance), handed to
-    # the device in batches by C++ (no Python in the loop).  K scans take a few milliseconds; so that the clock is not measuring
-    # start-up effects the same list is repeated R times inside the call (R from an untimed calibration pass), ms_per_step = t / (K R).
-    def job_of(i, pool=None):
-        s = (pool or scans)[i % len(pool or scans)]
-        return dict(dptr=s["d"].data_ptr(), n=len(s["raw"]), t=1.0 + 0.1 * i, state=s["guess"], cov=P0)
-
-    jobs = [job_of(i) for i in range(args.steps)]
+    # the device in batches by C++ (no Python in the loop), ms_per_step = t / K.  --min-seconds S > 0: the same list is repeated R times
+    # inside the call instead, R from an untimed calibration pass so that the region lasts at least S, and ms_per_step = t / (K R).
     # ... and of the same scans one at a time through a ONE-slot batch: the whole registration (downsample chain, five passes of search / linearise /
     # filter step on the device) as one captured graph and one hipGraphLaunch, against the host-driven per-pass loop above
     latency_graph_ms = None
-    if rank == 0 and world == 1 and args.secondary:  # (not in the short forms the profiling passes run: its one-slot launches would enter their per-kernel averages)
+    if rank == 0 and world == 1 and args.full and args.secondary:  # (not in the short forms the profiling passes run: its one-slot launches would enter their per-kernel averages)
         try:
             b1 = lio.Batch(the_map, n_slots=1, n_groups=1, max_raw=1 << 17, max_ds=100000)
             for i in range(4):
@@ -133,21 +137,24 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
         except Exception:
             latency_graph_ms = None
 
-    # calibration pass: long enough to fill every round in flight several times (a list shorter than slots x groups runs un-pipelined and
-    # over-estimates the time per scan: round 4's first line had a 1.4 s region for --min-seconds 5)
-    n_cal = max(8 * args.steps, 6 * args.slots * args.groups if batch is not None else 8 * n_streams)
-    cal = lio.PreparedJobs([job_of(i) for i in range(n_cal)])
-    lio.run_prepared(cal, engines=engines, batch=batch)  # (once untimed: graphs instantiated, pools grown)
-    torch.cuda.synchronize()
-    c0 = time.perf_counter()
-    lio.run_prepared(cal, engines=engines, batch=batch)
-    torch.cuda.synchronize()
-    t_cal = max(time.perf_counter() - c0, 1e-6) * args.steps / n_cal  # seconds per --steps scans
-    repeats = max(1, int(np.ceil(1.1 * args.min_seconds / t_cal)))
-    if dist is not None:  # the same R on every rank
-        tr = torch.tensor([float(repeats)], device=dev, dtype=torch.float64)
-        dist.all_reduce(tr, op=dist.ReduceOp.MAX)
-        repeats = int(tr.item())
+    repeats = 1
+    min_seconds = args.min_seconds or 0.0
+    if min_seconds > 0:
+        # calibration pass: long enough to fill every round in flight several times (a list shorter than slots x groups runs un-pipelined and
+        # over-estimates the time per scan: round 4's first line had a 1.4 s region for --min-seconds 5)
+        n_cal = max(8 * args.steps, 6 * args.slots * args.groups if batch is not None else 8 * n_streams)
+        cal = lio.PreparedJobs([job_of(i) for i in range(n_cal)])
+        lio.run_prepared(cal, engines=engines, batch=batch)  # (once untimed: graphs instantiated, pools grown)
+        torch.cuda.synchronize()
+        c0 = time.perf_counter()
+        lio.run_prepared(cal, engines=engines, batch=batch)
+        torch.cuda.synchronize()
+        t_cal = max(time.perf_counter() - c0, 1e-6) * args.steps / n_cal  # seconds per --steps scans
+        repeats = max(1, int(np.ceil(1.1 * min_seconds / t_cal)))
+        if dist is not None:  # the same R on every rank
+            tr = torch.tensor([float(repeats)], device=dev, dtype=torch.float64)
+            dist.all_reduce(tr, op=dist.ReduceOp.MAX)
+            repeats = int(tr.item())
     # K x R jobs walking through the WHOLE pool (job i = scan i mod pool): with --steps 20 the list used to be the first 20 scans repeated R times
     timed_jobs = [job_of(i) for i in range(args.steps * repeats)]
     prep = lio.PreparedJobs(timed_jobs)  # marshalled into the C ABI's job array BEFORE the clock starts: the timed region is the one C call
@@ -176,14 +183,23 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
         tp = torch.tensor([float(acc["pts"])], device=dev, dtype=torch.float64)
         dist.all_reduce(tp, op=dist.ReduceOp.SUM)
         total_pts = float(tp.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results, len(scans))
 
     cand = the_map.knn_candidates - cand0
     S = 19
+    n_ds_avg, n_pass_avg, n_knn_avg = acc["n_ds"] / n_timed, acc["n_pass"] / n_timed, acc["n_knn"] / n_timed
+    # the checks below take scan i of the pool from job i of the timed call; a call shorter than the pool is completed by an untimed one
+    pool_results = results[: len(scans)]
+    if args.full and len(pool_results) < len(scans):
+        rest = lio.PreparedJobs([job_of(i) for i in range(len(pool_results), len(scans))])
+        lio.run_prepared(rest, engines=engines, batch=batch)
+        pool_results = pool_results + rest.results()
     # ---- the same workload with the upload INCLUDED (t_scan upload excluded and included, both reported): the pool's clouds in
     # page-locked HOST memory, every job LIO_JOB_HOST_RAW -- the library copies a round's clouds to HBM on the round's stream, beside the kernels of the
     # other rounds in flight (the reference's path starts with this copy: slam/src/py_utils.cpp:149-181, slam_wrapper.cpp:64-84).  Same C call, same jobs.
     upload = None
-    if batch is not None and args.upload_scans != 0:
+    if args.full and batch is not None and args.upload_scans != 0:
         try:
             pinned = [lio.PinnedCloud(sc["raw"]) for sc in scans]
 
@@ -191,7 +207,7 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
                 sc, pc = scans[i % len(scans)], pinned[i % len(scans)]
                 return dict(dptr=pc.ptr, n=pc.n, t=1.0 + 0.1 * i, state=sc["guess"], cov=P0, flags=lio.JOB_HOST_RAW)
 
-            n_up = args.upload_scans if args.upload_scans > 0 else int(min(n_timed, max(4 * args.slots * args.groups, np.ceil(2.5 / max(t_local / n_timed, 3.5e-5)))))
+            n_up = args.upload_scans if args.upload_scans > 0 else int(max(4 * args.slots * args.groups, np.ceil(2.5 / max(t_local / n_timed, 3.5e-5))))
             lio.run_prepared(lio.PreparedJobs([job_host(i) for i in range(2 * args.slots * args.groups)]), batch=batch)  # (raw rings allocated, untimed)
             prep_up = lio.PreparedJobs([job_host(i) for i in range(n_up)])
             barrier()
@@ -200,7 +216,7 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
             torch.cuda.synchronize()
             t_up = time.perf_counter() - u0
             res_up = prep_up.results()
-            same_up = rc_up == 0 and all(r["rc"] == 3 and np.array_equal(r["state"], results[i % len(scans)]["state"]) for i, r in enumerate(res_up))
+            same_up = rc_up == 0 and all(r["rc"] == 3 and np.array_equal(r["state"], pool_results[i % len(scans)]["state"]) for i, r in enumerate(res_up))
             bytes_up = float(sum(16 * len(scans[i % len(scans)]["raw"]) for i in range(n_up)))
             if dist is not None:
                 tu = torch.tensor([t_up], device=dev, dtype=torch.float64)
@@ -214,7 +230,6 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
             del prep_up, pinned
         except Exception as ex:  # the headline must not depend on this leg
             upload = {"error": repr(ex)[-300:]}
-    n_ds_avg = acc["n_ds"] / n_timed
     # ---- roofline of the dominant kernel (stencil kNN) ------------------------------------------------------------------------------
     # algorithmic bytes [SURVEY.md 8d]: B_knn = N_ds * (16 query + 16 * S slot probes) + 16 * (points resident in the probed voxels), per
     # scan and neighbour-search pass; the kernel's time from HIP events recorded on the streams it is launched on.  Timed OUTSIDE the
@@ -323,88 +338,89 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
                          "not read, may exceed 1.  frac_touched = the bytes the exactly pruned sweep asks for.  frac_valu = VALU wave-instructions per launch "
                          "over the measured issue rate (tools/valu_peak/valu_peak.hip, run in this process)")
 
-    if batch is not None:
-        leg = solo_leg(the_map, [job_of(i) for i in range(max(args.slots * 8, len(scans)))])
-        iso_us, iso_bytes, iso_launches, others, touched_bytes = leg["us"], leg["bytes"], leg["launches"], leg["others"], leg["touched_bytes"]
-        timed_region = None
-    else:
-        kt = dict(knn_us=0.0, linearize_us=0.0, finalize_us=0.0, knn_launches=0, linearize_launches=0, finalize_launches=0)
-        for e in engines:
-            k1 = e.scan.kernel_times(reset=True)
-            for k in kt:
-                kt[k] += k1[k]
-            e.scan.enable_kernel_timing(0)
-        eng.scan.enable_kernel_timing(1)
-        eng.scan.kernel_times(reset=True)
-        cand1 = the_map.knn_candidates
-        for i in range(32):
-            step(i)
-        k1 = eng.scan.kernel_times(reset=True)
-        iso_launches = max(int(k1["knn_launches"]), 1)
-        iso_us = k1["knn_us"] / iso_launches
-        iso_bytes = n_ds_avg * (16 + 16 * S) + 16.0 * (the_map.knn_candidates - cand1) / iso_launches
-        eng.scan.enable_kernel_timing(2)
-        eng.scan.kernel_times(reset=True)
-        for i in range(16):
-            step(i)
-        k2 = eng.scan.kernel_times(reset=True)
-        eng.scan.enable_kernel_timing(0)
-        others = {"linearize+report": round(k2["linearize_us"] / max(k2["linearize_launches"], 1), 2)}
-        launches = max(int(kt["knn_launches"]), 1)
-        knn_bytes = n_ds_avg * (16 + 16 * S) + 16.0 * cand / launches
-        knn_us = kt["knn_us"] / launches
-        shared = knn_bytes / (knn_us * 1e-6) / 1e9 if knn_us > 0 else 0.0
-        timed_region = {"avg_launch_us": round(knn_us, 2), "launches": launches, "achieved": round(shared, 1), "frac": round(shared / HBM_PEAK_GBS, 4),
-                        "streams": n_streams}
-        kernel_name = "knn_kernel<2, 0> (16 lanes per query)"
-    achieved = iso_bytes / (iso_us * 1e-6) / 1e9 if iso_us > 0 else 0.0
-    # ---- the whole scan against the roofline, as SURVEY.md 8d defines it: B_scan = B_ds + n_knn B_knn + n_pass B_lin (+ B_ins, none against a
-    # static map) over the scan's wall time in the timed region ----
-    n_pass_avg, n_knn_avg = acc["n_pass"] / n_timed, acc["n_knn"] / n_timed
-    b_ds = 16.0 * n_raw + 16.0 * n_ds_avg
-    b_knn = n_ds_avg * (16 + 16 * S) + 16.0 * cand / max(acc["n_knn"], 1)
-    b_lin = n_ds_avg * (16 + 5 * 16) + 16.0 * n_ds_avg + 8 * 32 * np.ceil(n_ds_avg / 64)
-    b_scan = b_ds + n_knn_avg * b_knn + n_pass_avg * b_lin
-    # the device's own copy rate (report the fraction of the nominal AND of a measured peak): 1 GiB device-to-device copies,
-    # read + write counted, torch events on torch's stream (nothing of the hot path is in flight here)
-    copy_peak = None
-    try:
-        nbytes = 1 << 30
-        src = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        dst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        for _ in range(3):
-            dst.copy_(src)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            dst.copy_(src)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_peak = round(2.0 * nbytes * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-        del src, dst
-    except Exception:
+    roofline = None
+    if args.full:
+        if batch is not None:
+            leg = solo_leg(the_map, [job_of(i) for i in range(max(args.slots * 8, len(scans)))])
+            iso_us, iso_bytes, iso_launches, others, touched_bytes = leg["us"], leg["bytes"], leg["launches"], leg["others"], leg["touched_bytes"]
+            timed_region = None
+        else:
+            kt = dict(knn_us=0.0, linearize_us=0.0, finalize_us=0.0, knn_launches=0, linearize_launches=0, finalize_launches=0)
+            for e in engines:
+                k1 = e.scan.kernel_times(reset=True)
+                for k in kt:
+                    kt[k] += k1[k]
+                e.scan.enable_kernel_timing(0)
+            eng.scan.enable_kernel_timing(1)
+            eng.scan.kernel_times(reset=True)
+            cand1 = the_map.knn_candidates
+            for i in range(32):
+                step(i)
+            k1 = eng.scan.kernel_times(reset=True)
+            iso_launches = max(int(k1["knn_launches"]), 1)
+            iso_us = k1["knn_us"] / iso_launches
+            iso_bytes = n_ds_avg * (16 + 16 * S) + 16.0 * (the_map.knn_candidates - cand1) / iso_launches
+            eng.scan.enable_kernel_timing(2)
+            eng.scan.kernel_times(reset=True)
+            for i in range(16):
+                step(i)
+            k2 = eng.scan.kernel_times(reset=True)
+            eng.scan.enable_kernel_timing(0)
+            others = {"linearize+report": round(k2["linearize_us"] / max(k2["linearize_launches"], 1), 2)}
+            launches = max(int(kt["knn_launches"]), 1)
+            knn_bytes = n_ds_avg * (16 + 16 * S) + 16.0 * cand / launches
+            knn_us = kt["knn_us"] / launches
+            shared = knn_bytes / (knn_us * 1e-6) / 1e9 if knn_us > 0 else 0.0
+            timed_region = {"avg_launch_us": round(knn_us, 2), "launches": launches, "achieved": round(shared, 1), "frac": round(shared / HBM_PEAK_GBS, 4),
+                            "streams": n_streams}
+            kernel_name = "knn_kernel<2, 0> (16 lanes per query)"
+        achieved = iso_bytes / (iso_us * 1e-6) / 1e9 if iso_us > 0 else 0.0
+        # ---- the whole scan against the roofline, as SURVEY.md 8d defines it: B_scan = B_ds + n_knn B_knn + n_pass B_lin (+ B_ins, none against a
+        # static map) over the scan's wall time in the timed region ----
+        b_ds = 16.0 * n_raw + 16.0 * n_ds_avg
+        b_knn = n_ds_avg * (16 + 16 * S) + 16.0 * cand / max(acc["n_knn"], 1)
+        b_lin = n_ds_avg * (16 + 5 * 16) + 16.0 * n_ds_avg + 8 * 32 * np.ceil(n_ds_avg / 64)
+        b_scan = b_ds + n_knn_avg * b_knn + n_pass_avg * b_lin
+        # the device's own copy rate (report the fraction of the nominal AND of a measured peak): 1 GiB device-to-device copies,
+        # read + write counted, torch events on torch's stream (nothing of the hot path is in flight here)
         copy_peak = None
-    t_scan = t_max / n_timed
-    if batch is not None:
-        roofline = knn_roofline(leg, "knn_batch_traffic.json")
-    else:
-        roofline = dict(bound="hbm", kernel=kernel_name, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4),
-                        traffic=None, algorithmic_bytes_per_launch=int(iso_bytes), avg_launch_us=round(iso_us, 2), launches=iso_launches, per_stream=timed_region)
-    roofline.update(measured_copy_peak=copy_peak, frac_of_measured_copy_peak=(round(roofline["achieved"] / copy_peak, 4) if copy_peak else None),
-                    timed_region=round(t_max, 4), timed_region_s=round(t_max, 4), other_kernels_us=others,
-                    whole_scan={"algorithmic_bytes_per_scan": int(b_scan), "seconds_per_scan": t_scan, "credit_GBps": round(b_scan / t_scan / 1e9, 1),
-                                "credit_over_peak": round(b_scan / t_scan / 1e9 / HBM_PEAK_GBS, 4),
-                                "what": "SURVEY 8d's bytes of the REFERENCE algorithm per scan (every point of the 19 stencil voxels of every query counted) over "
-                                        "the scan's wall time: credit for work the exactly pruned, cache-shared sweep does not do -- NOT a bandwidth utilisation (the "
-                                        "kernels' own are roofline.frac and configs.*.roofline)",
-                                "terms": {"B_ds": int(b_ds), "B_knn": int(b_knn), "n_knn": round(n_knn_avg, 2), "B_lin": int(b_lin), "n_pass": round(n_pass_avg, 2),
-                                          "B_ins": 0, "note": "B_ins = 0: the metric's map is static (BASELINE config 2 / the headline: independent scans against a "
-                                                              "fixed map, no map_incremental); the insert is timed in configs.config3_* and configs.sequence_batch"}})
+        try:
+            nbytes = 1 << 30
+            src = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            dst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            for _ in range(3):
+                dst.copy_(src)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_peak = round(2.0 * nbytes * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+            del src, dst
+        except Exception:
+            copy_peak = None
+        t_scan = t_max / n_timed
+        if batch is not None:
+            roofline = knn_roofline(leg, "knn_batch_traffic.json")
+        else:
+            roofline = dict(bound="hbm", kernel=kernel_name, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4),
+                            traffic=None, algorithmic_bytes_per_launch=int(iso_bytes), avg_launch_us=round(iso_us, 2), launches=iso_launches, per_stream=timed_region)
+        roofline.update(measured_copy_peak=copy_peak, frac_of_measured_copy_peak=(round(roofline["achieved"] / copy_peak, 4) if copy_peak else None),
+                        timed_region=round(t_max, 4), timed_region_s=round(t_max, 4), other_kernels_us=others,
+                        whole_scan={"algorithmic_bytes_per_scan": int(b_scan), "seconds_per_scan": t_scan, "credit_GBps": round(b_scan / t_scan / 1e9, 1),
+                                    "credit_over_peak": round(b_scan / t_scan / 1e9 / HBM_PEAK_GBS, 4),
+                                    "what": "SURVEY 8d's bytes of the REFERENCE algorithm per scan (every point of the 19 stencil voxels of every query counted) over "
+                                            "the scan's wall time: credit for work the exactly pruned, cache-shared sweep does not do -- NOT a bandwidth utilisation (the "
+                                            "kernels' own are roofline.frac and configs.*.roofline)",
+                                    "terms": {"B_ds": int(b_ds), "B_knn": int(b_knn), "n_knn": round(n_knn_avg, 2), "B_lin": int(b_lin), "n_pass": round(n_pass_avg, 2),
+                                              "B_ins": 0, "note": "B_ins = 0: the metric's map is static (BASELINE config 2 / the headline: independent scans against a "
+                                                                  "fixed map, no map_incremental); the insert is timed in configs.config3_* and configs.sequence_batch"}})
 
     # ---- CPU baseline: the oracle restatement of the same path on a bounded sample of the same workload ---------
     cpu = None
     batch_vs_oracle = None
-    if rank == 0 and world == 1 and args.cpu_scans > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_scans > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle  # test infrastructure; used here only as the timed CPU baseline / checker
 
@@ -433,10 +449,10 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
                 sg, so = eng.get_state(), o.get_state()
                 worst_dp = max(worst_dp, float(np.linalg.norm(sg[:3] - so[:3])))
                 worst_da = max(worst_da, float(synth.quat_angle(sg[3:7], so[3:7])))
-                if batch is not None and i < len(results):
+                if batch is not None and i < len(pool_results):
                     # ... and the TIMED path itself: the state the batched engine returned for this scan inside the timed region (job i of the timed
                     # list = scan i of the pool; jobs are independent scans, so every later repeat of it must carry the same bits -- checked below)
-                    rb = results[i]
+                    rb = pool_results[i]
                     if (rb["n_pass"], rb["n_knn_pass"]) != (len(lo_passes), sum(p["knn"] for p in lo_passes)):
                         pass_mismatch.append([i, rb["n_pass"], rb["n_knn_pass"], len(lo_passes), sum(p["knn"] for p in lo_passes)])
                     batch_dp = max(batch_dp, float(np.linalg.norm(rb["state"][:3] - so[:3])))
@@ -445,7 +461,7 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
                     batch_checked += 1
         batch_vs_oracle = None
         if batch is not None:
-            same = all(np.array_equal(results[i]["state"], results[i % len(scans)]["state"]) for i in range(len(results)))
+            same = all(np.array_equal(results[i]["state"], pool_results[i % len(scans)]["state"]) for i in range(len(results)))
             batch_vs_oracle = {"max_dpos_m": batch_dp, "max_drot_rad": batch_da, "max_dstate": batch_ds, "scans_checked": batch_checked,
                                "all_timed_results_bit_identical_to_the_checked_ones": bool(same), "timed_results": len(results),
                                "pass_structure_mismatches": pass_mismatch, "parity_ok": bool(same and batch_ds <= 1e-9 and not pass_mismatch),
@@ -544,7 +560,7 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
 
     # ---- secondary configurations (BASELINE.json configs 2 and 3), outside the timed region, reported under `configs` ----
     configs = None
-    if rank == 0 and world == 1 and args.secondary and batch is not None:
+    if args.full and rank == 0 and world == 1 and args.secondary and batch is not None:
         configs = {}
         def timed_leg(b_, jl, seconds):
             """jl through the batch b_ once to warm, then repeated for about `seconds`: (ms per scan, points/s, results of the first pass)"""
@@ -676,7 +692,7 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
     # config 5's joint registration runs on) is brought up once OUTSIDE the timed region and its small-message all-gather timed, so that a
     # multi-GPU run leaves a measured collective latency and the communicator's own rank count in the line
     collective = None
-    if dist is not None:
+    if args.full and dist is not None:
         try:
             collective = rccl_probe(dist, rank, world, local_rank)
         except Exception as ex:  # the probe must never cost the run its line
@@ -700,11 +716,11 @@ def bench_metric(args, torch, dist, world, rank, local_rank, dev):
                        "map_bytes_hbm": the_map.nbytes,
                        "engine": ("batched: %d scans per launch, %d rounds in flight, filter loop on the device, 1 host thread" % (args.slots, args.groups))
                                  if batch is not None else ("%d engines, one host thread + stream each" % n_streams),
-                       "single_stream_latency_ms_per_scan": round(latency_ms, 4),
+                       "single_stream_latency_ms_per_scan": (round(latency_ms, 4) if latency_ms is not None else None),
                        "single_scan_one_graph_latency_ms": (round(latency_graph_ms, 4) if latency_graph_ms else None)},
             "pose_error_vs_truth": {"max_dpos_m": pose_err, "max_drot_rad": ang_err,
                                     "note": "the reference's algorithm itself: at most four ESKF iterations from a prior 0.3 m / 2 deg off; the GPU pose "
-                                            "equals the oracle's and the reference's own (cpu_baseline.gpu_vs_*_pose)"},
+                                            "equals the oracle's and the reference's own (cpu_baseline.gpu_vs_*_pose)"} if args.full else None,
             "batch_vs_oracle_pose": batch_vs_oracle, "upload_included": upload, "roofline": roofline, "cpu_baseline": cpu, "configs": configs,
         }
         emit(out, "metric")

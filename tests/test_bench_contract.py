@@ -265,3 +265,27 @@ def test_round6_record_carries_the_parity_figures_the_verdict_asked_for():
     assert e["scans"] == 64 and e["inside_in_translation"] >= 60 and e["reference_envelope_m"]["median"] > e["hip_to_nearest_reference_run_m"]["median"]
     assert json.loads(open(os.path.join(ROOT, "profiles", "r06_bench.json")).read())["ms_per_step"] == j["ms_per_step"]
     assert len(open(os.path.join(ROOT, "profiles", "r06_bench.json")).read()) <= 6000
+
+
+def test_dump_outputs_writes_what_the_timed_call_returned(tmp_path):
+    """--dump-outputs DIR (metric config): the last step's state_out and counts, and those of the last min(steps, pool) steps, as float64 .npy
+    files; --full is the switch of everything beside the headline"""
+    import sys
+
+    import numpy as np
+
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert re.search(r'"--full", action="store_true"', src) and re.search(r'"--dump-outputs", default=None', src)
+    sys.path.insert(0, ROOT)
+    from benchlegs.common import dump_outputs
+
+    rng = np.random.default_rng(0)
+    results = [dict(rc=3, n_ds=1000 + i, n_pass=4, n_knn_pass=3, state=rng.normal(size=26)) for i in range(300)]
+    for n, pool in ((300, 128), (20, 128)):
+        d = tmp_path / f"d{n}"
+        dump_outputs(str(d), results[:n], pool)
+        got = {f.stem: np.load(f) for f in d.iterdir()}
+        assert set(got) == {"last_state", "last_counts", "pool_states", "pool_counts"} and all(a.dtype == np.float64 for a in got.values())
+        k = min(n, pool)
+        assert np.array_equal(got["last_state"], results[n - 1]["state"]) and got["last_counts"].tolist() == [3, 1000 + n - 1, 4, 3]
+        assert np.array_equal(got["pool_states"], np.stack([r["state"] for r in results[n - k:n]])) and got["pool_counts"].shape == (k, 4)

@@ -2,11 +2,12 @@
 # quick A/B of an environment knob of the library: bash tools/experiments/ab_env.sh VAR v1 v2 ...   ("-" = unset)
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; mkdir -p gpurun_out/abe
+OUT=${OUT:-bench_out/abe}; mkdir -p $OUT
 VAR=$1; shift
 for rep in 1 2; do
 for V in "$@"; do
 if [ "$V" = "-" ]; then unset $VAR; else export $VAR=$V; fi
-timeout 300 python bench.py --steps 20 --warmup 5 --secondary 0 --min-seconds 3 --cpu-scans 0 --ref-scans 0 --upload-scans 0 > gpurun_out/abe/b.json 2> gpurun_out/abe/b.err
+timeout 300 python bench.py --steps 20 --warmup 5 --secondary 0 --min-seconds 3 --cpu-scans 0 --ref-scans 0 --upload-scans 0 --full > $OUT/b.json 2> $OUT/b.err
 python - <<PY
 import json
 try:

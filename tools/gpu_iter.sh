@@ -11,7 +11,7 @@ cd $R
 export TMPDIR=/tmp
 TESTS=${1:-tests/test_gpu_parity.py tests/test_batch_gpu.py tests/test_voxelgrid_vs_ref.py tests/test_voxelgrid_monster_gpu.py}
 timeout 800 python -m pytest $TESTS -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?"; tail -3 $O/pytest.log
-timeout 240 python bench.py --steps 20 --warmup 5 --secondary 0 --min-seconds 2 --cpu-scans 0 --ref-scans 0 --upload-scans 0 > $O/bench.json 2> $O/bench.err
+timeout 240 python bench.py --steps 20 --warmup 5 --secondary 0 --min-seconds 2 --cpu-scans 0 --ref-scans 0 --upload-scans 0 --full > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 d = json.load(open("$R/bench_full.json")); r = d["roofline"]
@@ -19,7 +19,7 @@ print("ms/scan", d["ms_per_step"], "single-stream latency", d["config"].get("sin
 PY
 if [ "$2" = "profile" ]; then
     cd /tmp
-    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r -- python $R/bench.py --steps 20 --warmup 5 --secondary 0 --groups 1 --min-seconds 1 --cpu-scans 0 --ref-scans 0 > $O/one_round.json 2> $O/prof.err
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r -- python $R/bench.py --steps 20 --warmup 5 --secondary 0 --groups 1 --min-seconds 1 --cpu-scans 0 --ref-scans 0 --full > $O/one_round.json 2> $O/prof.err
     find $O/prof -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_one_round_in_flight.csv \;
     rm -rf $O/prof
     python - <<PY
