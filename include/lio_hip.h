@@ -54,8 +54,9 @@ int lio_device_count(void);
  * calls a revision-4 library is written past -- rebuild, or check the revision and allocate sizeof(lio_batch_times) of THIS header;
  * lio_timings.n_added may be -1 = "insert still in flight, not read back"; lio_engine_timings may return a deferred LIO_E_CAPACITY);
  * 5 = round 5 (LIO_JOB_HOST_RAW, lio_pinned_alloc / lio_pinned_free, lio_abi_version itself);
- * 6 = round 6 (lio_map_set_tie_mode / lio_map_tie_stats: candidates exactly as far as the fifth nearest are now kept as the reference keeps them). */
-#define LIO_ABI_VERSION 6
+ * 6 = round 6 (lio_map_set_tie_mode / lio_map_tie_stats: candidates exactly as far as the fifth nearest are now kept as the reference keeps them);
+ * 7 = lio_cloud_* (the dense-map export: a device-resident cloud that grows over a drive, and the VoxelGrid of the whole cloud). */
+#define LIO_ABI_VERSION 7
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -699,6 +700,38 @@ int lio_localmap_num_keyframes(lio_localmap*);
 int lio_localmap_update(lio_localmap*, lio_ndt* target, const double pose_xyz[3], double update_distance, double radius, double key_frame_distance,
                         float leaf, int* n_keyframes, uint32_t* n_points);
 int lio_localmap_download(lio_localmap*, float* out_xyzi, uint32_t cap);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Dense-map export on the device: one cloud that grows over a drive (the reference's static g_accumulate_cloud,
+ * slam/src/graph_utils.cpp:410, and g_map_config.points, :152-158), fed frame by frame and filtered as a whole.
+ * The cloud lives in HBM; it grows geometrically when it has to, and a failed allocation returns an error and leaves it
+ * unchanged.  NULL from lio_cloud_create without a device: there is no CPU fallback.
+ * Appends (the per-frame bodies of accumulate_cloud, graph_utils.cpp:423-429, and export_points, :168-178): every point is
+ *   - its intensity multiplied by intensity_scale unless that is 1 (numpy_to_pointcloud(points, 255.0), py_utils.cpp:102-116),
+ *   - transformed by the row-major f64 matrix T as pcl::transformPointCloud(in, out, Matrix4d) does (f64, terms left to right, cast to f32;
+ *     non-finite points too; T = NULL: identity),
+ *   - kept only if z_min <= z <= z_max (compared in f64; NaN z is dropped) when z_band != 0 (export_points, graph_utils.cpp:173),
+ *   - appended in input order.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_cloud lio_cloud;
+lio_cloud* lio_cloud_create(int device, uint64_t reserve_points);
+void lio_cloud_destroy(lio_cloud*);
+int lio_cloud_clear(lio_cloud*);                 /* save_accumulate_cloud's reset, graph_utils.cpp:444 */
+int lio_cloud_size(lio_cloud*, uint64_t* n);
+/* the scan's raw cloud as it stands (after lio_scan_upload and lio_scan_undistort_poses: undistortion_cloud, graph_utils.cpp:384-396); waits
+ * for the append, so the scan may be reused at once */
+int lio_cloud_append_scan(lio_cloud*, lio_scan*, const double T[16], float intensity_scale, int z_band, double z_min, double z_max);
+int lio_cloud_append_host(lio_cloud*, const float* xyzi, uint64_t n, const double T[16], float intensity_scale, int z_band, double z_min, double z_max);
+/* pcl::VoxelGrid::filter with setLeafSize(leaf, leaf, leaf) over the whole cloud, in place (save_accumulate_cloud, graph_utils.cpp:436-441):
+ * the semantics of lio_scan_voxel_downsample (bbox of the finite points, the int32 overflow guard returning the input, one centroid per
+ * occupied voxel as sequential f32 sums in ascending input index, ascending voxel index) for up to 2^31 - 1 points (PCL's int index range;
+ * more: LIO_E_CAPACITY).  The sort scratch is allocated for the call and freed after it; *n_out (may be NULL) = points left. */
+int lio_cloud_voxel_downsample(lio_cloud*, float leaf, uint64_t* n_out);
+int64_t lio_cloud_download(lio_cloud*, float* xyzi, uint64_t cap);   /* the point count, or -(points) when cap is too small */
+int lio_cloud_scratch_bytes(lio_cloud*, uint64_t* bytes);            /* peak device scratch lio_cloud_voxel_downsample takes at the current size */
+/* device time (HIP events on the cloud's stream) of the last append (without the host-to-device copy of lio_cloud_append_host) and of the
+ * last voxel grid (the kernel chain, without the scratch allocation) */
+int lio_cloud_last_times(lio_cloud*, double* append_us, double* voxel_us);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

@@ -12,7 +12,9 @@
 // -- except that the cloud goes numpy -> pinned staging buffer -> HBM in ONE pass (lio_fastlio_pcl_stage / _commit): the static
 // transform and the stamp conversion are applied while copying, the 48-byte PointXYZINormal inflation and the two intermediate
 // PCL clouds of the reference never exist.
-// Off the hot path (graph back end, GNSS, map export, colouration: SURVEY.md section 2 OUT-OF-SCOPE, Appendix B): type-correct minimal
+// The dense-map export (set_export_map_config / export_points / dump_map_points, accumulate_cloud / save_accumulate_cloud,
+// save_undistortion_cloud: graph_utils.cpp:160-200, 384-446) runs on the device over lio_cloud_* (csrc/cloud.hip).
+// Off the hot path (graph back end, GNSS, colouration: SURVEY.md section 2 OUT-OF-SCOPE, Appendix B): type-correct minimal
 // implementations -- empty dict / list, identity 4 x 4, stored-and-returned settings -- so that slam.py and map_manager.py run
 // unchanged.  They are listed in INTEGRATION.md.
 #include <pybind11/numpy.h>
@@ -168,8 +170,6 @@ struct Slam {
     double init_pose[6] = {0, 0, 0, 0, 0, 0};
     std::string dest;
     int dest_port = 0;
-    double export_z[2] = {0, 0};
-    std::string export_color;
     uint64_t max_points = 8000000, max_voxels = 1u << 21;
 };
 std::unique_ptr<Slam> g;  // one global instance per process, like the reference's slam_ptr (slam_wrapper.cpp:4)
@@ -953,9 +953,172 @@ void dump_keyframe(const std::string& directory, uint64_t stamp, int id, py::arr
     write_keyframe_data(directory, stamp, id, T);
 }
 void dump_odometry(const std::string& directory) { (void)directory; }
-void set_export_map_config(double z_min, double z_max, std::string color) { if (g) { g->export_z[0] = z_min; g->export_z[1] = z_max; g->export_color = color; } }
-void export_points(py::array_t<float>& points_input, py::array_t<float>& odom_input) { (void)points_input; (void)odom_input; }
-void dump_map_points(std::string file) { (void)file; }
+// ---- dense-map export (graph_utils.cpp:160-200 and 384-446) over lio_cloud: the frames go to the device, are moved into the world frame there
+// and, for save_accumulate_cloud, filtered as one cloud by the device-wide VoxelGrid ----
+// set_export_map_config / export_points / dump_map_points: the reference keeps g_map_config (a static, independent of the SLAM instance).
+// export_points only keeps host copies of (points, odom): it needs no device, and dump_map_points moves every deferred key frame in one pass.
+struct ExportCfg {
+    double z_min = 0, z_max = 0;  // (zero-initialised static storage in the reference until the first set_export_map_config)
+    std::string color;
+    std::vector<std::vector<float>> points;  // N x 4 as given
+    std::vector<Mat4> odom;
+};
+ExportCfg g_export;
+// accumulate_cloud / save_accumulate_cloud: the reference's static g_accumulate_cloud (graph_utils.cpp:410)
+struct Accumulate {
+    lio_cloud* cloud = nullptr;
+    lio_scan* scan = nullptr;  // the frame being undistorted
+    uint32_t scan_cap = 0;
+};
+Accumulate g_acc;
+
+// numpy N x (>= 4) f32 -> xyzi
+std::vector<float> xyzi_of(py::array_t<float>& input, const char* what) {
+    auto a = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(input);
+    if (!a || a.ndim() != 2 || a.shape(1) < 4) throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": points must be N x 4 float32");
+    const size_t n = (size_t)a.shape(0), cs = (size_t)a.shape(1);
+    std::vector<float> out(4 * n);
+    const float* src = a.data();
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < 4; k++) out[4 * i + k] = src[i * cs + k];
+    return out;
+}
+
+// a general 4 x 4 inverse (adjugate / determinant, f64): odometrys[0].T.inverse() of undistortion_cloud, graph_utils.cpp:391-393
+Mat4 inverse4(const Mat4& A) {
+    const double* m = A.m;
+    double inv[16];
+    inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
+    inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
+    inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
+    inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
+    inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
+    inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
+    inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
+    inv[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
+    inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
+    inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
+    inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
+    inv[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
+    inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
+    inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
+    inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
+    inv[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
+    const double det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12];
+    Mat4 r;
+    for (int i = 0; i < 16; i++) r.m[i] = inv[i] / det;
+    return r;
+}
+
+// numpy_to_odometry (py_utils.cpp:260-270): TUM rows (stamp us, x, y, z, qx, qy, qz, qw); rotation = Eigen::Quaterniond(w, x, y, z) =
+// (col 7, 4, 5, 6), toRotationMatrix as Eigen writes it (Quaternion.h, not normalised)
+struct TumPose {
+    uint64_t stamp;
+    Mat4 T;
+};
+std::vector<TumPose> tum_poses(py::array_t<double>& poses_in) {
+    auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(poses_in);
+    if (!a || a.ndim() != 2 || a.shape(1) < 8) throw std::invalid_argument("slam_wrapper: poses must be N x 8 TUM rows (stamp, x, y, z, qx, qy, qz, qw)");
+    auto r = a.unchecked<2>();
+    std::vector<TumPose> out;
+    for (py::ssize_t i = 0; i < r.shape(0); i++) {
+        TumPose p;
+        p.stamp = (uint64_t)r(i, 0);
+        p.T = Mat4::identity();
+        const double w = r(i, 7), x = r(i, 4), y = r(i, 5), z = r(i, 6);
+        const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+        const double twx = tx * w, twy = ty * w, twz = tz * w;
+        const double txx = tx * x, txy = ty * x, txz = tz * x;
+        const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+        p.T(0, 0) = 1 - (tyy + tzz); p.T(0, 1) = txy - twz; p.T(0, 2) = txz + twy;
+        p.T(1, 0) = txy + twz; p.T(1, 1) = 1 - (txx + tzz); p.T(1, 2) = tyz - twx;
+        p.T(2, 0) = txz - twy; p.T(2, 1) = tyz + twx; p.T(2, 2) = 1 - (txx + tyy);
+        p.T(0, 3) = r(i, 1); p.T(1, 3) = r(i, 2); p.T(2, 3) = r(i, 3);
+        out.push_back(p);
+    }
+    return out;
+}
+// undistortion_cloud's relative poses (graph_utils.cpp:391-393): T_i <- T_0^-1 * T_i (f64), i = 0 included
+std::vector<Mat4> relative_poses(const std::vector<TumPose>& poses) {
+    std::vector<Mat4> rel;
+    if (poses.empty()) return rel;
+    const Mat4 inv0 = inverse4(poses[0].T);
+    for (const TumPose& p : poses) rel.push_back(mul(inv0, p.T));
+    return rel;
+}
+
+// undistortion_cloud (graph_utils.cpp:384-396) on the device: the frame into g_acc.scan, undistortPoints(poses, cloud) there
+// (lio_scan_undistort_poses, slam_utils.cpp:193-228).  Throws on what the reference leaves undefined or this module leaves out.
+void undistort_frame(py::array_t<float>& points, py::dict& points_attr, const std::vector<TumPose>& poses, const char* what) {
+    if (poses.empty()) throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": no poses (the reference indexes an empty pose list)");
+    if (poses.size() > 64) throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": more than 64 poses in one frame are not supported");
+    const std::vector<float> xyzi = xyzi_of(points, what);
+    const size_t n = xyzi.size() / 4;
+    auto attr = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(py::cast<py::array>(points_attr["points_attr"]));
+    if (!attr || attr.ndim() != 2 || attr.shape(1) < 1 || (size_t)attr.shape(0) != n)
+        throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": points_attr must be N x 2 with one row per point");
+    const uint64_t header = py::cast<uint64_t>(points_attr["timestamp"]);
+    std::vector<uint32_t> stamp(n);
+    for (size_t i = 0; i < n; i++) stamp[i] = (uint32_t)attr.data()[i * attr.shape(1)];  // PointAttr::stamp = ref_attr(i, 0)
+    std::vector<uint64_t> ps;
+    std::vector<double> rel;
+    for (const Mat4& T : relative_poses(poses)) rel.insert(rel.end(), T.m, T.m + 16);
+    for (const TumPose& p : poses) ps.push_back(p.stamp);
+    for (size_t i = 2; i < poses.size(); i++)
+        if (ps[i] - header < ps[i - 1] - header)
+            throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": the pose intervals must not end earlier than their predecessors");
+    if (n > 0xFFFFFFFFull) throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": too many points in one frame");
+    if (!g_acc.scan || g_acc.scan_cap < n) {
+        if (g_acc.scan) lio_scan_destroy(g_acc.scan);
+        g_acc.scan_cap = (uint32_t)std::max<size_t>(n, 1 << 17);
+        g_acc.scan = lio_scan_create(0, g_acc.scan_cap, 1024);
+        if (!g_acc.scan) g_acc.scan_cap = 0;
+        require(g_acc.scan != nullptr, "no HIP device for the undistortion");
+    }
+    require(lio_scan_upload(g_acc.scan, xyzi.data(), (uint32_t)n) == LIO_OK, "frame upload failed");
+    require(lio_scan_undistort_poses(g_acc.scan, stamp.data(), 0, header, ps.data(), rel.data(), (uint32_t)ps.size()) == LIO_OK, "undistortion failed");
+}
+
+void set_export_map_config(double z_min, double z_max, std::string color) {
+    g_export = ExportCfg();
+    g_export.z_min = z_min;
+    g_export.z_max = z_max;
+    g_export.color = color;
+}
+void export_points(py::array_t<float>& points_input, py::array_t<float>& odom_input) {
+    if (g_export.color == "rgb") return;  // the colour map is out of scope (get_color_map is empty)
+    auto od = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(odom_input);
+    if (!od || od.size() != 16) throw std::invalid_argument("slam_wrapper: export_points: odom must be 4 x 4");
+    Mat4 T;
+    for (int i = 0; i < 16; i++) T.m[i] = (double)od.data()[i];  // numpy_to_eigen(const py::array_t<float>&) -> Matrix4d
+    g_export.points.push_back(xyzi_of(points_input, "export_points"));
+    g_export.odom.push_back(T);
+}
+void dump_map_points(std::string file) {
+    if (g_export.color == "rgb") return;  // getColorMap: nothing without the colour map, and an empty cloud is not written
+    uint64_t total = 0;
+    for (const auto& p : g_export.points) total += p.size() / 4;
+    if (total == 0) return;
+    lio_cloud* c = lio_cloud_create(0, total);
+    require(c != nullptr, "dump_map_points: no HIP device");
+    std::vector<float> out;
+    int64_t m = 0;
+    for (size_t k = 0; k < g_export.points.size() && m >= 0; k++) {
+        const auto& p = g_export.points[k];
+        if (lio_cloud_append_host(c, p.data(), p.size() / 4, g_export.odom[k].m, 255.0f, 1, g_export.z_min, g_export.z_max) != LIO_OK) m = -1;
+    }
+    uint64_t n = 0;
+    if (m >= 0 && lio_cloud_size(c, &n) == LIO_OK) {
+        out.resize(4 * n + 4);
+        m = lio_cloud_download(c, out.data(), n);
+    } else {
+        m = -1;
+    }
+    lio_cloud_destroy(c);
+    require(m >= 0, "dump_map_points: the device pass failed");
+    if (m == 0) return;
+    require(write_pcd_binary(file, out.data(), (size_t)m), "dump_map_points: cannot write the file");
+}
 py::list dump_graph(const std::string& directory) { (void)directory; return py::list(); }
 py::list align_pose(double stamp1, double stamp2, py::array_t<double>& estimate1_py, py::array_t<double>& estimate2_py, py::array_t<double>& poses_stamp,
                     py::list& poses_py) {
@@ -963,12 +1126,38 @@ py::list align_pose(double stamp1, double stamp2, py::array_t<double>& estimate1
     return poses_py;
 }
 void save_undistortion_cloud(std::string file, py::array_t<float>& points, py::dict& points_attr, py::array_t<double>& poses) {
-    (void)file; (void)points; (void)points_attr; (void)poses;
+    const std::vector<TumPose> tum = tum_poses(poses);
+    undistort_frame(points, points_attr, tum, "save_undistortion_cloud");
+    std::vector<float> out(4 * (size_t)g_acc.scan_cap + 4);
+    const int n = lio_scan_download_raw(g_acc.scan, out.data(), g_acc.scan_cap);
+    require(n >= 0, "save_undistortion_cloud: download failed");
+    if (n == 0) return;  // (savePCDFileBinary refuses an empty cloud)
+    require(write_pcd_binary(file, out.data(), (size_t)n), "save_undistortion_cloud: cannot write the file");
 }
 void accumulate_cloud(py::array_t<float>& points, py::dict& points_attr, py::array_t<double>& poses, std::string odometry_type, bool extract_ground) {
-    (void)points; (void)points_attr; (void)poses; (void)odometry_type; (void)extract_ground;
+    if (odometry_type != "TUM")
+        throw std::invalid_argument("slam_wrapper: accumulate_cloud: odometry_type '" + odometry_type + "' is not supported (only \"TUM\"; the reference indexes an empty pose list)");
+    if (extract_ground)
+        throw std::invalid_argument("slam_wrapper: accumulate_cloud: extract_ground=True is not supported (detect_ground, PCL normals + RANSAC, is out of scope)");
+    const std::vector<TumPose> tum = tum_poses(poses);
+    undistort_frame(points, points_attr, tum, "accumulate_cloud");
+    if (!g_acc.cloud) {
+        g_acc.cloud = lio_cloud_create(0, 0);
+        require(g_acc.cloud != nullptr, "accumulate_cloud: no HIP device");
+    }
+    // pcl::transformPointCloud(*cloud, *transformed, odometrys[0].T) with the absolute pose, then *g_accumulate_cloud += *transformed
+    require(lio_cloud_append_scan(g_acc.cloud, g_acc.scan, tum[0].T.m, 1.0f, 0, 0.0, 0.0) == LIO_OK, "accumulate_cloud: append failed");
 }
-void save_accumulate_cloud(std::string file, double resolution) { (void)file; (void)resolution; }
+void save_accumulate_cloud(std::string file, double resolution) {
+    uint64_t n = 0;
+    if (!g_acc.cloud || lio_cloud_size(g_acc.cloud, &n) != LIO_OK || n == 0) return;
+    if (resolution > 0.0) require(lio_cloud_voxel_downsample(g_acc.cloud, (float)resolution, &n) == LIO_OK, "save_accumulate_cloud: voxel grid failed");
+    std::vector<float> out(4 * (size_t)n + 4);
+    const int64_t m = lio_cloud_download(g_acc.cloud, out.data(), n);
+    require(m >= 0, "save_accumulate_cloud: download failed");
+    lio_cloud_clear(g_acc.cloud);
+    if (m > 0) require(write_pcd_binary(file, out.data(), (size_t)m), "save_accumulate_cloud: cannot write the file");
+}
 void texture_mesh(std::string mesh_path, std::string cloud_path, std::string output_path) { (void)mesh_path; (void)cloud_path; (void)output_path; }
 void set_colouration_config(py::list& cameras) { (void)cameras; }
 void set_map_odometrys(py::array_t<double>& poses) { (void)poses; }
@@ -986,6 +1175,21 @@ py::array_t<double> _transform_from_rpyt(double x, double y, double z, double ya
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++) r(i, j) = T(i, j);
     return a;
+}
+// _tum_relative_poses(poses) -> (T0, [T0^-1 * T_i]): numpy_to_odometry + undistortion_cloud's relative poses, as the module computes them
+py::tuple _tum_relative_poses(py::array_t<double>& poses) {
+    const std::vector<TumPose> tum = tum_poses(poses);
+    auto to_np = [](const Mat4& T) {
+        py::array_t<double> a({4, 4});
+        auto r = a.mutable_unchecked<2>();
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < 4; j++) r(i, j) = T(i, j);
+        return a;
+    };
+    py::list rel;
+    for (const Mat4& T : relative_poses(tum)) rel.append(to_np(T));
+    if (tum.empty()) throw std::invalid_argument("slam_wrapper: _tum_relative_poses: no poses");
+    return py::make_tuple(to_np(tum[0].T), rel);
 }
 void _set_capacity(uint64_t max_points, uint64_t max_voxels) { if (g) { g->max_points = max_points; g->max_voxels = max_voxels; } }
 
@@ -1046,5 +1250,6 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("save_render_cloud", &save_render_cloud, "save render cloud", py::arg("file"));
     m.def("_engine_handle", &_engine_handle);
     m.def("_transform_from_rpyt", &_transform_from_rpyt);
+    m.def("_tum_relative_poses", &_tum_relative_poses, py::arg("poses"));
     m.def("_set_capacity", &_set_capacity, py::arg("max_points"), py::arg("max_voxels"));
 }

@@ -34,6 +34,8 @@ SYMBOLS = [
     "lio_state_boxplus", "lio_state_boxminus",
     "lio_localmap_create", "lio_localmap_destroy", "lio_localmap_add_keyframe", "lio_localmap_num_keyframes", "lio_localmap_update",
     "lio_localmap_download",
+    "lio_cloud_create", "lio_cloud_destroy", "lio_cloud_clear", "lio_cloud_size", "lio_cloud_append_scan", "lio_cloud_append_host",
+    "lio_cloud_voxel_downsample", "lio_cloud_download", "lio_cloud_scratch_bytes", "lio_cloud_last_times",
     "lio_pose_estimator_create", "lio_pose_estimator_destroy", "lio_pose_estimator_predict", "lio_pose_estimator_match", "lio_pose_estimator_match_gps", "lio_pose_estimator_guess", "lio_pose_estimator_observe",
     "lio_pose_estimator_match_gps_only", "lio_pose_estimator_get_timed_pose", "lio_pose_estimator_predict_nostate",
     "lio_pose_estimator_correct", "lio_pose_estimator_get_dt", "lio_pose_estimator_get", "lio_pose_estimator_set", "lio_pose_estimator_matrix",
@@ -224,6 +226,16 @@ def lib():
     sig("lio_localmap_num_keyframes", cint, vp)
     sig("lio_localmap_update", cint, vp, vp, f64p, dbl, dbl, dbl, flt, C.POINTER(cint), C.POINTER(u32))
     sig("lio_localmap_download", cint, vp, f32p, u32)
+    sig("lio_cloud_create", vp, cint, u64)
+    sig("lio_cloud_destroy", None, vp)
+    sig("lio_cloud_clear", cint, vp)
+    sig("lio_cloud_size", cint, vp, C.POINTER(u64))
+    sig("lio_cloud_append_scan", cint, vp, vp, f64p, flt, cint, dbl, dbl)
+    sig("lio_cloud_append_host", cint, vp, f32p, u64, f64p, flt, cint, dbl, dbl)
+    sig("lio_cloud_voxel_downsample", cint, vp, flt, C.POINTER(u64))
+    sig("lio_cloud_download", C.c_int64, vp, f32p, u64)
+    sig("lio_cloud_scratch_bytes", cint, vp, C.POINTER(u64))
+    sig("lio_cloud_last_times", cint, vp, f64p, f64p)
     sig("lio_pose_estimator_create", vp, f32p, u64, f32p, f32p, dbl)
     sig("lio_pose_estimator_destroy", None, vp)
     sig("lio_pose_estimator_predict", cint, vp, u64, f32p, f32p)

@@ -654,6 +654,73 @@ class Gicp:
         return out, bool(conv.value), int(it.value)
 
 
+class Cloud:
+    """lio_cloud: a device-resident cloud that grows over a drive, and pcl::VoxelGrid over all of it (the dense-map export of
+    graph_utils.cpp:160-200, 410-446).  Appends transform (f64, as pcl::transformPointCloud with a Matrix4d), scale the intensity, keep an
+    inclusive z band and keep the input order."""
+
+    def __init__(self, reserve=0, device=0):
+        self.h = lib().lio_cloud_create(device, int(reserve))
+        if not self.h:
+            raise capi.LioError("lio_cloud_create failed: " + lib().lio_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_cloud_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _args(T, intensity_scale, z_band):
+        M = np.eye(4) if T is None else np.ascontiguousarray(T, np.float64).reshape(4, 4)
+        M = np.ascontiguousarray(M, np.float64)
+        band = z_band is not None
+        lo, hi = (float(z_band[0]), float(z_band[1])) if band else (0.0, 0.0)
+        return M, float(intensity_scale), int(band), lo, hi
+
+    def append_host(self, xyzi, T=None, intensity_scale=1.0, z_band=None):
+        p = f32(xyzi).reshape(-1, 4)
+        M, sc, band, lo, hi = self._args(T, intensity_scale, z_band)
+        check(lib().lio_cloud_append_host(self.h, ptr(p, C.c_float), len(p), ptr(M, C.c_double), sc, band, lo, hi), "cloud append_host")
+
+    def append_scan(self, scan, T=None, intensity_scale=1.0, z_band=None):
+        M, sc, band, lo, hi = self._args(T, intensity_scale, z_band)
+        check(lib().lio_cloud_append_scan(self.h, scan.h, ptr(M, C.c_double), sc, band, lo, hi), "cloud append_scan")
+
+    def clear(self):
+        check(lib().lio_cloud_clear(self.h), "cloud clear")
+
+    @property
+    def size(self):
+        n = C.c_uint64(0)
+        check(lib().lio_cloud_size(self.h, C.byref(n)), "cloud size")
+        return int(n.value)
+
+    def voxel_downsample(self, leaf):
+        n = C.c_uint64(0)
+        check(lib().lio_cloud_voxel_downsample(self.h, float(leaf), C.byref(n)), "cloud voxel downsample")
+        return int(n.value)
+
+    def download(self):
+        n = self.size
+        out = np.zeros((n, 4), np.float32)
+        m = lib().lio_cloud_download(self.h, ptr(out, C.c_float), n)
+        check(m if m >= 0 else capi.LIO_E_CAPACITY, "cloud download")
+        return out[:m]
+
+    def scratch_bytes(self):
+        b = C.c_uint64(0)
+        check(lib().lio_cloud_scratch_bytes(self.h, C.byref(b)), "cloud scratch bytes")
+        return int(b.value)
+
+    def last_times(self):
+        """(append_us, voxel_us): device time of the last append and of the last voxel grid"""
+        a, v = C.c_double(0), C.c_double(0)
+        check(lib().lio_cloud_last_times(self.h, C.byref(a), C.byref(v)), "cloud times")
+        return a.value, v.value
+
+
 def transform_cloud_f32(cloud, M):
     """pcl::transformPointCloud(in, out, M) for XYZ(I) points as PCL 1.9.1 evaluates it in f32: xyz = M(0..2, 0..3) * [x y z 1], left to right"""
     c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4).copy()
