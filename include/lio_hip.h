@@ -55,8 +55,9 @@ int lio_device_count(void);
  * lio_timings.n_added may be -1 = "insert still in flight, not read back"; lio_engine_timings may return a deferred LIO_E_CAPACITY);
  * 5 = round 5 (LIO_JOB_HOST_RAW, lio_pinned_alloc / lio_pinned_free, lio_abi_version itself);
  * 6 = round 6 (lio_map_set_tie_mode / lio_map_tie_stats: candidates exactly as far as the fifth nearest are now kept as the reference keeps them);
- * 7 = lio_cloud_* (the dense-map export: a device-resident cloud that grows over a drive, and the VoxelGrid of the whole cloud). */
-#define LIO_ABI_VERSION 7
+ * 7 = lio_cloud_* (the dense-map export: a device-resident cloud that grows over a drive, and the VoxelGrid of the whole cloud);
+ * 8 = lio_knn_index_* (exact k nearest neighbours over a static cloud; texture_mesh). */
+#define LIO_ABI_VERSION 8
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -732,6 +733,30 @@ int lio_cloud_scratch_bytes(lio_cloud*, uint64_t* bytes);            /* peak dev
 /* device time (HIP events on the cloud's stream) of the last append (without the host-to-device copy of lio_cloud_append_host) and of the
  * last voxel grid (the kernel chain, without the scratch allocation) */
 int lio_cloud_last_times(lio_cloud*, double* append_us, double* voxel_us);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * Exact k nearest neighbours over a static cloud: the pcl::KdTreeFLANN<PointXYZRGB> of texture_mesh (slam/src/graph_utils.cpp:449-501,
+ * FLANN's default L2_Simple<float>), as a device index (csrc/knn_index.hip).  NULL from lio_knn_index_create without a device: there is
+ * no CPU fallback.
+ *   - only points with three finite coordinates are indexed (PCL's isFinite filter in setInputCloud); indices refer to the input order;
+ *   - distance = ((dx*dx) + dy*dy) + dz*dz in f32, d = p - q, every operation a separate IEEE operation;
+ *   - the result is the k smallest distances in ascending (d2, index) order: ties at equal f32 distance go to the SMALLER input index
+ *     (the project's rule: FLANN's own order among equal distances depends on its tree);
+ *   - fewer than k indexed points: what there is (FLANN lowers k to the point count); a query with a non-finite coordinate: none;
+ *   - up to 2^31 - 1 input points (PCL's int index; more: LIO_E_CAPACITY), any number of queries (the device takes them in chunks).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_knn_index lio_knn_index;
+lio_knn_index* lio_knn_index_create(int device);
+void lio_knn_index_destroy(lio_knn_index*);
+/* xyz: n x 3 f32 (host); rgb: n packed 0x??RRGGBB words or NULL; *n_finite (may be NULL) = points indexed.  Replaces any earlier build. */
+int lio_knn_index_build(lio_knn_index*, const float* xyz, const uint32_t* rgb, uint64_t n, uint64_t* n_finite);
+/* q: m x 3 f32 (host); 1 <= k <= 8; idx / d2: m x k, ascending (d2, idx); missing slots idx = -1, d2 = +inf */
+int lio_knn_index_query(lio_knn_index*, const float* q, uint64_t m, int k, int32_t* idx, float* d2);
+/* per query: floor(sum / count) of the r, g, b bytes of its (up to) k neighbours; count 0 -> 0, 0, 0.  rgb_out: m x 3 bytes.
+ * LIO_E_STATE when the index holds points but was built without colours. */
+int lio_knn_index_colour(lio_knn_index*, const float* q, uint64_t m, int k, uint8_t* rgb_out);
+/* device time (HIP events on the index's stream, no host copies) of the last build and of the last query / colour call (all its chunks) */
+int lio_knn_index_last_times(lio_knn_index*, double* build_us, double* query_us);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

@@ -20,6 +20,7 @@
 // transform: per point in f64, terms left to right, no contraction (-ffp-contract=off), cast to f32; non-finite points are transformed too.
 #include <algorithm>
 
+#include "cloud_sort.h"
 #include "lio_common.h"
 
 namespace lio {
@@ -463,6 +464,29 @@ __global__ __launch_bounds__(kThreads) void cl_scatter(const uint32_t* __restric
         __builtin_amdgcn_wave_barrier();
         if (ok[r]) { kout[pos] = k[r]; vout[pos] = v[r]; }
     }
+}
+
+// words of scratch one radix_pass over n keys takes: the [digit][tile] table (+1) and its scan's tile sums
+uint64_t radix_scratch_words(uint64_t n) {
+    const uint64_t tab = 256ull * tiles_of(n) + 1;
+    return round_words(tab) + round_words(scan_aux_words(tab) + 64);
+}
+
+// one stable 8-bit pass of the key sort above for callers outside this file (knn_index.hip): tile histogram, device-wide scan of the
+// [digit][tile] table, stable scatter -- the launches of lio_cloud_voxel_downsample's passes, with cl_hist for every digit
+int radix_pass(hipStream_t st, const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout, uint32_t n, int shift, uint32_t* scratch) {
+    if (n == 0) return LIO_OK;
+    const uint32_t ntiles = (uint32_t)tiles_of(n);
+    const uint64_t tab = 256ull * ntiles;
+    uint32_t* table = scratch;
+    uint32_t* aux = scratch + round_words(tab + 1);
+    cl_hist<<<dim3(ntiles), dim3(kThreads), 0, st>>>(kin, n, shift, table, ntiles);
+    LIO_HIP_TRY(hipGetLastError());
+    const int rc = exclusive_scan(st, table, tab, aux);
+    if (rc != LIO_OK) return rc;
+    cl_scatter<<<dim3(ntiles), dim3(kThreads), 0, st>>>(kin, vin, kout, vout, n, shift, table, ntiles);
+    LIO_HIP_TRY(hipGetLastError());
+    return LIO_OK;
 }
 
 // run heads (first sorted position of every occupied voxel) per tile

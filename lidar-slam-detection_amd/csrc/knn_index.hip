@@ -1,0 +1,685 @@
+// knn_index.hip -- exact k nearest neighbours over a static cloud on gfx950 (wave64): the pcl::KdTreeFLANN<PointXYZRGB> of texture_mesh
+// (slam/src/graph_utils.cpp:449-501), as an implicit bounding-volume tree over Morton-ordered leaves.
+//
+//   expand    xyz (n x 3) -> float4 {x, y, z, input index bits} + the finite points per tile
+//   compact   device-wide exclusive scan of the tile counts -> stable write of the finite points (PCL's isFinite filter; input order kept)
+//   bbox      per-workgroup records (grid-stride) -> one workgroup folds them
+//   morton    63-bit key per point, 21 bits per axis over the finite box, as a low and a high word
+//   sort      four 8-bit passes by the low word, a gather of the high word, four passes by the high word (cloud.hip's stable radix pass)
+//   leaves    kLeaf consecutive sorted points per leaf, gathered as float4 {x, y, z, index bits}, and one AABB per leaf
+//   levels    a complete binary tree in heap order over the leaves (padded to a power of two with empty boxes), eight levels per launch
+//             folded in LDS
+//   query     the queries Morton-sorted the same way; one lane per query walks the tree nearer child first without a stack (the path is the
+//             node index, one bit per level says whether the lane is in the far child), the top k in registers ordered by (d2, index)
+//
+// Exactness: a point's distance is ((dx*dx) + dy*dy) + dz*dz in f32 (d = p - q, no contraction: -ffp-contract=off); a box's bound is the same
+// expression over the clamped per-axis gaps max(lo - q, q - hi, 0).  Rounding is monotone, so the bound never exceeds the distance of a point
+// inside the box; a box is skipped only when its bound is STRICTLY greater than the current k-th distance (at equality a smaller index can still
+// win).  Ties at equal f32 distance go to the smaller input index -- the project's rule (FLANN's order depends on its tree).
+// Workgroups hand results to each other only at kernel boundaries.  Point indices are 32-bit (PCL's int: 2^31 - 1 points), byte offsets 64-bit.
+#include <algorithm>
+#include <vector>
+
+#include "cloud_sort.h"
+#include "lio_common.h"
+
+namespace lio {
+namespace knn_index {
+
+constexpr int kThreads = 256;
+constexpr int kItems = 8;
+constexpr uint32_t kTile = kThreads * kItems;  // points per workgroup of the expand / compact
+constexpr int kWaves = kThreads / 64;
+constexpr uint32_t kLeaf = 32;                 // points per leaf
+constexpr uint32_t kBoxBlocks = 1024;          // workgroups of the bbox's first level
+constexpr int kFold = 8;                       // tree levels per fold launch (256 nodes -> 1)
+constexpr uint32_t kNone = 0xFFFFFFFFu;        // an empty result slot
+constexpr uint64_t kQueryChunk = 1ull << 22;   // queries per device pass (bounds the query scratch)
+
+inline uint64_t tiles_of(uint64_t m) { return (m + kTile - 1) / kTile; }
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// every input point as {x, y, z, index bits}, and the finite ones per tile
+__global__ __launch_bounds__(kThreads) void kx_expand(const float* __restrict__ xyz, uint32_t n, float4* __restrict__ pts, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t wc[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t base = blockIdx.x * kTile;
+    uint32_t c = 0;
+#pragma unroll
+    for (int r = 0; r < kItems; r++) {
+        const uint32_t i = base + r * kThreads + threadIdx.x;
+        if (i < n) {
+            const float x = xyz[3ull * i], y = xyz[3ull * i + 1], z = xyz[3ull * i + 2];
+            pts[i] = make_float4(x, y, z, __uint_as_float(i));
+            c += finite3(x, y, z) ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off);
+    if (lane == 0) wc[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+}
+
+// stable compaction of the finite points: item r of lane l of wave w goes to tile prefix + (finite items of rounds < r) + (of waves < w in
+// round r) + (of lanes < l)
+__global__ __launch_bounds__(kThreads) void kx_compact(const float4* __restrict__ pts, uint32_t n, const uint32_t* __restrict__ offs, float4* __restrict__ out) {
+    __shared__ uint32_t wcnt[kItems][kWaves];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint32_t base = blockIdx.x * kTile;
+    float4 p[kItems];
+    unsigned long long km[kItems];
+#pragma unroll
+    for (int r = 0; r < kItems; r++) {
+        const uint32_t i = base + r * kThreads + tid;
+        p[r] = pts[i < n ? i : n - 1u];
+        km[r] = __ballot(i < n && finite3(p[r].x, p[r].y, p[r].z));
+        if (lane == 0) wcnt[r][wave] = (uint32_t)__popcll(km[r]);
+    }
+    __syncthreads();
+    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint32_t run = offs[blockIdx.x];
+#pragma unroll
+    for (int r = 0; r < kItems; r++) {
+        uint32_t woff = 0, rtot = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) {
+            const uint32_t t = wcnt[r][w];
+            woff += (w < wave) ? t : 0u;
+            rtot += t;
+        }
+        if ((km[r] >> lane) & 1ull) out[run + woff + (uint32_t)__popcll(km[r] & lt)] = p[r];
+        run += rtot;
+    }
+}
+
+// bbox of n finite points, level 1: one record {min x y z, max x y z} per workgroup (grid-stride)
+__global__ __launch_bounds__(kThreads) void kx_box_part(const float4* __restrict__ p, uint32_t n, float* __restrict__ parts) {
+    float mn0 = INFINITY, mn1 = INFINITY, mn2 = INFINITY, mx0 = -INFINITY, mx1 = -INFINITY, mx2 = -INFINITY;
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+        const float4 q = p[i];
+        mn0 = fminf(mn0, q.x); mn1 = fminf(mn1, q.y); mn2 = fminf(mn2, q.z);
+        mx0 = fmaxf(mx0, q.x); mx1 = fmaxf(mx1, q.y); mx2 = fmaxf(mx2, q.z);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mn0 = fminf(mn0, __shfl_xor(mn0, off)); mn1 = fminf(mn1, __shfl_xor(mn1, off)); mn2 = fminf(mn2, __shfl_xor(mn2, off));
+        mx0 = fmaxf(mx0, __shfl_xor(mx0, off)); mx1 = fmaxf(mx1, __shfl_xor(mx1, off)); mx2 = fmaxf(mx2, __shfl_xor(mx2, off));
+    }
+    __shared__ float red[kWaves][6];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[wave][0] = mn0; red[wave][1] = mn1; red[wave][2] = mn2;
+        red[wave][3] = mx0; red[wave][4] = mx1; red[wave][5] = mx2;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        float v = red[0][threadIdx.x];
+        for (int w = 1; w < kWaves; w++) v = threadIdx.x < 3 ? fminf(v, red[w][threadIdx.x]) : fmaxf(v, red[w][threadIdx.x]);
+        parts[6u * blockIdx.x + threadIdx.x] = v;
+    }
+}
+
+// level 2: one workgroup folds the records into box[6]
+__global__ __launch_bounds__(kThreads) void kx_box_fold(const float* __restrict__ parts, uint32_t nparts, float* __restrict__ box) {
+    __shared__ float red[kWaves][6];
+    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t b = threadIdx.x; b < nparts; b += kThreads)
+        for (int a = 0; a < 6; a++) v[a] = a < 3 ? fminf(v[a], parts[6u * b + a]) : fmaxf(v[a], parts[6u * b + a]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int a = 0; a < 6; a++) v[a] = a < 3 ? fminf(v[a], __shfl_xor(v[a], off)) : fmaxf(v[a], __shfl_xor(v[a], off));
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 6; a++) red[threadIdx.x >> 6][a] = v[a];
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int a = threadIdx.x;
+        float r = red[0][a];
+        for (int w = 1; w < kWaves; w++) r = a < 3 ? fminf(r, red[w][a]) : fmaxf(r, red[w][a]);
+        box[a] = r;
+    }
+}
+
+__device__ __forceinline__ uint64_t spread3(uint32_t a) {  // the 21 low bits of a to every third bit
+    uint64_t x = a & 0x1FFFFFu;
+    x = (x | x << 32) & 0x1F00000000FFFFull;
+    x = (x | x << 16) & 0x1F0000FF0000FFull;
+    x = (x | x << 8) & 0x100F00F00F00F00Full;
+    x = (x | x << 4) & 0x10C30C30C30C30C3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+__device__ __forceinline__ uint32_t quant21(float v, float lo, float hi) {
+    const float ext = hi - lo;
+    float t = ext > 0.f ? (v - lo) * (2097151.0f / ext) : 0.f;
+    t = fminf(fmaxf(t, 0.f), 2097151.0f);
+    return (uint32_t)t;
+}
+__device__ __forceinline__ uint64_t morton(float x, float y, float z, const float* b) {
+    return spread3(quant21(x, b[0], b[3])) | (spread3(quant21(y, b[1], b[4])) << 1) | (spread3(quant21(z, b[2], b[5])) << 2);
+}
+
+// keys of the (finite) points of the index; vals = their positions
+__global__ __launch_bounds__(kThreads) void kx_keys_points(const float4* __restrict__ p, uint32_t n, const float* __restrict__ box, uint32_t* __restrict__ klo,
+                                                           uint32_t* __restrict__ khi, uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = p[i];
+    const uint64_t k = morton(q.x, q.y, q.z, box);
+    klo[i] = (uint32_t)k;
+    khi[i] = (uint32_t)(k >> 32);
+    vals[i] = i;
+}
+
+// keys of the queries over the index's box (clamped to it); non-finite queries sort last
+__global__ __launch_bounds__(kThreads) void kx_keys_queries(const float* __restrict__ q, uint32_t m, const float* __restrict__ box, uint32_t* __restrict__ klo,
+                                                            uint32_t* __restrict__ khi, uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= m) return;
+    const float x = q[3ull * i], y = q[3ull * i + 1], z = q[3ull * i + 2];
+    const uint64_t k = finite3(x, y, z) ? morton(x, y, z, box) : ~0ull;
+    klo[i] = (uint32_t)k;
+    khi[i] = (uint32_t)(k >> 32);
+    vals[i] = i;
+}
+
+__global__ __launch_bounds__(kThreads) void kx_gather_u32(const uint32_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint32_t* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) dst[i] = src[idx[i]];
+}
+
+__global__ __launch_bounds__(kThreads) void kx_gather_points(const float4* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, float4* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) dst[i] = src[idx[i]];
+}
+
+// one AABB per leaf slot l < P at heap node P + l (nodes[2 i] = lo, nodes[2 i + 1] = hi); slots past the last leaf get the empty box
+// (lo = +inf > hi = -inf)
+__global__ __launch_bounds__(kThreads) void kx_leaf_boxes(const float4* __restrict__ leaves, uint32_t nf, uint32_t nl, uint32_t P, float4* __restrict__ nodes) {
+    const uint32_t l = blockIdx.x * kThreads + threadIdx.x;
+    if (l >= P) return;
+    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
+    if (l < nl) {
+        const uint32_t a = l * kLeaf, b = min(a + kLeaf, nf);
+        for (uint32_t j = a; j < b; j++) {
+            const float4 p = leaves[j];
+            lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
+            hi.x = fmaxf(hi.x, p.x); hi.y = fmaxf(hi.y, p.y); hi.z = fmaxf(hi.z, p.z);
+        }
+    }
+    nodes[2ull * (P + l)] = lo;
+    nodes[2ull * (P + l) + 1] = hi;
+}
+
+// `levels` levels of the tree above the level whose first node is `first` (= 2^L, 2^L nodes): every workgroup folds 256 of its nodes (fewer
+// near the root) in LDS and writes each level it makes
+__global__ __launch_bounds__(kThreads) void kx_fold(float4* __restrict__ nodes, uint32_t first, int levels) {
+    __shared__ float4 slo[kThreads], shi[kThreads];
+    const uint32_t cnt = min(first, (uint32_t)kThreads);
+    const uint32_t b0 = first + blockIdx.x * cnt;  // first child node of this workgroup
+    const uint32_t t = threadIdx.x;
+    if (t < cnt) {
+        slo[t] = nodes[2ull * (b0 + t)];
+        shi[t] = nodes[2ull * (b0 + t) + 1];
+    }
+    __syncthreads();
+    uint32_t w = cnt, base = b0;
+    for (int s = 0; s < levels; s++) {
+        w >>= 1;
+        base >>= 1;
+        float4 lo, hi;
+        if (t < w) {
+            const float4 l0 = slo[2 * t], l1 = slo[2 * t + 1], h0 = shi[2 * t], h1 = shi[2 * t + 1];
+            lo = make_float4(fminf(l0.x, l1.x), fminf(l0.y, l1.y), fminf(l0.z, l1.z), 0.f);
+            hi = make_float4(fmaxf(h0.x, h1.x), fmaxf(h0.y, h1.y), fmaxf(h0.z, h1.z), 0.f);
+        }
+        __syncthreads();
+        if (t < w) {
+            slo[t] = lo;
+            shi[t] = hi;
+            nodes[2ull * (base + t)] = lo;
+            nodes[2ull * (base + t) + 1] = hi;
+        }
+        __syncthreads();
+    }
+}
+
+// lower bound of the f32 distance from q to any point of the box; `empty` for the padding boxes; *mid = squared distance to the box's centre
+// (visiting order only)
+__device__ __forceinline__ float box_bound(const float4* __restrict__ nodes, uint32_t node, float qx, float qy, float qz, bool* empty, float* mid) {
+    const float4 lo = nodes[2ull * node], hi = nodes[2ull * node + 1];
+    *empty = lo.x > hi.x;
+    const float cx = (lo.x + hi.x) * 0.5f - qx, cy = (lo.y + hi.y) * 0.5f - qy, cz = (lo.z + hi.z) * 0.5f - qz;
+    *mid = cx * cx + cy * cy + cz * cz;
+    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.f);
+    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.f);
+    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.f);
+    return gx * gx + gy * gy + gz * gz;
+}
+
+template <int K>
+__device__ __forceinline__ void consider(float d, uint32_t id, float (&kd)[K], uint32_t (&ki)[K]) {
+    if (!(d < kd[K - 1] || (d == kd[K - 1] && id < ki[K - 1]))) return;
+#pragma unroll
+    for (int s = 0; s < K; s++) {  // insertion: the candidate sinks to its place, the slots behind it move one down, the last drops out
+        const bool lt = d < kd[s] || (d == kd[s] && id < ki[s]);
+        const float td = kd[s];
+        const uint32_t ti = ki[s];
+        kd[s] = lt ? d : td;
+        ki[s] = lt ? id : ti;
+        d = lt ? td : d;
+        id = lt ? ti : id;
+    }
+}
+
+// one lane per query, in Morton order (perm); results go to the query's own position.  COLOUR: the floor-mean of the r, g, b bytes of the
+// (up to) K neighbours packed as 0x00RRGGBB; otherwise the K (index, d2) pairs, ascending (d2, index), empty slots (-1, +inf).
+template <int K, bool COLOUR>
+__global__ __launch_bounds__(kThreads) void kx_query(const float* __restrict__ q, uint32_t m, const uint32_t* __restrict__ perm, const float4* __restrict__ nodes,
+                                                     const float4* __restrict__ leaves, uint32_t nf, uint32_t P, int L, const uint32_t* __restrict__ rgb,
+                                                     int32_t* __restrict__ oidx, float* __restrict__ od2, uint32_t* __restrict__ ocol) {
+    const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t qi = perm[j];
+    const float qx = q[3ull * qi], qy = q[3ull * qi + 1], qz = q[3ull * qi + 2];
+    float kd[K];
+    uint32_t ki[K];
+#pragma unroll
+    for (int s = 0; s < K; s++) { kd[s] = INFINITY; ki[s] = kNone; }
+    if (nf > 0 && finite3(qx, qy, qz)) {
+        uint32_t node = 1, far = 0;  // far: bit l set = the path's node at level l is the far child of its parent
+        int lvl = 0;
+        bool down = true;
+        while (true) {
+            if (down) {
+                if (lvl == L) {
+                    const uint32_t a = (node - P) * kLeaf, cnt = min(kLeaf, nf - a);
+                    for (uint32_t t0 = 0; t0 < cnt; t0 += 8) {
+                        float4 p[8];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) p[u] = leaves[a + min(t0 + u, cnt - 1u)];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) {
+                            if (t0 + u >= cnt) break;
+                            const float dx = p[u].x - qx, dy = p[u].y - qy, dz = p[u].z - qz;
+                            consider<K>(dx * dx + dy * dy + dz * dz, __float_as_uint(p[u].w), kd, ki);
+                        }
+                    }
+                    down = false;
+                } else {
+                    bool e0, e1;
+                    float m0, m1;
+                    const uint32_t c0 = 2 * node;
+                    const float b0 = box_bound(nodes, c0, qx, qy, qz, &e0, &m0), b1 = box_bound(nodes, c0 + 1, qx, qy, qz, &e1, &m1);
+                    // nearer bound first; equal bounds (typically 0: q inside both boxes) by the distance to the box centres -- the order only
+                    // decides how soon the k-th distance shrinks, never what is found
+                    const bool right = e0 || (!e1 && (b1 < b0 || (b1 == b0 && m1 < m0)));
+                    const bool ne = right ? e1 : e0;
+                    const float nb = right ? b1 : b0;
+                    if (ne || nb > kd[K - 1]) {
+                        down = false;  // the far child is empty or no nearer
+                    } else {
+                        node = c0 + (right ? 1u : 0u);
+                        lvl++;
+                        far &= ~(1u << lvl);
+                    }
+                }
+            } else {
+                if (lvl == 0) break;
+                if (!((far >> lvl) & 1u)) {
+                    bool es;
+                    float ms;
+                    const uint32_t sib = node ^ 1u;
+                    const float bs = box_bound(nodes, sib, qx, qy, qz, &es, &ms);
+                    if (!es && !(bs > kd[K - 1])) {
+                        node = sib;
+                        far |= 1u << lvl;
+                        down = true;
+                        continue;
+                    }
+                }
+                node >>= 1;
+                lvl--;
+            }
+        }
+    }
+    if (COLOUR) {
+        uint32_t r = 0, g = 0, b = 0, c = 0;
+#pragma unroll
+        for (int s = 0; s < K; s++)
+            if (ki[s] != kNone) {
+                const uint32_t w = rgb[ki[s]];
+                r += (w >> 16) & 255u;
+                g += (w >> 8) & 255u;
+                b += w & 255u;
+                c++;
+            }
+        ocol[qi] = c ? ((r / c) << 16) | ((g / c) << 8) | (b / c) : 0u;
+    } else {
+#pragma unroll
+        for (int s = 0; s < K; s++) {
+            oidx[(uint64_t)qi * K + s] = ki[s] == kNone ? -1 : (int32_t)ki[s];
+            od2[(uint64_t)qi * K + s] = kd[s];
+        }
+    }
+}
+
+template <bool COLOUR>
+void launch_query(int k, hipStream_t st, const float* q, uint32_t m, const uint32_t* perm, const float4* nodes, const float4* leaves, uint32_t nf, uint32_t P,
+                  int L, const uint32_t* rgb, int32_t* oidx, float* od2, uint32_t* ocol) {
+    const dim3 g((m + kThreads - 1) / kThreads), b(kThreads);
+    switch (k) {
+#define KX_CASE(KK) \
+    case KK: kx_query<KK, COLOUR><<<g, b, 0, st>>>(q, m, perm, nodes, leaves, nf, P, L, rgb, oidx, od2, ocol); break;
+        KX_CASE(1) KX_CASE(2) KX_CASE(3) KX_CASE(4) KX_CASE(5) KX_CASE(6) KX_CASE(7) KX_CASE(8)
+#undef KX_CASE
+        default: break;
+    }
+}
+
+inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kThreads - 1) / kThreads); }
+
+// device allocations of one call, freed when it returns
+struct Temps {
+    std::vector<void*> p;
+    ~Temps() {
+        for (void* x : p) (void)hipFree(x);
+    }
+    template <typename T>
+    T* get(uint64_t count) {
+        void* x = nullptr;
+        if (hipMalloc(&x, std::max<uint64_t>(count, 1) * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("lio_knn_index: %llu bytes of device memory not available", (unsigned long long)(count * sizeof(T)));
+            return nullptr;
+        }
+        p.push_back(x);
+        return static_cast<T*>(x);
+    }
+};
+
+// the Morton order of n keys (63 bits as low / high words): four passes by the low word, the high word gathered into that order, four
+// passes by it.  klo / vals hold the input and are overwritten; returns the permutation (a pointer to vals or vb).
+int morton_sort(hipStream_t st, uint32_t* klo, const uint32_t* khi, uint32_t* vals, uint32_t* kb, uint32_t* vb, uint32_t n, uint32_t* scratch, uint32_t** perm) {
+    uint32_t *ka = klo, *va = vals;
+    for (int p = 0; p < 4; p++) {
+        const int rc = cloud::radix_pass(st, ka, va, kb, vb, n, 8 * p, scratch);
+        if (rc != LIO_OK) return rc;
+        std::swap(ka, kb);
+        std::swap(va, vb);
+    }
+    kx_gather_u32<<<dim3(blocks_of(n)), dim3(kThreads), 0, st>>>(khi, va, n, ka);  // (four passes: the order is back in klo / vals)
+    LIO_HIP_TRY(hipGetLastError());
+    for (int p = 0; p < 4; p++) {
+        const int rc = cloud::radix_pass(st, ka, va, kb, vb, n, 8 * p, scratch);
+        if (rc != LIO_OK) return rc;
+        std::swap(ka, kb);
+        std::swap(va, vb);
+    }
+    *perm = va;
+    return LIO_OK;
+}
+
+}  // namespace knn_index
+}  // namespace lio
+
+using namespace lio;
+using namespace lio::knn_index;
+
+struct lio_knn_index {
+    int device;
+    hipStream_t stream;
+    hipEvent_t ev[2];
+    float4* leaves;  // nf points in Morton order, {x, y, z, input index bits}
+    float4* nodes;   // 2 x 2P float4: the heap-ordered AABBs (node 0 unused)
+    uint32_t* rgb;   // n packed colours in input order (NULL: built without)
+    float* box;      // the finite box, 6 floats
+    uint64_t n;
+    uint32_t nf, nl, P;
+    int L;
+    double build_us, query_us;
+};
+
+namespace {
+
+void release(lio_knn_index* x) {
+    if (x->leaves) (void)hipFree(x->leaves);
+    if (x->nodes) (void)hipFree(x->nodes);
+    if (x->rgb) (void)hipFree(x->rgb);
+    x->leaves = x->nodes = nullptr;
+    x->rgb = nullptr;
+    x->n = x->nf = x->nl = x->P = 0;
+    x->L = 0;
+}
+
+float elapsed_us(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f;
+}
+
+// the k nearest of m host queries: (idx, d2) when rgb_out is NULL, else the colours
+int run_query(lio_knn_index* x, const float* q, uint64_t m, int k, int32_t* idx, float* d2, uint8_t* rgb_out) {
+    x->query_us = 0;
+    if (m == 0) return LIO_OK;
+    hipSetDevice(x->device);
+    const bool colour = rgb_out != nullptr;
+    if (x->nf == 0) {  // nothing indexed: every slot empty
+        for (uint64_t i = 0; i < m; i++) {
+            if (colour) {
+                rgb_out[3 * i] = rgb_out[3 * i + 1] = rgb_out[3 * i + 2] = 0;
+            } else {
+                for (int s = 0; s < k; s++) { idx[i * k + s] = -1; d2[i * k + s] = INFINITY; }
+            }
+        }
+        return LIO_OK;
+    }
+    const uint64_t chunk = std::min<uint64_t>(m, kQueryChunk);
+    Temps T;
+    float* dq = T.get<float>(3 * chunk);
+    uint32_t *klo = T.get<uint32_t>(chunk), *khi = T.get<uint32_t>(chunk), *vals = T.get<uint32_t>(chunk), *kb = T.get<uint32_t>(chunk), *vb = T.get<uint32_t>(chunk);
+    uint32_t* scratch = T.get<uint32_t>(cloud::radix_scratch_words(chunk));
+    int32_t* oidx = colour ? nullptr : T.get<int32_t>(chunk * k);
+    float* od2 = colour ? nullptr : T.get<float>(chunk * k);
+    uint32_t* ocol = colour ? T.get<uint32_t>(chunk) : nullptr;
+    if (!dq || !klo || !khi || !vals || !kb || !vb || !scratch || (colour ? !ocol : (!oidx || !od2))) return LIO_E_DEVICE;
+    std::vector<uint32_t> hcol(colour ? chunk : 0);
+    double total = 0;
+    for (uint64_t q0 = 0; q0 < m; q0 += chunk) {
+        const uint32_t mc = (uint32_t)std::min<uint64_t>(chunk, m - q0);
+        LIO_HIP_TRY(hipMemcpyAsync(dq, q + 3 * q0, 3ull * mc * sizeof(float), hipMemcpyHostToDevice, x->stream));
+        LIO_HIP_TRY(hipEventRecord(x->ev[0], x->stream));
+        kx_keys_queries<<<dim3(blocks_of(mc)), dim3(kThreads), 0, x->stream>>>(dq, mc, x->box, klo, khi, vals);
+        LIO_HIP_TRY(hipGetLastError());
+        uint32_t* perm = nullptr;
+        const int rc = morton_sort(x->stream, klo, khi, vals, kb, vb, mc, scratch, &perm);
+        if (rc != LIO_OK) return rc;
+        if (colour)
+            launch_query<true>(k, x->stream, dq, mc, perm, x->nodes, x->leaves, x->nf, x->P, x->L, x->rgb, nullptr, nullptr, ocol);
+        else
+            launch_query<false>(k, x->stream, dq, mc, perm, x->nodes, x->leaves, x->nf, x->P, x->L, nullptr, oidx, od2, nullptr);
+        LIO_HIP_TRY(hipGetLastError());
+        LIO_HIP_TRY(hipEventRecord(x->ev[1], x->stream));
+        if (colour) {
+            LIO_HIP_TRY(hipMemcpyAsync(hcol.data(), ocol, (uint64_t)mc * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+        } else {
+            LIO_HIP_TRY(hipMemcpyAsync(idx + q0 * k, oidx, (uint64_t)mc * k * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+            LIO_HIP_TRY(hipMemcpyAsync(d2 + q0 * k, od2, (uint64_t)mc * k * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+        }
+        LIO_HIP_TRY(hipStreamSynchronize(x->stream));
+        total += elapsed_us(x->ev[0], x->ev[1]);
+        if (colour)
+            for (uint32_t i = 0; i < mc; i++) {
+                const uint32_t w = hcol[i];
+                uint8_t* o = rgb_out + 3 * (q0 + i);
+                o[0] = (uint8_t)(w >> 16);
+                o[1] = (uint8_t)(w >> 8);
+                o[2] = (uint8_t)w;
+            }
+    }
+    x->query_us = total;
+    return LIO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lio_knn_index* lio_knn_index_create(int device) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) {
+        (void)hipGetLastError();
+        set_error("lio_knn_index_create: no HIP device %d (there is no CPU fallback)", device);
+        return nullptr;
+    }
+    if (hipSetDevice(device) != hipSuccess) { set_error("lio_knn_index_create: hipSetDevice(%d) failed", device); return nullptr; }
+    lio_knn_index* x = new lio_knn_index();
+    memset(x, 0, sizeof(*x));
+    x->device = device;
+    bool ok = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++) ok = hipEventCreate(&x->ev[i]) == hipSuccess;
+    ok = ok && hipMalloc(&x->box, 8 * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        set_error("lio_knn_index_create: stream / event / box allocation failed");
+        lio_knn_index_destroy(x);
+        return nullptr;
+    }
+    return x;
+}
+
+void lio_knn_index_destroy(lio_knn_index* x) {
+    if (!x) return;
+    hipSetDevice(x->device);
+    if (x->stream) hipStreamSynchronize(x->stream);
+    release(x);
+    if (x->box) hipFree(x->box);
+    for (int i = 0; i < 2; i++)
+        if (x->ev[i]) hipEventDestroy(x->ev[i]);
+    if (x->stream) hipStreamDestroy(x->stream);
+    delete x;
+}
+
+int lio_knn_index_build(lio_knn_index* x, const float* xyz, const uint32_t* rgb, uint64_t n, uint64_t* n_finite) {
+    if (!x || (!xyz && n)) return LIO_E_INVALID;
+    if (n > 0x7FFFFFFFull) {
+        set_error("lio_knn_index_build: %llu points exceed the int index range (2^31 - 1)", (unsigned long long)n);
+        return LIO_E_CAPACITY;
+    }
+    hipSetDevice(x->device);
+    release(x);
+    x->build_us = 0;
+    if (n_finite) *n_finite = 0;
+    if (n == 0) return LIO_OK;
+    const uint32_t nn = (uint32_t)n, ntiles = (uint32_t)tiles_of(n);
+    Temps T;
+    float* dxyz = T.get<float>(3 * n);
+    float4* pts = T.get<float4>(n);
+    float4* cpt = T.get<float4>(n);
+    const uint64_t cwords = (ntiles + 1ull + 63) & ~63ull;  // the scan's tile sums start 256-byte aligned (it reads them as uint4)
+    uint32_t* counts = T.get<uint32_t>(cwords + cloud::scan_aux_words(ntiles + 1) + 64);
+    float* parts = T.get<float>(6ull * kBoxBlocks);
+    if (!dxyz || !pts || !cpt || !counts || !parts) return LIO_E_DEVICE;
+    if (rgb && hipMalloc(&x->rgb, n * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        x->rgb = nullptr;
+        set_error("lio_knn_index_build: %llu bytes of device memory not available for the colours", (unsigned long long)(n * 4));
+        return LIO_E_DEVICE;
+    }
+    LIO_HIP_TRY(hipMemcpyAsync(dxyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, x->stream));
+    if (rgb) LIO_HIP_TRY(hipMemcpyAsync(x->rgb, rgb, n * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
+    LIO_HIP_TRY(hipEventRecord(x->ev[0], x->stream));
+    // finite points, compacted in input order
+    LIO_HIP_TRY(hipMemsetAsync(counts + ntiles, 0, sizeof(uint32_t), x->stream));
+    kx_expand<<<dim3(ntiles), dim3(kThreads), 0, x->stream>>>(dxyz, nn, pts, counts);
+    LIO_HIP_TRY(hipGetLastError());
+    int rc = cloud::exclusive_scan(x->stream, counts, ntiles + 1ull, counts + cwords);
+    if (rc != LIO_OK) return rc;
+    kx_compact<<<dim3(ntiles), dim3(kThreads), 0, x->stream>>>(pts, nn, counts, cpt);
+    LIO_HIP_TRY(hipGetLastError());
+    uint32_t nf = 0;
+    LIO_HIP_TRY(hipMemcpyAsync(&nf, counts + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    LIO_HIP_TRY(hipStreamSynchronize(x->stream));
+    if (n_finite) *n_finite = nf;
+    x->n = n;
+    if (nf == 0) {
+        LIO_HIP_TRY(hipEventRecord(x->ev[1], x->stream));
+        LIO_HIP_TRY(hipStreamSynchronize(x->stream));
+        x->build_us = elapsed_us(x->ev[0], x->ev[1]);
+        return LIO_OK;
+    }
+    // the box, the Morton order, the leaves
+    const uint32_t nb = std::min<uint32_t>(ntiles, kBoxBlocks);
+    kx_box_part<<<dim3(nb), dim3(kThreads), 0, x->stream>>>(cpt, nf, parts);
+    kx_box_fold<<<dim3(1), dim3(kThreads), 0, x->stream>>>(parts, nb, x->box);
+    LIO_HIP_TRY(hipGetLastError());
+    {
+        Temps S;
+        uint32_t *klo = S.get<uint32_t>(nf), *khi = S.get<uint32_t>(nf), *vals = S.get<uint32_t>(nf), *kb = S.get<uint32_t>(nf), *vb = S.get<uint32_t>(nf);
+        uint32_t* scratch = S.get<uint32_t>(cloud::radix_scratch_words(nf));
+        if (!klo || !khi || !vals || !kb || !vb || !scratch) return LIO_E_DEVICE;
+        kx_keys_points<<<dim3(blocks_of(nf)), dim3(kThreads), 0, x->stream>>>(cpt, nf, x->box, klo, khi, vals);
+        LIO_HIP_TRY(hipGetLastError());
+        uint32_t* perm = nullptr;
+        rc = morton_sort(x->stream, klo, khi, vals, kb, vb, nf, scratch, &perm);
+        if (rc != LIO_OK) return rc;
+        kx_gather_points<<<dim3(blocks_of(nf)), dim3(kThreads), 0, x->stream>>>(cpt, perm, nf, pts);  // pts (n >= nf slots) becomes the leaves
+        LIO_HIP_TRY(hipGetLastError());
+        LIO_HIP_TRY(hipStreamSynchronize(x->stream));
+    }
+    const uint32_t nl = (nf + kLeaf - 1) / kLeaf;
+    int L = 0;
+    while ((1u << L) < nl) L++;
+    const uint32_t P = 1u << L;
+    if (hipMalloc(&x->nodes, 4ull * P * sizeof(float4)) != hipSuccess) {
+        (void)hipGetLastError();
+        x->nodes = nullptr;
+        set_error("lio_knn_index_build: %llu bytes of device memory not available for the tree", (unsigned long long)(4ull * P * sizeof(float4)));
+        return LIO_E_DEVICE;
+    }
+    kx_leaf_boxes<<<dim3(blocks_of(P)), dim3(kThreads), 0, x->stream>>>(pts, nf, nl, P, x->nodes);
+    LIO_HIP_TRY(hipGetLastError());
+    for (int lv = L; lv > 0;) {
+        const int f = std::min(lv, kFold);
+        const uint32_t first = 1u << lv;
+        const uint32_t blocks = std::max<uint32_t>(1u, first / kThreads);
+        kx_fold<<<dim3(blocks), dim3(kThreads), 0, x->stream>>>(x->nodes, first, f);
+        LIO_HIP_TRY(hipGetLastError());
+        lv -= f;
+    }
+    LIO_HIP_TRY(hipEventRecord(x->ev[1], x->stream));
+    LIO_HIP_TRY(hipStreamSynchronize(x->stream));
+    x->build_us = elapsed_us(x->ev[0], x->ev[1]);
+    // keep the leaves: take pts out of the temporaries
+    T.p.erase(std::find(T.p.begin(), T.p.end(), (void*)pts));
+    x->leaves = pts;
+    x->nf = nf;
+    x->nl = nl;
+    x->P = P;
+    x->L = L;
+    return LIO_OK;
+}
+
+int lio_knn_index_query(lio_knn_index* x, const float* q, uint64_t m, int k, int32_t* idx, float* d2) {
+    if (!x || k < 1 || k > 8 || (m && (!q || !idx || !d2))) return LIO_E_INVALID;
+    return run_query(x, q, m, k, idx, d2, nullptr);
+}
+
+int lio_knn_index_colour(lio_knn_index* x, const float* q, uint64_t m, int k, uint8_t* rgb_out) {
+    if (!x || k < 1 || k > 8 || (m && (!q || !rgb_out))) return LIO_E_INVALID;
+    if (x->nf && !x->rgb) {
+        set_error("lio_knn_index_colour: the index was built without colours");
+        return LIO_E_STATE;
+    }
+    return run_query(x, q, m, k, nullptr, nullptr, rgb_out);
+}
+
+int lio_knn_index_last_times(lio_knn_index* x, double* build_us, double* query_us) {
+    if (!x) return LIO_E_INVALID;
+    if (build_us) *build_us = x->build_us;
+    if (query_us) *query_us = x->query_us;
+    return LIO_OK;
+}
+
+}  // extern "C"

@@ -13,7 +13,8 @@
 // transform and the stamp conversion are applied while copying, the 48-byte PointXYZINormal inflation and the two intermediate
 // PCL clouds of the reference never exist.
 // The dense-map export (set_export_map_config / export_points / dump_map_points, accumulate_cloud / save_accumulate_cloud,
-// save_undistortion_cloud: graph_utils.cpp:160-200, 384-446) runs on the device over lio_cloud_* (csrc/cloud.hip).
+// save_undistortion_cloud: graph_utils.cpp:160-200, 384-446) runs on the device over lio_cloud_* (csrc/cloud.hip), texture_mesh
+// (graph_utils.cpp:449-501) over lio_knn_index_* (csrc/knn_index.hip).
 // Off the hot path (graph back end, GNSS, colouration: SURVEY.md section 2 OUT-OF-SCOPE, Appendix B): type-correct minimal
 // implementations -- empty dict / list, identity 4 x 4, stored-and-returned settings -- so that slam.py and map_manager.py run
 // unchanged.  They are listed in INTEGRATION.md.
@@ -23,9 +24,11 @@
 
 #include <dirent.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
+#include <charconv>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -1158,7 +1161,252 @@ void save_accumulate_cloud(std::string file, double resolution) {
     lio_cloud_clear(g_acc.cloud);
     if (m > 0) require(write_pcd_binary(file, out.data(), (size_t)m), "save_accumulate_cloud: cannot write the file");
 }
-void texture_mesh(std::string mesh_path, std::string cloud_path, std::string output_path) { (void)mesh_path; (void)cloud_path; (void)output_path; }
+// ---- texture_mesh (graph_utils.cpp:449-501): a coloured PCD, an OBJ mesh, every vertex coloured by its 3 nearest cloud points -----------------
+// The readers and the writer are the module's own (PCL is not linked): every refusal raises ValueError naming the reason.
+[[noreturn]] void refuse(const char* who, const std::string& why) { throw std::invalid_argument(std::string("slam_wrapper: ") + who + ": " + why); }
+
+bool slurp(const std::string& path, std::string& out) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return false;
+    f.seekg(0, std::ios::end);
+    const std::streamoff sz = f.tellg();
+    if (sz < 0) return false;
+    out.resize((size_t)sz);
+    f.seekg(0);
+    return sz == 0 || (bool)f.read(&out[0], sz);
+}
+
+bool is_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; }
+
+// the next whitespace-separated token of [p, end)
+bool next_token(const char*& p, const char* end, const char*& a, const char*& b) {
+    while (p < end && is_space(*p)) p++;
+    if (p >= end) return false;
+    a = p;
+    while (p < end && !is_space(*p)) p++;
+    b = p;
+    return true;
+}
+
+// correctly rounded decimal -> f32 (as lexical_cast<float> / strtof); "nan", "inf" accepted; subnormal results through strtof (from_chars
+// reports them out of range)
+bool parse_f32(const char* a, const char* b, float& v) {
+    if (a < b && *a == '+') a++;
+    const auto r = std::from_chars(a, b, v);
+    if (r.ec == std::errc() && r.ptr == b) return true;
+    if (r.ec != std::errc::result_out_of_range) return false;
+    const std::string t(a, b);
+    char* e = nullptr;
+    v = std::strtof(t.c_str(), &e);
+    return e == t.c_str() + t.size();
+}
+
+template <typename T>
+bool parse_int(const char* a, const char* b, T& v) {
+    if (a < b && *a == '+') a++;
+    const auto r = std::from_chars(a, b, v);
+    return r.ec == std::errc() && r.ptr == b;
+}
+
+// a PointXYZRGB cloud: x y z (4-byte floats) and the 32-bit pattern of `rgb` / `rgba` (r = bits 16-23, g = 8-15, b = 0-7), other fields of any
+// SIZE / COUNT skipped; DATA ascii or binary; WIDTH * HEIGHT points (POINTS when given)
+void read_rgb_pcd(const std::string& path, std::vector<float>& xyz, std::vector<uint32_t>& rgb, const char* who) {
+    std::string buf;
+    if (!slurp(path, buf)) refuse(who, "cannot read the cloud '" + path + "'");
+    std::vector<std::string> fields, types;
+    std::vector<int> sizes, counts;
+    long long width = -1, height = 1, points = -1;
+    std::string data;
+    size_t pos = 0;
+    while (pos < buf.size() && data.empty()) {
+        size_t e = buf.find('\n', pos);
+        if (e == std::string::npos) e = buf.size();
+        std::string line = buf.substr(pos, e - pos);
+        pos = e + 1;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream ls(line);
+        std::string key;
+        ls >> key;
+        bool ok = true;
+        if (key == "FIELDS") { std::string v; while (ls >> v) fields.push_back(v); }
+        else if (key == "SIZE") { int v; while (ls >> v) sizes.push_back(v); ok = ls.eof(); }
+        else if (key == "TYPE") { std::string v; while (ls >> v) types.push_back(v); }
+        else if (key == "COUNT") { int v; while (ls >> v) counts.push_back(v); ok = ls.eof(); }
+        else if (key == "WIDTH") ok = (bool)(ls >> width);
+        else if (key == "HEIGHT") ok = (bool)(ls >> height);
+        else if (key == "POINTS") ok = (bool)(ls >> points);
+        else if (key == "DATA") { ls >> data; if (data.empty()) ok = false; }
+        if (!ok) refuse(who, "malformed PCD header line '" + line + "' in '" + path + "'");
+    }
+    if (data.empty()) refuse(who, "no DATA line in '" + path + "'");
+    if (data == "binary_compressed") refuse(who, "DATA binary_compressed is not supported ('" + path + "')");
+    if (data != "ascii" && data != "binary") refuse(who, "unknown DATA kind '" + data + "' in '" + path + "'");
+    if (counts.empty()) counts.assign(fields.size(), 1);
+    if (fields.empty() || sizes.size() != fields.size() || types.size() != fields.size() || counts.size() != fields.size())
+        refuse(who, "malformed PCD header (FIELDS / SIZE / TYPE / COUNT disagree) in '" + path + "'");
+    if (points < 0) points = width * height;
+    if (width < 0 || height < 0 || points < 0) refuse(who, "malformed PCD header (no WIDTH) in '" + path + "'");
+    int xyz_f[3] = {-1, -1, -1}, col_f = -1;
+    for (size_t i = 0; i < fields.size(); i++) {
+        if (sizes[i] <= 0 || counts[i] <= 0) refuse(who, "malformed PCD header (SIZE / COUNT) in '" + path + "'");
+        const int k = fields[i] == "x" ? 0 : fields[i] == "y" ? 1 : fields[i] == "z" ? 2 : -1;
+        if (k >= 0 && xyz_f[k] < 0) xyz_f[k] = (int)i;
+        if ((fields[i] == "rgb" || fields[i] == "rgba") && col_f < 0) col_f = (int)i;
+    }
+    for (int k = 0; k < 3; k++)
+        if (xyz_f[k] < 0 || sizes[xyz_f[k]] != 4 || types[xyz_f[k]] != "F") refuse(who, "the cloud needs x, y and z as 4-byte floats ('" + path + "')");
+    if (col_f < 0) refuse(who, "the cloud has no rgb / rgba field ('" + path + "'): nothing to colour the mesh with");
+    if (sizes[col_f] != 4 || (types[col_f] != "F" && types[col_f] != "U" && types[col_f] != "I"))
+        refuse(who, "the cloud's " + fields[col_f] + " field is not a 4-byte word ('" + path + "')");
+    const size_t n = (size_t)points;
+    xyz.assign(3 * n, 0.f);
+    rgb.assign(n, 0u);
+    if (data == "binary") {
+        size_t stride = 0;
+        std::vector<size_t> off(fields.size());
+        for (size_t i = 0; i < fields.size(); i++) { off[i] = stride; stride += (size_t)sizes[i] * counts[i]; }
+        if (stride == 0 || (buf.size() - std::min(pos, buf.size())) / stride < n) refuse(who, "the binary data of '" + path + "' is shorter than its header says");
+        const char* d = buf.data() + pos;
+        for (size_t i = 0; i < n; i++, d += stride) {
+            for (int k = 0; k < 3; k++) std::memcpy(&xyz[3 * i + k], d + off[xyz_f[k]], 4);
+            std::memcpy(&rgb[i], d + off[col_f], 4);
+        }
+    } else {
+        const char* p = buf.data() + std::min(pos, buf.size());
+        const char* end = buf.data() + buf.size();
+        const char *a, *b;
+        for (size_t i = 0; i < n; i++)
+            for (size_t f = 0; f < fields.size(); f++)
+                for (int c = 0; c < counts[f]; c++) {
+                    if (!next_token(p, end, a, b)) refuse(who, "the ascii data of '" + path + "' ends before its header's point count");
+                    if (c) continue;
+                    bool ok = true;
+                    if ((int)f == col_f) {
+                        if (types[f] == "F") { float v; ok = parse_f32(a, b, v); std::memcpy(&rgb[i], &v, 4); }
+                        else if (types[f] == "U") { uint32_t v; ok = parse_int(a, b, v); rgb[i] = v; }
+                        else { int32_t v; ok = parse_int(a, b, v); rgb[i] = (uint32_t)v; }
+                    } else {
+                        for (int k = 0; k < 3; k++)
+                            if ((int)f == xyz_f[k]) ok = parse_f32(a, b, xyz[3 * i + k]);
+                    }
+                    if (!ok) refuse(who, "bad value '" + std::string(a, b) + "' in the ascii data of '" + path + "'");
+                }
+    }
+}
+
+// an OBJ mesh: `v x y z [...]` (extra values ignored), `f` with i, i/t, i//n, i/t/n and negative (relative) indices, polygons of any arity;
+// other statements ignored.  faces: the 0-based indices of every face in turn, face_size: their arities.
+void read_obj(const std::string& path, std::vector<float>& v, std::vector<int32_t>& faces, std::vector<uint32_t>& face_size, const char* who) {
+    std::string buf;
+    if (!slurp(path, buf)) refuse(who, "cannot read the mesh '" + path + "'");
+    v.clear();
+    faces.clear();
+    face_size.clear();
+    const char* p = buf.data();
+    const char* end = p + buf.size();
+    size_t line_no = 0;
+    std::vector<int64_t> raw;  // face indices as written (1-based or negative), checked once every vertex is known
+    while (p < end) {
+        const char* e = static_cast<const char*>(std::memchr(p, '\n', (size_t)(end - p)));
+        if (!e) e = end;
+        line_no++;
+        const char* q = p;
+        const char* le = e;
+        p = e + 1;
+        const char *a, *b;
+        if (!next_token(q, le, a, b)) continue;
+        const size_t kw = (size_t)(b - a);
+        auto bad = [&](const char* what) { refuse(who, std::string(what) + " at line " + std::to_string(line_no) + " of '" + path + "'"); };
+        if (kw == 1 && *a == 'v') {
+            float c[3];
+            for (int k = 0; k < 3; k++)
+                if (!next_token(q, le, a, b) || !parse_f32(a, b, c[k])) bad("malformed vertex");
+            v.insert(v.end(), c, c + 3);
+        } else if (kw == 1 && *a == 'f') {
+            uint32_t cnt = 0;
+            const int64_t nv = (int64_t)(v.size() / 3);
+            while (next_token(q, le, a, b)) {
+                const char* s = static_cast<const char*>(std::memchr(a, '/', (size_t)(b - a)));
+                int64_t i = 0;
+                if (!parse_int(a, s ? s : b, i) || i == 0) bad("malformed face index");
+                if (i < 0) {
+                    i = nv + i;  // relative: -1 is the last vertex read so far
+                    if (i < 0) bad("face index out of range");
+                    raw.push_back(i);
+                } else {
+                    raw.push_back(i - 1);
+                }
+                cnt++;
+            }
+            if (cnt == 0) bad("face without vertices");
+            if (cnt > 255) bad("face of more than 255 vertices (the PLY list count is a uchar)");
+            face_size.push_back(cnt);
+        }
+    }
+    const int64_t nv = (int64_t)(v.size() / 3);
+    faces.resize(raw.size());
+    for (size_t i = 0; i < raw.size(); i++) {
+        if (raw[i] >= nv) refuse(who, "face index " + std::to_string(raw[i] + 1) + " out of range (" + std::to_string(nv) + " vertices) in '" + path + "'");
+        faces[i] = (int32_t)raw[i];
+    }
+}
+
+// the mesh as PLY, binary little endian: float x y z + uchar red green blue per vertex, `list uchar int vertex_indices` per face -- the layout
+// PCL 1.9's savePLYFileBinary gives a PointXYZRGB mesh, restated (PCL is not linked)
+bool write_mesh_ply(const std::string& path, const float* v, const uint8_t* rgb, size_t nv, const int32_t* faces, const uint32_t* face_size, size_t nf) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) return false;
+    f << "ply\nformat binary_little_endian 1.0\ncomment PCL generated\nelement vertex " << nv
+      << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nelement face " << nf
+      << "\nproperty list uchar int vertex_indices\nend_header\n";
+    std::vector<char> out(nv * 15);
+    for (size_t i = 0; i < nv; i++) {
+        std::memcpy(&out[15 * i], v + 3 * i, 12);
+        std::memcpy(&out[15 * i + 12], rgb + 3 * i, 3);
+    }
+    f.write(out.data(), (std::streamsize)out.size());
+    out.clear();
+    size_t k = 0;
+    for (size_t i = 0; i < nf; i++) {
+        out.push_back((char)(uint8_t)face_size[i]);
+        const size_t at = out.size();
+        out.resize(at + 4ull * face_size[i]);
+        std::memcpy(&out[at], faces + k, 4ull * face_size[i]);
+        k += face_size[i];
+    }
+    f.write(out.data(), (std::streamsize)out.size());
+    return (bool)f;
+}
+
+void texture_mesh(std::string mesh_path, std::string cloud_path, std::string output_path) {
+    const char* who = "texture_mesh";
+    struct stat st;
+    if (stat(output_path.c_str(), &st) != 0 || !S_ISDIR(st.st_mode) || access(output_path.c_str(), W_OK | X_OK) != 0)
+        refuse(who, "the output directory '" + output_path + "' cannot be written");
+    std::vector<float> xyz, verts;
+    std::vector<uint32_t> rgb, face_size;
+    std::vector<int32_t> faces;
+    read_rgb_pcd(cloud_path, xyz, rgb, who);
+    size_t finite = 0;
+    for (size_t i = 0; i < rgb.size(); i++) finite += std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2]);
+    if (finite == 0) refuse(who, "the cloud '" + cloud_path + "' has no finite point");
+    if (rgb.size() > 0x7FFFFFFFull) refuse(who, "the cloud '" + cloud_path + "' has more than 2^31 - 1 points");
+    read_obj(mesh_path, verts, faces, face_size, who);
+    const size_t nv = verts.size() / 3;
+    std::vector<uint8_t> colour(3 * nv + 3);
+    {
+        py::gil_scoped_release nogil;
+        lio_knn_index* x = lio_knn_index_create(0);
+        require(x != nullptr, "texture_mesh: no HIP device");
+        int rc = lio_knn_index_build(x, xyz.data(), rgb.data(), rgb.size(), nullptr);
+        if (rc == LIO_OK) rc = lio_knn_index_colour(x, verts.data(), nv, 3, colour.data());  // smooth_factor = 3
+        lio_knn_index_destroy(x);
+        require(rc == LIO_OK, "texture_mesh: the device pass failed");
+    }
+    const std::string out = output_path + "/texture_mesh.ply";
+    if (!write_mesh_ply(out, verts.data(), colour.data(), nv, faces.data(), face_size.data(), face_size.size())) refuse(who, "cannot write '" + out + "'");
+}
 void set_colouration_config(py::list& cameras) { (void)cameras; }
 void set_map_odometrys(py::array_t<double>& poses) { (void)poses; }
 void colouration_frame(std::string lidar_name, py::dict& points, py::dict& points_attr, py::dict& image_dict, py::dict& image_stream_dict, py::dict& image_param) {
@@ -1190,6 +1438,53 @@ py::tuple _tum_relative_poses(py::array_t<double>& poses) {
     for (const Mat4& T : relative_poses(tum)) rel.append(to_np(T));
     if (tum.empty()) throw std::invalid_argument("slam_wrapper: _tum_relative_poses: no poses");
     return py::make_tuple(to_np(tum[0].T), rel);
+}
+// texture_mesh's readers and writer without a device: _read_rgb_pcd(path) -> (xyz f32 n x 3, rgb u32 n); _read_obj(path) -> (vertices f32 m x 3,
+// [faces]); _write_mesh_ply(path, vertices, rgb m x 3 uint8, faces)
+py::tuple _read_rgb_pcd(std::string path) {
+    std::vector<float> xyz;
+    std::vector<uint32_t> rgb;
+    read_rgb_pcd(path, xyz, rgb, "_read_rgb_pcd");
+    py::array_t<float> a({(py::ssize_t)rgb.size(), (py::ssize_t)3});
+    py::array_t<uint32_t> c((py::ssize_t)rgb.size());
+    if (!rgb.empty()) {
+        std::memcpy(a.mutable_data(), xyz.data(), xyz.size() * 4);
+        std::memcpy(c.mutable_data(), rgb.data(), rgb.size() * 4);
+    }
+    return py::make_tuple(a, c);
+}
+py::tuple _read_obj(std::string path) {
+    std::vector<float> v;
+    std::vector<int32_t> faces;
+    std::vector<uint32_t> fs;
+    read_obj(path, v, faces, fs, "_read_obj");
+    py::array_t<float> a({(py::ssize_t)(v.size() / 3), (py::ssize_t)3});
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * 4);
+    py::list fl;
+    size_t k = 0;
+    for (uint32_t c : fs) {
+        py::list f;
+        for (uint32_t j = 0; j < c; j++) f.append(faces[k + j]);
+        k += c;
+        fl.append(f);
+    }
+    return py::make_tuple(a, fl);
+}
+void _write_mesh_ply(std::string path, py::array_t<float, py::array::c_style | py::array::forcecast> vertices,
+                     py::array_t<uint8_t, py::array::c_style | py::array::forcecast> rgb, py::list faces) {
+    if (vertices.ndim() != 2 || vertices.shape(1) != 3) throw std::invalid_argument("slam_wrapper: _write_mesh_ply: vertices must be m x 3");
+    const size_t nv = (size_t)vertices.shape(0);
+    if (rgb.ndim() != 2 || rgb.shape(1) != 3 || (size_t)rgb.shape(0) != nv) throw std::invalid_argument("slam_wrapper: _write_mesh_ply: rgb must be m x 3");
+    std::vector<int32_t> flat;
+    std::vector<uint32_t> fs;
+    for (py::handle f : faces) {
+        const std::vector<int32_t> idx = py::cast<std::vector<int32_t>>(f);
+        if (idx.empty() || idx.size() > 255) throw std::invalid_argument("slam_wrapper: _write_mesh_ply: a face has 1 to 255 vertices");
+        flat.insert(flat.end(), idx.begin(), idx.end());
+        fs.push_back((uint32_t)idx.size());
+    }
+    if (!write_mesh_ply(path, vertices.data(), rgb.data(), nv, flat.data(), fs.data(), fs.size()))
+        throw std::invalid_argument("slam_wrapper: _write_mesh_ply: cannot write '" + path + "'");
 }
 void _set_capacity(uint64_t max_points, uint64_t max_voxels) { if (g) { g->max_points = max_points; g->max_voxels = max_voxels; } }
 
@@ -1251,5 +1546,8 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("_engine_handle", &_engine_handle);
     m.def("_transform_from_rpyt", &_transform_from_rpyt);
     m.def("_tum_relative_poses", &_tum_relative_poses, py::arg("poses"));
+    m.def("_read_rgb_pcd", &_read_rgb_pcd, py::arg("path"));
+    m.def("_read_obj", &_read_obj, py::arg("path"));
+    m.def("_write_mesh_ply", &_write_mesh_ply, py::arg("path"), py::arg("vertices"), py::arg("rgb"), py::arg("faces"));
     m.def("_set_capacity", &_set_capacity, py::arg("max_points"), py::arg("max_voxels"));
 }

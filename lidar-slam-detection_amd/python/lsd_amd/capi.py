@@ -36,6 +36,7 @@ SYMBOLS = [
     "lio_localmap_download",
     "lio_cloud_create", "lio_cloud_destroy", "lio_cloud_clear", "lio_cloud_size", "lio_cloud_append_scan", "lio_cloud_append_host",
     "lio_cloud_voxel_downsample", "lio_cloud_download", "lio_cloud_scratch_bytes", "lio_cloud_last_times",
+    "lio_knn_index_create", "lio_knn_index_destroy", "lio_knn_index_build", "lio_knn_index_query", "lio_knn_index_colour", "lio_knn_index_last_times",
     "lio_pose_estimator_create", "lio_pose_estimator_destroy", "lio_pose_estimator_predict", "lio_pose_estimator_match", "lio_pose_estimator_match_gps", "lio_pose_estimator_guess", "lio_pose_estimator_observe",
     "lio_pose_estimator_match_gps_only", "lio_pose_estimator_get_timed_pose", "lio_pose_estimator_predict_nostate",
     "lio_pose_estimator_correct", "lio_pose_estimator_get_dt", "lio_pose_estimator_get", "lio_pose_estimator_set", "lio_pose_estimator_matrix",
@@ -236,6 +237,12 @@ def lib():
     sig("lio_cloud_download", C.c_int64, vp, f32p, u64)
     sig("lio_cloud_scratch_bytes", cint, vp, C.POINTER(u64))
     sig("lio_cloud_last_times", cint, vp, f64p, f64p)
+    sig("lio_knn_index_create", vp, cint)
+    sig("lio_knn_index_destroy", None, vp)
+    sig("lio_knn_index_build", cint, vp, f32p, C.POINTER(C.c_uint32), u64, C.POINTER(u64))
+    sig("lio_knn_index_query", cint, vp, f32p, u64, cint, i32p, f32p)
+    sig("lio_knn_index_colour", cint, vp, f32p, u64, cint, u8p)
+    sig("lio_knn_index_last_times", cint, vp, f64p, f64p)
     sig("lio_pose_estimator_create", vp, f32p, u64, f32p, f32p, dbl)
     sig("lio_pose_estimator_destroy", None, vp)
     sig("lio_pose_estimator_predict", cint, vp, u64, f32p, f32p)

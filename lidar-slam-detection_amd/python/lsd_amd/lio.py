@@ -721,6 +721,55 @@ class Cloud:
         return a.value, v.value
 
 
+class KnnIndex:
+    """lio_knn_index: exact k nearest neighbours over a static cloud (pcl::KdTreeFLANN<PointXYZRGB> of texture_mesh, graph_utils.cpp:449-501).
+    Only finite points are indexed; distances are ((dx*dx) + dy*dy) + dz*dz in f32; results ascend in (d2, index), ties going to the smaller
+    input index; missing slots are (-1, +inf); a non-finite query has no neighbours."""
+
+    def __init__(self, device=0):
+        self.h = lib().lio_knn_index_create(device)
+        if not self.h:
+            raise capi.LioError("lio_knn_index_create failed: " + lib().lio_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_knn_index_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def build(self, xyz, rgb=None):
+        """xyz: n x 3; rgb: n packed 0x??RRGGBB words or None.  Returns the number of points indexed (the finite ones)."""
+        p = f32(xyz).reshape(-1, 3)
+        c = None if rgb is None else np.ascontiguousarray(rgb, np.uint32).reshape(-1)
+        if c is not None and len(c) != len(p):
+            raise ValueError("KnnIndex.build: one colour per point")
+        nf = C.c_uint64(0)
+        check(lib().lio_knn_index_build(self.h, ptr(p, C.c_float), None if c is None else ptr(c, C.c_uint32), len(p), C.byref(nf)), "knn index build")
+        return int(nf.value)
+
+    def query(self, q, k):
+        """(idx int32 m x k, d2 f32 m x k)"""
+        p = f32(q).reshape(-1, 3)
+        idx = np.empty((len(p), k), np.int32)
+        d2 = np.empty((len(p), k), np.float32)
+        check(lib().lio_knn_index_query(self.h, ptr(p, C.c_float), len(p), int(k), ptr(idx, C.c_int32), ptr(d2, C.c_float)), "knn index query")
+        return idx, d2
+
+    def colour(self, q, k=3):
+        """m x 3 uint8: floor-mean of the r, g, b bytes of each query's (up to) k neighbours; none -> 0, 0, 0"""
+        p = f32(q).reshape(-1, 3)
+        out = np.empty((len(p), 3), np.uint8)
+        check(lib().lio_knn_index_colour(self.h, ptr(p, C.c_float), len(p), int(k), ptr(out, C.c_uint8)), "knn index colour")
+        return out
+
+    def last_times(self):
+        """(build_us, query_us): device time of the last build and of the last query / colour call"""
+        b, q = C.c_double(0), C.c_double(0)
+        check(lib().lio_knn_index_last_times(self.h, C.byref(b), C.byref(q)), "knn index times")
+        return b.value, q.value
+
+
 def transform_cloud_f32(cloud, M):
     """pcl::transformPointCloud(in, out, M) for XYZ(I) points as PCL 1.9.1 evaluates it in f32: xyz = M(0..2, 0..3) * [x y z 1], left to right"""
     c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4).copy()
