@@ -56,8 +56,9 @@ int lio_device_count(void);
  * 5 = round 5 (LIO_JOB_HOST_RAW, lio_pinned_alloc / lio_pinned_free, lio_abi_version itself);
  * 6 = round 6 (lio_map_set_tie_mode / lio_map_tie_stats: candidates exactly as far as the fifth nearest are now kept as the reference keeps them);
  * 7 = lio_cloud_* (the dense-map export: a device-resident cloud that grows over a drive, and the VoxelGrid of the whole cloud);
- * 8 = lio_knn_index_* (exact k nearest neighbours over a static cloud; texture_mesh). */
-#define LIO_ABI_VERSION 8
+ * 8 = lio_knn_index_* (exact k nearest neighbours over a static cloud; texture_mesh);
+ * 9 = lio_ground_* (the ground detector: height clip, normals, plane RANSAC, inlier cloud). */
+#define LIO_ABI_VERSION 9
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -757,6 +758,81 @@ int lio_knn_index_query(lio_knn_index*, const float* q, uint64_t m, int k, int32
 int lio_knn_index_colour(lio_knn_index*, const float* q, uint64_t m, int k, uint8_t* rgb_out);
 /* device time (HIP events on the index's stream, no host copies) of the last build and of the last query / colour call (all its chunks) */
 int lio_knn_index_last_times(lio_knn_index*, double* build_us, double* query_us);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * Ground extraction on the device (csrc/ground.hip): detect_ground of slam/src/graph_utils.cpp:329-382 with plane_clip (:285-297) and
+ * normal_filtering (:299-327) -- the same stage as the mapping mode's floor detector, slam/backend/hdl_graph_slam/apps/
+ * floor_detection_nodelet.cpp:79-193.  PCL is restated from its published algorithms (1.9.1); where its behaviour cannot be reproduced the
+ * rule is this project's and is written here.  NULL from lio_ground_create without a device: there is no CPU fallback.
+ *   clip     a point is kept iff x, y, z are finite and sensor_height - clip_low <= z < sensor_height + clip_high, z compared in f64
+ *            (PlaneClipper3D with (0, 0, 1, .): inclusive, then negated, :337-338); input order kept.
+ *   normals  (use_normal_filter != 0) the k = 10 nearest clipped points of every clipped point, itself first, by the rules of lio_knn_index
+ *            (f32 distances, ties to the smaller index); centroid and 3 x 3 scatter about it in f64 over the neighbours in ascending
+ *            (d2, index) order; the unit eigenvector n of the smallest eigenvalue by cyclic Jacobi in f64 (THE PROJECT'S RULE: PCL's eigen
+ *            solver works in f32 and rounds differently); fewer than 3 neighbours: NaN, dropped.  Kept iff |n_z| > cos(normal_thresh_deg)|n|
+ *            (:316-320); order kept.
+ *   ransac   pcl::RandomSampleConsensus over SampleConsensusModelPlane, no refit.  THE PROJECT'S RULE for the draws (PCL's generator and
+ *            shuffle are not reproducible): with mix(x) = { x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 }
+ *            on uint32 and s = mix(seed ^ 0x9E3779B9), draw j over N points uses r_t = mix(s + 3 j + t), t = 0, 1, 2 (mod 2^32):
+ *              i0 = (r0 * N) >> 32;  i1 = (r1 * (N - 1)) >> 32, plus 1 if i1 >= i0;
+ *              i2 = (r2 * (N - 2)) >> 32, plus 1 if i2 >= min(i0, i1), then plus 1 if i2 >= max(i0, i1)      (64-bit products)
+ *            -- three distinct indices (lio_ground_draw computes them on the host).  The plane, every f32 operation rounded to nearest on
+ *            its own (no fused multiply-add), in this order: a = p1 - p0, b = p2 - p0;
+ *              c = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx);  l2 = (cx*cx + cy*cy) + cz*cz;  l = sqrt(l2);  n = c / l;
+ *              d = -(((nx*p0x) + ny*p0y) + nz*p0z).
+ *            A draw whose l2 is zero or not finite is bad and counts as PCL counts a skipped sample.  The score of a plane is the number
+ *            of points with |((nx*x + ny*y) + nz*z) + d| < (float)distance_threshold in f32.  The loop is ransac.hpp's, in draw order:
+ *            while (iterations < k && skipped < 10 max_iterations): a bad draw -> ++skipped; else a strictly larger count becomes the best
+ *            and k = log(1 - probability) / log(clamp(1 - pow(best / N, 3), eps, 1 - eps)), then ++iterations and stop once
+ *            iterations > max_iterations.  The device scores 64 draws per launch; draws past the loop's end are discarded.
+ *   result   none when fewer than min_points points are left after the filter, when the best plane has fewer than min_points inliers, or
+ *            when |n_z| < cos(floor_normal_thresh_deg) (:342, :356, :366-370); else the coefficients, negated if n_z < 0 (:373-375), and
+ *            the inliers of the `<` test in order (the points as they came in, intensity included).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_ground lio_ground;
+typedef struct lio_ground_params {
+    double sensor_height;            /* 0 */
+    double clip_low;                 /* height_clip_range_low */
+    double clip_high;                /* height_clip_range_high */
+    int32_t use_normal_filter;       /* the floor detector's use_normal_filtering; detect_ground always filters */
+    double normal_thresh_deg;        /* 20 */
+    int32_t k;                       /* neighbours of the normal estimation; only 10 is built */
+    double distance_threshold;       /* 0.1, compared as f32 */
+    int32_t min_points;              /* floor_pts_thresh = 1024 */
+    double floor_normal_thresh_deg;  /* 10 */
+    int32_t max_iterations;          /* 1000 (PCL's default) */
+    double probability;              /* 0.99 (PCL's default) */
+    uint32_t seed;                   /* of the draws */
+} lio_ground_params;
+/* preset 0: detect_ground (graph_utils.cpp:330-333: clip 1.5 / 1.5); preset 1: the floor detector's initialize_params
+ * (floor_detection_nodelet.cpp:38-46: clip 2.0 / 1.0) */
+void lio_ground_default_params(lio_ground_params*, int preset);
+/* draw j of a run with `seed` over n >= 3 points, by the rule above (host only; n < 3: zeros) */
+void lio_ground_draw(uint32_t seed, uint32_t j, uint32_t n, uint32_t out[3]);
+lio_ground* lio_ground_create(int device);
+void lio_ground_destroy(lio_ground*);
+/* detect_ground on the scan's raw cloud as it stands (after lio_scan_upload / lio_scan_undistort_poses).  *found = 1 and coeffs = (nx, ny, nz,
+ * d) with n_z >= 0 when there is a floor.  replace != 0 and a floor: the scan's raw cloud becomes the inlier cloud (extract.filter(*cloud),
+ * :377-380), which lio_cloud_append_scan then appends; otherwise the scan is left as it is.  The counts may be NULL. */
+int lio_ground_detect_scan(lio_ground*, lio_scan*, const lio_ground_params*, int replace, int* found, float coeffs[4], uint32_t* n_clipped,
+                           uint32_t* n_filtered, uint32_t* n_inliers);
+/* the same for n host points (x, y, z, intensity) */
+int lio_ground_detect_host(lio_ground*, const float* xyzi, uint64_t n, const lio_ground_params*, int* found, float coeffs[4], uint32_t* n_clipped,
+                           uint32_t* n_filtered, uint32_t* n_inliers);
+/* the stages of the last call; each returns the number of items, or -(items) when cap is too small.
+ * indices: positions in the input cloud of the clipped (stage 0), the filtered (1) and the inlier points (2), ascending;
+ * normals: n x 3, one per clipped point (nothing when the filter was off); inliers: the inlier cloud, n x 4;
+ * draws: every draw the device scored (whole batches of 64; lio_ground_last_run tells how many the loop used): its three indices into the
+ * filtered points, its count (0xFFFFFFFF: a bad draw) and its plane (NaN for a bad draw); any of the three arrays may be NULL */
+int64_t lio_ground_download_indices(lio_ground*, int stage, uint32_t* out, uint64_t cap);
+int64_t lio_ground_download_normals(lio_ground*, float* out_n3, uint64_t cap);
+int64_t lio_ground_download_inliers(lio_ground*, float* xyzi, uint64_t cap);
+int64_t lio_ground_download_draws(lio_ground*, uint32_t* triples, uint32_t* counts, float* planes, uint64_t cap);
+/* the replay of the last call: iterations and skipped draws of ransac.hpp's loop, draws consumed, and the winning draw (-1: none) */
+int lio_ground_last_run(lio_ground*, int* iterations, int* skipped, int* draws_used, int* winner);
+/* device time (HIP events on the detector's stream) of the last call: clip + k-NN + normals + filter, and RANSAC with the inlier selection
+ * (the host's replay between the batches included) */
+int lio_ground_last_times(lio_ground*, double* filter_us, double* ransac_us);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

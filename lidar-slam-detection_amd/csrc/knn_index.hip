@@ -10,7 +10,10 @@
 //   levels    a complete binary tree in heap order over the leaves (padded to a power of two with empty boxes), eight levels per launch
 //             folded in LDS
 //   query     the queries Morton-sorted the same way; one lane per query walks the tree nearer child first without a stack (the path is the
-//             node index, one bit per level says whether the lane is in the far child), the top k in registers ordered by (d2, index)
+//             node index, one bit per level says whether the lane is in the far child), the top k in registers ordered by (d2, index);
+//             knn_index_dev.h holds the same walk as a function for kernels of other files (kept apart from this kernel's own loop: inlined
+//             from a function the compiler lays it out with more branches and two more registers) and declares the build from device
+//             memory at the end of this file's namespace
 //
 // Exactness: a point's distance is ((dx*dx) + dy*dy) + dz*dz in f32 (d = p - q, no contraction: -ffp-contract=off); a box's bound is the same
 // expression over the clamped per-axis gaps max(lo - q, q - hi, 0).  Rounding is monotone, so the bound never exceeds the distance of a point
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "cloud_sort.h"
+#include "knn_index_dev.h"
 #include "lio_common.h"
 
 namespace lio {
@@ -30,10 +34,8 @@ constexpr int kThreads = 256;
 constexpr int kItems = 8;
 constexpr uint32_t kTile = kThreads * kItems;  // points per workgroup of the expand / compact
 constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kLeaf = 32;                 // points per leaf
 constexpr uint32_t kBoxBlocks = 1024;          // workgroups of the bbox's first level
 constexpr int kFold = 8;                       // tree levels per fold launch (256 nodes -> 1)
-constexpr uint32_t kNone = 0xFFFFFFFFu;        // an empty result slot
 constexpr uint64_t kQueryChunk = 1ull << 22;   // queries per device pass (bounds the query scratch)
 
 inline uint64_t tiles_of(uint64_t m) { return (m + kTile - 1) / kTile; }
@@ -246,34 +248,6 @@ __global__ __launch_bounds__(kThreads) void kx_fold(float4* __restrict__ nodes, 
     }
 }
 
-// lower bound of the f32 distance from q to any point of the box; `empty` for the padding boxes; *mid = squared distance to the box's centre
-// (visiting order only)
-__device__ __forceinline__ float box_bound(const float4* __restrict__ nodes, uint32_t node, float qx, float qy, float qz, bool* empty, float* mid) {
-    const float4 lo = nodes[2ull * node], hi = nodes[2ull * node + 1];
-    *empty = lo.x > hi.x;
-    const float cx = (lo.x + hi.x) * 0.5f - qx, cy = (lo.y + hi.y) * 0.5f - qy, cz = (lo.z + hi.z) * 0.5f - qz;
-    *mid = cx * cx + cy * cy + cz * cz;
-    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.f);
-    return gx * gx + gy * gy + gz * gz;
-}
-
-template <int K>
-__device__ __forceinline__ void consider(float d, uint32_t id, float (&kd)[K], uint32_t (&ki)[K]) {
-    if (!(d < kd[K - 1] || (d == kd[K - 1] && id < ki[K - 1]))) return;
-#pragma unroll
-    for (int s = 0; s < K; s++) {  // insertion: the candidate sinks to its place, the slots behind it move one down, the last drops out
-        const bool lt = d < kd[s] || (d == kd[s] && id < ki[s]);
-        const float td = kd[s];
-        const uint32_t ti = ki[s];
-        kd[s] = lt ? d : td;
-        ki[s] = lt ? id : ti;
-        d = lt ? td : d;
-        id = lt ? ti : id;
-    }
-}
-
 // one lane per query, in Morton order (perm); results go to the query's own position.  COLOUR: the floor-mean of the r, g, b bytes of the
 // (up to) K neighbours packed as 0x00RRGGBB; otherwise the K (index, d2) pairs, ascending (d2, index), empty slots (-1, +inf).
 template <int K, bool COLOUR>
@@ -298,9 +272,9 @@ __global__ __launch_bounds__(kThreads) void kx_query(const float* __restrict__ q
                     const uint32_t a = (node - P) * kLeaf, cnt = min(kLeaf, nf - a);
                     for (uint32_t t0 = 0; t0 < cnt; t0 += 8) {
                         float4 p[8];
-#pragma unroll
+    #pragma unroll
                         for (int u = 0; u < 8; u++) p[u] = leaves[a + min(t0 + u, cnt - 1u)];
-#pragma unroll
+    #pragma unroll
                         for (int u = 0; u < 8; u++) {
                             if (t0 + u >= cnt) break;
                             const float dx = p[u].x - qx, dy = p[u].y - qy, dz = p[u].z - qz;
@@ -419,6 +393,131 @@ int morton_sort(hipStream_t st, uint32_t* klo, const uint32_t* khi, uint32_t* va
         std::swap(va, vb);
     }
     *perm = va;
+    return LIO_OK;
+}
+
+// ---- the build from device memory (knn_index_dev.h): the same stages with the point count read from *d_n by every kernel, launched over
+// its upper bound n_max; the slots past the count sort last (key ~0) and end in empty leaf boxes ----
+__global__ __launch_bounds__(kThreads) void kxd_box_part(const float4* __restrict__ p, const uint32_t* __restrict__ d_n, float* __restrict__ parts) {
+    const uint32_t n = *d_n;
+    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
+        const float4 q = p[i];
+        v[0] = fminf(v[0], q.x); v[1] = fminf(v[1], q.y); v[2] = fminf(v[2], q.z);
+        v[3] = fmaxf(v[3], q.x); v[4] = fmaxf(v[4], q.y); v[5] = fmaxf(v[5], q.z);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int a = 0; a < 6; a++) v[a] = a < 3 ? fminf(v[a], __shfl_xor(v[a], off)) : fmaxf(v[a], __shfl_xor(v[a], off));
+    __shared__ float red[kWaves][6];
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 6; a++) red[threadIdx.x >> 6][a] = v[a];
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int a = threadIdx.x;
+        float r = red[0][a];
+        for (int w = 1; w < kWaves; w++) r = a < 3 ? fminf(r, red[w][a]) : fmaxf(r, red[w][a]);
+        parts[6u * blockIdx.x + a] = r;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void kxd_keys_points(const float4* __restrict__ p, const uint32_t* __restrict__ d_n, uint32_t n_max,
+                                                            const float* __restrict__ box, uint32_t* __restrict__ klo, uint32_t* __restrict__ khi,
+                                                            uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n_max) return;
+    uint64_t k = ~0ull;
+    if (i < *d_n) {
+        const float4 q = p[i];
+        k = morton(q.x, q.y, q.z, box);
+    }
+    klo[i] = (uint32_t)k;
+    khi[i] = (uint32_t)(k >> 32);
+    vals[i] = i;
+}
+
+__global__ __launch_bounds__(kThreads) void kxd_gather_points(const float4* __restrict__ src, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ d_n,
+                                                              float4* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < *d_n) dst[i] = src[idx[i]];  // (the stable sort keeps the n valid slots, whose keys are below ~0 or equal to it at a smaller position, first)
+}
+
+__global__ __launch_bounds__(kThreads) void kxd_leaf_boxes(const float4* __restrict__ leaves, const uint32_t* __restrict__ d_n, uint32_t P, float4* __restrict__ nodes) {
+    const uint32_t l = blockIdx.x * kThreads + threadIdx.x;
+    if (l >= P) return;
+    const uint32_t nf = *d_n, nl = (nf + kLeaf - 1) / kLeaf;
+    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
+    if (l < nl) {
+        const uint32_t a = l * kLeaf, b = min(a + kLeaf, nf);
+        for (uint32_t j = a; j < b; j++) {
+            const float4 p = leaves[j];
+            lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
+            hi.x = fmaxf(hi.x, p.x); hi.y = fmaxf(hi.y, p.y); hi.z = fmaxf(hi.z, p.z);
+        }
+    }
+    nodes[2ull * (P + l)] = lo;
+    nodes[2ull * (P + l) + 1] = hi;
+}
+
+static uint32_t leaf_slots(uint64_t n, int* L) {
+    const uint32_t nl = (uint32_t)((std::max<uint64_t>(n, 1) + kLeaf - 1) / kLeaf);
+    int l = 0;
+    while ((1u << l) < nl) l++;
+    *L = l;
+    return 1u << l;
+}
+
+void device_index_free(DeviceIndex& x) {
+    void* all[] = {x.leaves, x.nodes, x.box, x.parts, x.klo, x.khi, x.vals, x.kb, x.vb, x.scratch};
+    for (void* p : all)
+        if (p) (void)hipFree(p);
+    x = DeviceIndex();
+}
+
+int device_index_reserve(DeviceIndex& x, uint64_t n_max) {
+    if (n_max <= x.cap) return LIO_OK;
+    if (n_max > 0x7FFFFFFFull) { set_error("knn index: %llu points exceed the int index range (2^31 - 1)", (unsigned long long)n_max); return LIO_E_CAPACITY; }
+    const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(n_max, std::max<uint64_t>(2 * x.cap, 1ull << 16)), 0x7FFFFFFFull);
+    device_index_free(x);
+    int L = 0;
+    const uint32_t P = leaf_slots(want, &L);
+    bool ok = hipMalloc(&x.leaves, want * sizeof(float4)) == hipSuccess && hipMalloc(&x.nodes, 4ull * P * sizeof(float4)) == hipSuccess &&
+              hipMalloc(&x.box, 8 * sizeof(float)) == hipSuccess && hipMalloc(&x.parts, 6ull * kBoxBlocks * sizeof(float)) == hipSuccess &&
+              hipMalloc(&x.scratch, cloud::radix_scratch_words(want) * sizeof(uint32_t)) == hipSuccess;
+    uint32_t** w[] = {&x.klo, &x.khi, &x.vals, &x.kb, &x.vb};
+    for (uint32_t** p : w) ok = ok && hipMalloc(p, want * sizeof(uint32_t)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        device_index_free(x);
+        set_error("knn index: device memory for a tree over %llu points not available", (unsigned long long)want);
+        return LIO_E_DEVICE;
+    }
+    x.cap = want;
+    return LIO_OK;
+}
+
+int device_index_build(hipStream_t st, DeviceIndex& x, const float4* pts, const uint32_t* d_n, uint32_t n_max) {
+    if (n_max == 0 || n_max > x.cap) return LIO_E_INVALID;
+    const uint32_t nb = std::min<uint32_t>(blocks_of(n_max), kBoxBlocks);
+    kxd_box_part<<<dim3(nb), dim3(kThreads), 0, st>>>(pts, d_n, x.parts);
+    kx_box_fold<<<dim3(1), dim3(kThreads), 0, st>>>(x.parts, nb, x.box);
+    kxd_keys_points<<<dim3(blocks_of(n_max)), dim3(kThreads), 0, st>>>(pts, d_n, n_max, x.box, x.klo, x.khi, x.vals);
+    LIO_HIP_TRY(hipGetLastError());
+    uint32_t* perm = nullptr;
+    const int rc = morton_sort(st, x.klo, x.khi, x.vals, x.kb, x.vb, n_max, x.scratch, &perm);
+    if (rc != LIO_OK) return rc;
+    kxd_gather_points<<<dim3(blocks_of(n_max)), dim3(kThreads), 0, st>>>(pts, perm, d_n, x.leaves);
+    x.P = leaf_slots(n_max, &x.L);
+    kxd_leaf_boxes<<<dim3(blocks_of(x.P)), dim3(kThreads), 0, st>>>(x.leaves, d_n, x.P, x.nodes);
+    LIO_HIP_TRY(hipGetLastError());
+    for (int lv = x.L; lv > 0;) {
+        const int f = std::min(lv, kFold);
+        const uint32_t first = 1u << lv;
+        kx_fold<<<dim3(std::max<uint32_t>(1u, first / kThreads)), dim3(kThreads), 0, st>>>(x.nodes, first, f);
+        lv -= f;
+    }
+    LIO_HIP_TRY(hipGetLastError());
     return LIO_OK;
 }
 

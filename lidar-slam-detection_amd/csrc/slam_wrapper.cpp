@@ -972,6 +972,9 @@ struct Accumulate {
     lio_cloud* cloud = nullptr;
     lio_scan* scan = nullptr;  // the frame being undistorted
     uint32_t scan_cap = 0;
+    lio_ground* ground = nullptr;  // detect_ground on the device, once set_ground_extraction enabled it
+    bool ground_on = false;
+    uint32_t ground_seed = 0;
 };
 Accumulate g_acc;
 
@@ -1137,13 +1140,39 @@ void save_undistortion_cloud(std::string file, py::array_t<float>& points, py::d
     if (n == 0) return;  // (savePCDFileBinary refuses an empty cloud)
     require(write_pcd_binary(file, out.data(), (size_t)n), "save_undistortion_cloud: cannot write the file");
 }
+// the detector of accumulate_cloud(extract_ground=True) and _detect_ground; throws when there is no device
+void need_ground(const char* what) {
+    if (g_acc.ground) return;
+    g_acc.ground = lio_ground_create(0);
+    if (!g_acc.ground) throw std::runtime_error(std::string("slam_wrapper: ") + what + ": ground extraction needs a HIP device (there is no CPU fallback): " + lio_last_error());
+}
+// Turns accumulate_cloud(extract_ground=True) on or off (off by default: the call then raises ValueError as before).  The stage is
+// detect_ground of graph_utils.cpp:329-382 on the device (include/lio_hip.h: lio_ground_*); the RANSAC's draws are THIS MODULE'S, a
+// counter-based generator of (seed, draw number), not PCL's random shuffle: the same frames and seed give the same cloud on every run,
+// and a different plane hypothesis sequence than the reference's on any run.
+void set_ground_extraction(bool enable, uint32_t seed) {
+    g_acc.ground_on = enable;
+    g_acc.ground_seed = seed;
+}
 void accumulate_cloud(py::array_t<float>& points, py::dict& points_attr, py::array_t<double>& poses, std::string odometry_type, bool extract_ground) {
     if (odometry_type != "TUM")
         throw std::invalid_argument("slam_wrapper: accumulate_cloud: odometry_type '" + odometry_type + "' is not supported (only \"TUM\"; the reference indexes an empty pose list)");
-    if (extract_ground)
-        throw std::invalid_argument("slam_wrapper: accumulate_cloud: extract_ground=True is not supported (detect_ground, PCL normals + RANSAC, is out of scope)");
+    if (extract_ground && !g_acc.ground_on)
+        throw std::invalid_argument("slam_wrapper: accumulate_cloud: extract_ground=True is off by default (detect_ground runs on the device with this "
+                                    "module's own RANSAC draws, not PCL's: enable it with set_ground_extraction(True, seed))");
+    if (extract_ground) need_ground("accumulate_cloud");  // (before the frame touches the device: nothing changes when there is none)
     const std::vector<TumPose> tum = tum_poses(poses);
     undistort_frame(points, points_attr, tum, "accumulate_cloud");
+    if (extract_ground) {
+        // detect_ground(cloud->cloud) in the sensor frame, graph_utils.cpp:421-423: no floor, no append; else the cloud is the inlier cloud
+        lio_ground_params gp;
+        lio_ground_default_params(&gp, 0);
+        gp.seed = g_acc.ground_seed;
+        int found = 0;
+        float coeffs[4];
+        require(lio_ground_detect_scan(g_acc.ground, g_acc.scan, &gp, 1, &found, coeffs, nullptr, nullptr, nullptr) == LIO_OK, "accumulate_cloud: ground detection failed");
+        if (!found) return;
+    }
     if (!g_acc.cloud) {
         g_acc.cloud = lio_cloud_create(0, 0);
         require(g_acc.cloud != nullptr, "accumulate_cloud: no HIP device");
@@ -1470,6 +1499,24 @@ py::tuple _read_obj(std::string path) {
     }
     return py::make_tuple(a, fl);
 }
+// detect_ground (graph_utils.cpp:329-382; preset 1: the floor detector's parameters) over a host cloud: (coeffs (4,) f32 or None, inliers N x 4)
+py::tuple _detect_ground(py::array_t<float>& points, int preset, uint32_t seed) {
+    std::vector<float> xyzi = xyzi_of(points, "_detect_ground");
+    need_ground("_detect_ground");
+    lio_ground_params gp;
+    lio_ground_default_params(&gp, preset);
+    gp.seed = seed;
+    int found = 0;
+    float coeffs[4];
+    uint32_t ni = 0;
+    require(lio_ground_detect_host(g_acc.ground, xyzi.data(), xyzi.size() / 4, &gp, &found, coeffs, nullptr, nullptr, &ni) == LIO_OK, "_detect_ground failed");
+    if (!found) return py::make_tuple(py::none(), py::array_t<float>(std::vector<py::ssize_t>{0, 4}));
+    py::array_t<float> in({(py::ssize_t)ni, (py::ssize_t)4});
+    require(lio_ground_download_inliers(g_acc.ground, in.mutable_data(), ni) == (int64_t)ni, "_detect_ground: download failed");
+    py::array_t<float> co(4);
+    std::memcpy(co.mutable_data(), coeffs, sizeof(coeffs));
+    return py::make_tuple(co, in);
+}
 void _write_mesh_ply(std::string path, py::array_t<float, py::array::c_style | py::array::forcecast> vertices,
                      py::array_t<uint8_t, py::array::c_style | py::array::forcecast> rgb, py::list faces) {
     if (vertices.ndim() != 2 || vertices.shape(1) != 3) throw std::invalid_argument("slam_wrapper: _write_mesh_ply: vertices must be m x 3");
@@ -1548,6 +1595,10 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("_tum_relative_poses", &_tum_relative_poses, py::arg("poses"));
     m.def("_read_rgb_pcd", &_read_rgb_pcd, py::arg("path"));
     m.def("_read_obj", &_read_obj, py::arg("path"));
+    m.def("set_ground_extraction", &set_ground_extraction,
+          "accumulate_cloud(extract_ground=True) on the device (off by default); the RANSAC draws are this module's counter-based generator of (seed, draw), not PCL's",
+          py::arg("enable"), py::arg("seed") = 0);
+    m.def("_detect_ground", &_detect_ground, py::arg("points"), py::arg("preset") = 0, py::arg("seed") = 0);
     m.def("_write_mesh_ply", &_write_mesh_ply, py::arg("path"), py::arg("vertices"), py::arg("rgb"), py::arg("faces"));
     m.def("_set_capacity", &_set_capacity, py::arg("max_points"), py::arg("max_voxels"));
 }

@@ -37,6 +37,9 @@ SYMBOLS = [
     "lio_cloud_create", "lio_cloud_destroy", "lio_cloud_clear", "lio_cloud_size", "lio_cloud_append_scan", "lio_cloud_append_host",
     "lio_cloud_voxel_downsample", "lio_cloud_download", "lio_cloud_scratch_bytes", "lio_cloud_last_times",
     "lio_knn_index_create", "lio_knn_index_destroy", "lio_knn_index_build", "lio_knn_index_query", "lio_knn_index_colour", "lio_knn_index_last_times",
+    "lio_ground_default_params", "lio_ground_draw", "lio_ground_create", "lio_ground_destroy", "lio_ground_detect_scan", "lio_ground_detect_host",
+    "lio_ground_download_indices", "lio_ground_download_normals", "lio_ground_download_inliers", "lio_ground_download_draws", "lio_ground_last_run",
+    "lio_ground_last_times",
     "lio_pose_estimator_create", "lio_pose_estimator_destroy", "lio_pose_estimator_predict", "lio_pose_estimator_match", "lio_pose_estimator_match_gps", "lio_pose_estimator_guess", "lio_pose_estimator_observe",
     "lio_pose_estimator_match_gps_only", "lio_pose_estimator_get_timed_pose", "lio_pose_estimator_predict_nostate",
     "lio_pose_estimator_correct", "lio_pose_estimator_get_dt", "lio_pose_estimator_get", "lio_pose_estimator_set", "lio_pose_estimator_matrix",
@@ -92,6 +95,12 @@ class GpsObservation(C.Structure):  # lio_gps_observation
 class NdtParams(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("lm_max_iterations", C.c_int32), ("rotation_epsilon_deg", C.c_double),
                 ("transformation_epsilon", C.c_double), ("lm_init_lambda_factor", C.c_double), ("max_process_time_ms", C.c_double)]
+
+
+class GroundParams(C.Structure):  # lio_ground_params
+    _fields_ = [("sensor_height", C.c_double), ("clip_low", C.c_double), ("clip_high", C.c_double), ("use_normal_filter", C.c_int32),
+                ("normal_thresh_deg", C.c_double), ("k", C.c_int32), ("distance_threshold", C.c_double), ("min_points", C.c_int32),
+                ("floor_normal_thresh_deg", C.c_double), ("max_iterations", C.c_int32), ("probability", C.c_double), ("seed", C.c_uint32)]
 
 
 class AlignJob(C.Structure):  # lio_align_job
@@ -243,6 +252,19 @@ def lib():
     sig("lio_knn_index_query", cint, vp, f32p, u64, cint, i32p, f32p)
     sig("lio_knn_index_colour", cint, vp, f32p, u64, cint, u8p)
     sig("lio_knn_index_last_times", cint, vp, f64p, f64p)
+    gp, u32p = C.POINTER(GroundParams), C.POINTER(u32)
+    sig("lio_ground_default_params", None, gp, cint)
+    sig("lio_ground_draw", None, u32, u32, u32, u32p)
+    sig("lio_ground_create", vp, cint)
+    sig("lio_ground_destroy", None, vp)
+    sig("lio_ground_detect_scan", cint, vp, vp, gp, cint, C.POINTER(cint), f32p, u32p, u32p, u32p)
+    sig("lio_ground_detect_host", cint, vp, f32p, u64, gp, C.POINTER(cint), f32p, u32p, u32p, u32p)
+    sig("lio_ground_download_indices", C.c_int64, vp, cint, u32p, u64)
+    sig("lio_ground_download_normals", C.c_int64, vp, f32p, u64)
+    sig("lio_ground_download_inliers", C.c_int64, vp, f32p, u64)
+    sig("lio_ground_download_draws", C.c_int64, vp, u32p, u32p, f32p, u64)
+    sig("lio_ground_last_run", cint, vp, C.POINTER(cint), C.POINTER(cint), C.POINTER(cint), C.POINTER(cint))
+    sig("lio_ground_last_times", cint, vp, f64p, f64p)
     sig("lio_pose_estimator_create", vp, f32p, u64, f32p, f32p, dbl)
     sig("lio_pose_estimator_destroy", None, vp)
     sig("lio_pose_estimator_predict", cint, vp, u64, f32p, f32p)

@@ -770,6 +770,129 @@ class KnnIndex:
         return b.value, q.value
 
 
+class GroundDetector:
+    """lio_ground: detect_ground of graph_utils.cpp:329-382 (the floor detector of floor_detection_nodelet.cpp:79-193) on the device: height
+    clip, normals from the 10 nearest neighbours, verticality filter, plane RANSAC, inlier cloud.  The draws of the RANSAC are this project's
+    (a counter-based generator of (seed, draw number), include/lio_hip.h; `ground_draw` restates it), not PCL's: the same seed gives the same
+    result on every run."""
+
+    def __init__(self, device=0):
+        self.h = lib().lio_ground_create(device)
+        if not self.h:
+            raise capi.LioError("lio_ground_create failed: " + lib().lio_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_ground_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def params(preset=0, **over):
+        """lio_ground_params of a preset (0: detect_ground, clip 1.5 / 1.5; 1: the floor detector, clip 2.0 / 1.0), fields overridden by name"""
+        p = capi.GroundParams()
+        lib().lio_ground_default_params(C.byref(p), int(preset))
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise ValueError(f"lio_ground_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+    def _result(self, found, co, nc, nf, ni):
+        return dict(found=bool(found.value), coeffs=co.copy() if found.value else None, n_clipped=int(nc.value), n_filtered=int(nf.value),
+                    n_inliers=int(ni.value))
+
+    def detect_scan(self, scan, params=None, replace=False):
+        p = params if params is not None else self.params()
+        found, co = C.c_int(0), np.zeros(4, np.float32)
+        nc, nf, ni = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().lio_ground_detect_scan(self.h, scan.h, C.byref(p), int(bool(replace)), C.byref(found), ptr(co, C.c_float), C.byref(nc), C.byref(nf),
+                                           C.byref(ni)), "ground detect_scan")
+        return self._result(found, co, nc, nf, ni)
+
+    def detect_host(self, xyzi, params=None):
+        p = params if params is not None else self.params()
+        pts = f32(xyzi).reshape(-1, 4)
+        found, co = C.c_int(0), np.zeros(4, np.float32)
+        nc, nf, ni = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(lib().lio_ground_detect_host(self.h, ptr(pts, C.c_float), len(pts), C.byref(p), C.byref(found), ptr(co, C.c_float), C.byref(nc), C.byref(nf),
+                                           C.byref(ni)), "ground detect_host")
+        return self._result(found, co, nc, nf, ni)
+
+    def indices(self, stage):
+        """positions in the input cloud of the clipped (0), filtered (1) or inlier (2) points of the last call"""
+        n = -lib().lio_ground_download_indices(self.h, int(stage), None, 0)
+        out = np.zeros(max(n, 0), np.uint32)
+        if n > 0:
+            check(int(lib().lio_ground_download_indices(self.h, int(stage), ptr(out, C.c_uint32), n)), "ground indices")
+        return out
+
+    def normals(self):
+        """n x 3 f32, one per clipped point of the last call"""
+        n = -lib().lio_ground_download_normals(self.h, None, 0)
+        out = np.zeros((max(n, 0), 3), np.float32)
+        if n > 0:
+            check(int(lib().lio_ground_download_normals(self.h, ptr(out, C.c_float), n)), "ground normals")
+        return out
+
+    def inliers(self):
+        """the inlier cloud of the last call, n x 4"""
+        n = -lib().lio_ground_download_inliers(self.h, None, 0)
+        out = np.zeros((max(n, 0), 4), np.float32)
+        if n > 0:
+            check(int(lib().lio_ground_download_inliers(self.h, ptr(out, C.c_float), n)), "ground inliers")
+        return out
+
+    def draws(self):
+        """(triples n x 3 u32, counts n u32 (0xFFFFFFFF: a bad draw), planes n x 4 f32) of every draw the device scored in the last call"""
+        n = -lib().lio_ground_download_draws(self.h, None, None, None, 0)
+        n = max(n, 0)
+        t, c, pl = np.zeros((n, 3), np.uint32), np.zeros(n, np.uint32), np.zeros((n, 4), np.float32)
+        if n > 0:
+            check(int(lib().lio_ground_download_draws(self.h, ptr(t, C.c_uint32), ptr(c, C.c_uint32), ptr(pl, C.c_float), n)), "ground draws")
+        return t, c, pl
+
+    def last_run(self):
+        """dict(iterations, skipped, draws_used, winner) of ransac.hpp's loop as the last call replayed it"""
+        a, b, c, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().lio_ground_last_run(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "ground last_run")
+        return dict(iterations=a.value, skipped=b.value, draws_used=c.value, winner=d.value)
+
+    def last_times(self):
+        """(filter_us, ransac_us): device time of clip + k-NN + normals + filter, and of the RANSAC with the inlier selection"""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib().lio_ground_last_times(self.h, C.byref(a), C.byref(b)), "ground times")
+        return a.value, b.value
+
+
+def _mix32(x):
+    x = np.asarray(x, np.uint64) & np.uint64(0xFFFFFFFF)
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & np.uint64(0xFFFFFFFF)
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & np.uint64(0xFFFFFFFF)
+    return x ^ (x >> np.uint64(16))
+
+
+def ground_draw(seed, j, n):
+    """the three distinct indices of draws j (an integer or an array) of a RANSAC run with `seed` over n >= 3 points: include/lio_hip.h's rule
+    in numpy integer arithmetic (uint64 holding 32-bit values).  Returns an array (..., 3) of int64."""
+    M = np.uint64(0xFFFFFFFF)
+    j = np.asarray(j, np.uint64)
+    s = _mix32(np.uint64(int(seed) & 0xFFFFFFFF) ^ np.uint64(0x9E3779B9))
+    r = [_mix32((s + np.uint64(3) * j + np.uint64(t)) & M) for t in range(3)]
+    N = np.uint64(n)
+    i0 = (r[0] * N) >> np.uint64(32)
+    i1 = (r[1] * (N - np.uint64(1))) >> np.uint64(32)
+    i1 = i1 + (i1 >= i0).astype(np.uint64)
+    i2 = (r[2] * (N - np.uint64(2))) >> np.uint64(32)
+    lo, hi = np.minimum(i0, i1), np.maximum(i0, i1)
+    i2 = i2 + (i2 >= lo).astype(np.uint64)
+    i2 = i2 + (i2 >= hi).astype(np.uint64)
+    return np.stack([i0, i1, i2], -1).astype(np.int64)
+
+
 def transform_cloud_f32(cloud, M):
     """pcl::transformPointCloud(in, out, M) for XYZ(I) points as PCL 1.9.1 evaluates it in f32: xyz = M(0..2, 0..3) * [x y z 1], left to right"""
     c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4).copy()
