@@ -57,8 +57,9 @@ int lio_device_count(void);
  * 6 = round 6 (lio_map_set_tie_mode / lio_map_tie_stats: candidates exactly as far as the fifth nearest are now kept as the reference keeps them);
  * 7 = lio_cloud_* (the dense-map export: a device-resident cloud that grows over a drive, and the VoxelGrid of the whole cloud);
  * 8 = lio_knn_index_* (exact k nearest neighbours over a static cloud; texture_mesh);
- * 9 = lio_ground_* (the ground detector: height clip, normals, plane RANSAC, inlier cloud). */
-#define LIO_ABI_VERSION 9
+ * 9 = lio_ground_* (the ground detector: height clip, normals, plane RANSAC, inlier cloud);
+ * 10 = lio_bev_* (the bird's-eye intensity image of a dense map: noise filter, per-pixel means, patch equalisation, 16-bit image). */
+#define LIO_ABI_VERSION 10
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -833,6 +834,79 @@ int lio_ground_last_run(lio_ground*, int* iterations, int* skipped, int* draws_u
 /* device time (HIP events on the detector's stream) of the last call: clip + k-NN + normals + filter, and RANSAC with the inlier selection
  * (the host's replay between the batches included) */
 int lio_ground_last_times(lio_ground*, double* filter_us, double* ransac_us);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * Bird's-eye intensity image of a dense map on the device (csrc/bev.hip): tools/postprocessing/convert_cloud_image.py, function by function,
+ * under numpy 2 promotion rules (Python scalars are weak, f32 arrays stay f32).  Where the reference is undefined or cannot be followed the
+ * rule is THE PROJECT'S and is marked so.  NULL from lio_bev_create without a device: there is no CPU fallback.
+ *   bounds   (load_pointcloud) PROJECT: points whose x, y or intensity is not finite are dropped first and counted (the reference's min / max
+ *            turn NaN); none left: LIO_E_INVALID.  x_min .. y_max are the f32 extremes; image_w = ceil((x_max - x_min) ppm) + 1 in f64, image_h
+ *            likewise; xs = rint((x - x_min) * (float)ppm), ys = rint((-(y - y_max)) * (float)ppm) in f32, ties to even.  The pixel key is
+ *            ys image_w + xs in 32 bits.  PROJECT: a side above 2^22 pixels or image_w image_h above 2^32 - 1 is LIO_E_CAPACITY (the key never
+ *            wraps), and so is a coordinate that leaves the image.
+ *   noise    (filter_noise) the m finite points in ascending (intensity, input index) order, -0.0 equal to +0.0 (PROJECT: numpy's argsort
+ *            leaves the order of equal intensities open); ranks [int(m 0.01), int(m 0.999)) (f64 products) are kept, in that order.
+ *   means    (scatter) occupied pixels in ascending key order; intensity and z of a pixel are f32 sums over its kept points taken one after
+ *            the other in that (intensity, input index) order, divided by the f32 count.
+ *   nodes    (convert) P = int(window ppm), h = int(P / 2), q = int(h / 2); the image is padded to W = int((image_w + h) / h) h, H likewise;
+ *            nodes at xi = 0, h, .., W and yi = 0, h, .., H; node number (xi / h) (H / h + 1) + yi / h.  A node runs when more than 100
+ *            occupied pixels lie in [xi - P, xi + P] x [yi - P, yi + P] (PROJECT: and one of them has a value in [0, 65535]; the reference
+ *            divides by zero there).  P < 2 is LIO_E_INVALID (the reference's range() has step 0).
+ *   equalise (intensity_normalize) v = I * 65535 in f32.  numpy's histogram with 1024 bins over [0, 65535]: edges e_i = f32(i * 65535 / 1024),
+ *            bin = the f32 estimate (v / 65535) * 1024 truncated, stepped down or up once against the edges, values outside ignored, the last
+ *            bin closed; density n_i / f64(e_(i+1) - e_i in f32) / N, its cumulative sum in f64 one bin after the other, cdf = (65535 cdf)
+ *            / cdf[1023].  interp(v): cdf[0] below 0, cdf[1023] from e_1023 on, cdf[j] at an edge, else slope_j (v - e_j) + cdf[j] in f64
+ *            with slope_j = (cdf[j+1] - cdf[j]) / (e_(j+1) - e_j); amplify = interp(v) / f64(max(v, 0.001f)); value(c) = f64(v) *
+ *            min(amplify, c).
+ *            PROJECT (numpy's pairwise f32 / f64 sums cannot be followed in parallel): a mean is sum(t) / count with every term
+ *            t = rint(clamp(x, -2^23, 2^23) * 2^16) as a 64-bit integer (NaN: 0) -- exact, so the same in any order.  mean(v) is that sum
+ *            over f64(v), rounded as f32((S / 2^16) / count); c_0 = f32(20480 / mean) and c_(k+1) = c_k + 0.1f in f32 when c_0 > 1, else
+ *            c_0 = 1.0 and c_(k+1) = c_k + 0.1 in f64 (Python's float, as max(1.0, .) returns it); the table ends at the first
+ *            c_k >= 120.  The step is the first k at which the table ends or sum(t(value(c_k))) >= 20480 * 2^16 * count: by bisection
+ *            when no v is negative (the sum is then monotone in c), by the reference's linear scan otherwise.  The node's result for a
+ *            pixel is f32(clip(value(c_step), 0, 65535)) (NaN: 0).
+ *   render   (convert, bev_generate) a pixel takes the result of the last running node, xi major and yi minor, whose inner region
+ *            [xi - q, xi + q] x [yi - q, yi + q] holds it; a pixel no running node holds keeps its raw mean I (not scaled: it renders as grey
+ *            0 or 1).  g = rint(value) in f32, ties to even (PROJECT: clamped to [0, 65535]; the reference indexes out of range), and the
+ *            image is grey[g] at (ys, xs) of the zero-filled H x W uint16 image, grey[i] = trunc(t_i * 65535) in f64 with
+ *            t_i = i * (1 / 65535), t_65535 = 1 (matplotlib's 'gray' resampled to 65536 entries; 88 entries are i - 1).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_bev lio_bev;
+typedef struct lio_bev_info {
+    uint32_t n_in, n_dropped;        /* points given; points dropped as not finite */
+    uint32_t n_kept, rank_lo, rank_hi; /* the noise filter's kept ranks [rank_lo, rank_hi) of the finite points */
+    uint32_t n_pixels;               /* occupied pixels */
+    uint32_t image_w, image_h;       /* load_pointcloud's size */
+    uint32_t padded_w, padded_h;     /* the image's size (after lio_bev_convert) */
+    int32_t patch, half_patch, quarter_patch;
+    uint32_t nodes_x, nodes_y;
+    uint32_t reserved;
+    double pixel_per_meter, x_min, x_max, y_min, y_max;
+} lio_bev_info;
+lio_bev* lio_bev_create(int device);
+void lio_bev_destroy(lio_bev*);
+/* load_pointcloud + filter_noise + scatter over n host points (x, y, z, intensity), or over the points of a lio_cloud where they lie */
+int lio_bev_preprocess_host(lio_bev*, const float* xyzi, uint64_t n, double pixel_per_meter);
+int lio_bev_preprocess_cloud(lio_bev*, lio_cloud*, double pixel_per_meter);
+/* a pixel list from elsewhere instead (convert's arguments): n strictly ascending keys ys image_w + xs with their intensities (z may be NULL) */
+int lio_bev_upload_pixels(lio_bev*, const uint32_t* keys, const float* intensity, const float* z, uint64_t n, uint32_t image_w, uint32_t image_h);
+/* convert + bev_generate over the handle's pixel list */
+int lio_bev_convert(lio_bev*, double window, double pixel_per_meter);
+int lio_bev_get_info(lio_bev*, lio_bev_info* out);
+/* the stages of the last calls; each returns the number of items, or -(items) when cap (in items) is too small.
+ * pixel_coords: (xs, ys) per input point, (-1, -1) for a dropped one; kept: input indices of the kept points in (intensity, index) order;
+ * pixels: key, mean intensity and mean z per occupied pixel (any array may be NULL); nodes: occupied pixels in the window, step (-1: the node
+ * did not run) and clip limit per node (any may be NULL); equalised: the f32 value per occupied pixel before rint; image: padded_h x padded_w */
+int64_t lio_bev_download_pixel_coords(lio_bev*, int32_t* xy, uint64_t cap);
+int64_t lio_bev_download_kept(lio_bev*, uint32_t* idx, uint64_t cap);
+int64_t lio_bev_download_pixels(lio_bev*, uint32_t* keys, float* intensity, float* z, uint64_t cap);
+int64_t lio_bev_download_nodes(lio_bev*, uint32_t* count, int32_t* step, double* clip, uint64_t cap);
+int64_t lio_bev_download_equalised(lio_bev*, float* out, uint64_t cap);
+int64_t lio_bev_download_image(lio_bev*, uint16_t* out, uint64_t cap);
+/* the grey table above (host only) */
+void lio_bev_grey_table(uint16_t out[65536]);
+/* device time (HIP events on the handle's stream) of the last preprocess (the two host read-backs included) and of the last convert */
+int lio_bev_last_times(lio_bev*, double* preprocess_us, double* convert_us);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

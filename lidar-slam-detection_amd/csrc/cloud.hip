@@ -665,6 +665,12 @@ struct lio_cloud {
     double append_us, voxel_us;
 };
 
+namespace lio {
+namespace cloud {
+CloudView cloud_view(const lio_cloud* c) { return CloudView{c->pts, c->n, c->stream, c->device}; }
+}  // namespace cloud
+}  // namespace lio
+
 namespace {
 
 // the sort scratch of one voxel grid over n points, carved from one allocation (256-byte aligned pieces)

@@ -1,7 +1,10 @@
-// cloud_sort.h -- the device-wide scan and the stable radix pass of cloud.hip, for the other files that sort (knn_index.hip).
+// cloud_sort.h -- the device-wide scan and the stable radix pass of cloud.hip, for the other files that sort (knn_index.hip, bev.hip), and the
+// view of a lio_cloud's device points for the files that read a whole cloud (bev.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+struct lio_cloud;
 
 namespace lio {
 namespace cloud {
@@ -14,6 +17,15 @@ int exclusive_scan(hipStream_t st, uint32_t* data, uint64_t m, uint32_t* aux);
 // scratch holds radix_scratch_words(n) words
 uint64_t radix_scratch_words(uint64_t n);
 int radix_pass(hipStream_t st, const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout, uint32_t n, int shift, uint32_t* scratch);
+
+// the points of a cloud as they lie on the device, and the stream its appends and voxel grid run on
+struct CloudView {
+    const float4* pts;
+    uint64_t n;
+    hipStream_t stream;
+    int device;
+};
+CloudView cloud_view(const lio_cloud* c);
 
 }  // namespace cloud
 }  // namespace lio

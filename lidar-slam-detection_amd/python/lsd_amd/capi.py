@@ -40,6 +40,9 @@ SYMBOLS = [
     "lio_ground_default_params", "lio_ground_draw", "lio_ground_create", "lio_ground_destroy", "lio_ground_detect_scan", "lio_ground_detect_host",
     "lio_ground_download_indices", "lio_ground_download_normals", "lio_ground_download_inliers", "lio_ground_download_draws", "lio_ground_last_run",
     "lio_ground_last_times",
+    "lio_bev_create", "lio_bev_destroy", "lio_bev_preprocess_host", "lio_bev_preprocess_cloud", "lio_bev_upload_pixels", "lio_bev_convert", "lio_bev_get_info",
+    "lio_bev_download_pixel_coords", "lio_bev_download_kept", "lio_bev_download_pixels", "lio_bev_download_nodes", "lio_bev_download_equalised",
+    "lio_bev_download_image", "lio_bev_grey_table", "lio_bev_last_times",
     "lio_pose_estimator_create", "lio_pose_estimator_destroy", "lio_pose_estimator_predict", "lio_pose_estimator_match", "lio_pose_estimator_match_gps", "lio_pose_estimator_guess", "lio_pose_estimator_observe",
     "lio_pose_estimator_match_gps_only", "lio_pose_estimator_get_timed_pose", "lio_pose_estimator_predict_nostate",
     "lio_pose_estimator_correct", "lio_pose_estimator_get_dt", "lio_pose_estimator_get", "lio_pose_estimator_set", "lio_pose_estimator_matrix",
@@ -101,6 +104,14 @@ class GroundParams(C.Structure):  # lio_ground_params
     _fields_ = [("sensor_height", C.c_double), ("clip_low", C.c_double), ("clip_high", C.c_double), ("use_normal_filter", C.c_int32),
                 ("normal_thresh_deg", C.c_double), ("k", C.c_int32), ("distance_threshold", C.c_double), ("min_points", C.c_int32),
                 ("floor_normal_thresh_deg", C.c_double), ("max_iterations", C.c_int32), ("probability", C.c_double), ("seed", C.c_uint32)]
+
+
+class BevInfo(C.Structure):  # lio_bev_info
+    _fields_ = [("n_in", C.c_uint32), ("n_dropped", C.c_uint32), ("n_kept", C.c_uint32), ("rank_lo", C.c_uint32), ("rank_hi", C.c_uint32),
+                ("n_pixels", C.c_uint32), ("image_w", C.c_uint32), ("image_h", C.c_uint32), ("padded_w", C.c_uint32), ("padded_h", C.c_uint32),
+                ("patch", C.c_int32), ("half_patch", C.c_int32), ("quarter_patch", C.c_int32), ("nodes_x", C.c_uint32), ("nodes_y", C.c_uint32),
+                ("reserved", C.c_uint32), ("pixel_per_meter", C.c_double), ("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double),
+                ("y_max", C.c_double)]
 
 
 class AlignJob(C.Structure):  # lio_align_job
@@ -265,6 +276,22 @@ def lib():
     sig("lio_ground_download_draws", C.c_int64, vp, u32p, u32p, f32p, u64)
     sig("lio_ground_last_run", cint, vp, C.POINTER(cint), C.POINTER(cint), C.POINTER(cint), C.POINTER(cint))
     sig("lio_ground_last_times", cint, vp, f64p, f64p)
+    u16p = C.POINTER(C.c_uint16)
+    sig("lio_bev_create", vp, cint)
+    sig("lio_bev_destroy", None, vp)
+    sig("lio_bev_preprocess_host", cint, vp, f32p, u64, dbl)
+    sig("lio_bev_preprocess_cloud", cint, vp, vp, dbl)
+    sig("lio_bev_upload_pixels", cint, vp, u32p, f32p, f32p, u64, u32, u32)
+    sig("lio_bev_convert", cint, vp, dbl, dbl)
+    sig("lio_bev_get_info", cint, vp, C.POINTER(BevInfo))
+    sig("lio_bev_download_pixel_coords", C.c_int64, vp, i32p, u64)
+    sig("lio_bev_download_kept", C.c_int64, vp, u32p, u64)
+    sig("lio_bev_download_pixels", C.c_int64, vp, u32p, f32p, f32p, u64)
+    sig("lio_bev_download_nodes", C.c_int64, vp, u32p, i32p, f64p, u64)
+    sig("lio_bev_download_equalised", C.c_int64, vp, f32p, u64)
+    sig("lio_bev_download_image", C.c_int64, vp, u16p, u64)
+    sig("lio_bev_grey_table", None, u16p)
+    sig("lio_bev_last_times", cint, vp, f64p, f64p)
     sig("lio_pose_estimator_create", vp, f32p, u64, f32p, f32p, dbl)
     sig("lio_pose_estimator_destroy", None, vp)
     sig("lio_pose_estimator_predict", cint, vp, u64, f32p, f32p)

@@ -866,6 +866,117 @@ class GroundDetector:
         return a.value, b.value
 
 
+class BevImage:
+    """lio_bev: the bird's-eye intensity image of tools/postprocessing/convert_cloud_image.py on the device (include/lio_hip.h states every
+    rule): noise filter by intensity rank, per-pixel means, patch-wise histogram equalisation, 16-bit grey image.  An invalid argument (no
+    finite point, a patch below 2 pixels, ...) raises ValueError; device trouble raises LioError."""
+
+    def __init__(self, device=0):
+        self.h = lib().lio_bev_create(device)
+        if not self.h:
+            raise capi.LioError("lio_bev_create failed: " + lib().lio_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_bev_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _check(rc, what):
+        if rc == capi.LIO_E_INVALID:
+            raise ValueError(f"{what}: {lib().lio_last_error().decode()}")
+        return check(rc, what)
+
+    def preprocess_host(self, xyzi, pixel_per_meter):
+        p = f32(xyzi).reshape(-1, 4)
+        self._check(lib().lio_bev_preprocess_host(self.h, ptr(p, C.c_float), len(p), float(pixel_per_meter)), "bev preprocess_host")
+        return self.info()
+
+    def preprocess_cloud(self, cloud, pixel_per_meter):
+        self._check(lib().lio_bev_preprocess_cloud(self.h, cloud.h, float(pixel_per_meter)), "bev preprocess_cloud")
+        return self.info()
+
+    def upload_pixels(self, keys, intensity, z, image_w, image_h):
+        k = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+        i = f32(intensity).reshape(-1)
+        zz = None if z is None else f32(z).reshape(-1)
+        if len(i) != len(k) or (zz is not None and len(zz) != len(k)):
+            raise ValueError("BevImage.upload_pixels: one intensity (and z) per key")
+        self._check(lib().lio_bev_upload_pixels(self.h, ptr(k, C.c_uint32), ptr(i, C.c_float), None if zz is None else ptr(zz, C.c_float), len(k),
+                                                int(image_w), int(image_h)), "bev upload_pixels")
+
+    def convert(self, window, pixel_per_meter):
+        self._check(lib().lio_bev_convert(self.h, float(window), float(pixel_per_meter)), "bev convert")
+        return self.image()
+
+    def info(self):
+        i = capi.BevInfo()
+        check(lib().lio_bev_get_info(self.h, C.byref(i)), "bev info")
+        return {k: getattr(i, k) for k, _ in capi.BevInfo._fields_ if k != "reserved"}
+
+    def pixel_coords(self):
+        """n x 2 int32 (xs, ys) per input point; (-1, -1) for a point dropped as not finite"""
+        n = max(-lib().lio_bev_download_pixel_coords(self.h, None, 0), 0)
+        out = np.zeros((n, 2), np.int32)
+        if n:
+            check(int(lib().lio_bev_download_pixel_coords(self.h, ptr(out, C.c_int32), n)), "bev pixel_coords")
+        return out
+
+    def kept(self):
+        """input indices of the points the noise filter kept, in ascending (intensity, index) order"""
+        n = max(-lib().lio_bev_download_kept(self.h, None, 0), 0)
+        out = np.zeros(n, np.uint32)
+        if n:
+            check(int(lib().lio_bev_download_kept(self.h, ptr(out, C.c_uint32), n)), "bev kept")
+        return out
+
+    def pixels(self):
+        """(key u32, mean intensity f32, mean z f32) per occupied pixel, keys ascending"""
+        n = max(-lib().lio_bev_download_pixels(self.h, None, None, None, 0), 0)
+        k, i, z = np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        if n:
+            check(int(lib().lio_bev_download_pixels(self.h, ptr(k, C.c_uint32), ptr(i, C.c_float), ptr(z, C.c_float), n)), "bev pixels")
+        return k, i, z
+
+    def nodes(self):
+        """(count u32, step i32 (-1: the node did not run), clip limit f64) per node, xi major"""
+        n = max(-lib().lio_bev_download_nodes(self.h, None, None, None, 0), 0)
+        c, s, cl = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        if n:
+            check(int(lib().lio_bev_download_nodes(self.h, ptr(c, C.c_uint32), ptr(s, C.c_int32), ptr(cl, C.c_double), n)), "bev nodes")
+        return c, s, cl
+
+    def equalised(self):
+        """the f32 value of every occupied pixel before rint"""
+        n = max(-lib().lio_bev_download_equalised(self.h, None, 0), 0)
+        out = np.zeros(n, np.float32)
+        if n:
+            check(int(lib().lio_bev_download_equalised(self.h, ptr(out, C.c_float), n)), "bev equalised")
+        return out
+
+    def image(self):
+        i = self.info()
+        out = np.zeros((i["padded_h"], i["padded_w"]), np.uint16)
+        n = lib().lio_bev_download_image(self.h, ptr(out, C.c_uint16), out.size)
+        check(int(n) if n >= 0 else capi.LIO_E_CAPACITY, "bev image")
+        return out
+
+    def last_times(self):
+        """(preprocess_us, convert_us): device time of the last preprocess and of the last convert"""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib().lio_bev_last_times(self.h, C.byref(a), C.byref(b)), "bev times")
+        return a.value, b.value
+
+
+def bev_grey_table():
+    """the 65536-entry grey table of the image (host only)"""
+    out = np.zeros(65536, np.uint16)
+    lib().lio_bev_grey_table(ptr(out, C.c_uint16))
+    return out
+
+
 def _mix32(x):
     x = np.asarray(x, np.uint64) & np.uint64(0xFFFFFFFF)
     x = x ^ (x >> np.uint64(16))
