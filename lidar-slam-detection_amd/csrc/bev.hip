@@ -4,9 +4,9 @@
 //
 //   bounds     finite flags, f32 min / max of x and y as ordered words (integer atomics: any order gives the same bits); the host derives the
 //              image size in f64
-//   noise      stable LSD radix sort (cloud_sort.h, 4 passes) of (canonical intensity, input index); ranks [int(m 0.01), int(m 0.999)) stay
+//   noise      stable LSD radix sort (device_prims.h, 4 passes) of (canonical intensity, input index); ranks [int(m 0.01), int(m 0.999)) stay
 //   scatter    pixel key ys w + xs of the kept points in that order, a second stable sort by the key (only the passes the key has bits for),
-//              run heads by tile counts -> device-wide scan -> compaction, then the sequential f32 sums of intensity and z per pixel in
+//              run heads by device_prims.h's stable compaction, then the sequential f32 sums of intensity and z per pixel in
 //              ascending (intensity, input index) order: one lane per pixel, one wave for a pixel of 64 points or more
 //   rows       for every image row and node column the range of the occupied-pixel list that lies in the column's window (binary searches)
 //   nodes      one workgroup per equalisation node: occupied pixels of its window from the row ranges, 1024-bin histogram in LDS (integer
@@ -21,16 +21,13 @@
 #include <cmath>
 #include <vector>
 
-#include "cloud_sort.h"
-#include "lio_common.h"
+#include "device_prims.h"
 
 namespace lio {
 namespace bev {
 
-constexpr int kThreads = 256;
-constexpr int kItems = 8;
-constexpr uint32_t kTile = kThreads * kItems;
-constexpr int kWaves = kThreads / 64;
+using namespace prims;
+
 constexpr int kBins = 1024;
 constexpr int kMaxSteps = 1280;     // (120 - 1) / 0.1 = 1190 steps at the most, with room for the drift of the f32 accumulation
 constexpr uint32_t kLongRun = 64;   // pixels of at least this many points are summed one wave per pixel
@@ -38,21 +35,6 @@ constexpr uint32_t kLongBlocks = 2048;
 constexpr double kBright = 20480.0; // BRIGHTNESS = 80 * 256
 constexpr double kTermMax = 8388608.0;  // 2^23 > 65535 * 120: the clamp of a fixed-point term
 constexpr uint32_t kMinCount = 100;
-
-inline uint32_t tiles_of(uint64_t n) { return (uint32_t)((n + kTile - 1) / kTile); }
-inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kThreads - 1) / kThreads); }
-inline uint64_t round_words(uint64_t w) { return (w + 63) & ~63ull; }
-
-__device__ inline uint32_t f2ord(float f) {
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float ord2f_host(uint32_t u) {
-    const uint32_t b = (u & 0x80000000u) ? (u ^ 0x80000000u) : ~u;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
-}
 
 struct Bounds {  // ordered words of the f32 extremes over the finite points
     uint32_t xmin, xmax, ymin, ymax, n_finite, bad;
@@ -65,7 +47,7 @@ struct Geo {  // the image and the node grid
     uint32_t nx, ny;    // nodes
 };
 
-__device__ __forceinline__ bool finite_pt(const float4& p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.w); }
+__device__ __forceinline__ bool finite_pt(const float4& p) { return finite3(p.x, p.y, p.w); }  // (z may be anything)
 
 __global__ __launch_bounds__(kThreads) void bv_bounds(const float4* __restrict__ p, uint32_t n, Bounds* __restrict__ b) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -128,7 +110,6 @@ __global__ __launch_bounds__(kThreads) void bv_pixel_keys(const uint32_t* __rest
 
 // run heads per tile
 __global__ __launch_bounds__(kThreads) void bv_head_count(const uint32_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t wc[kWaves];
     const uint32_t base = blockIdx.x * kTile;
     uint32_t c = 0;
 #pragma unroll
@@ -136,47 +117,26 @@ __global__ __launch_bounds__(kThreads) void bv_head_count(const uint32_t* __rest
         const uint32_t i = base + r * kThreads + threadIdx.x;
         c += (i < n && (i == 0 || keys[i - 1] != keys[i])) ? 1u : 0u;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off);
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+    compact_tile_count(c, counts);
 }
 
 // hpos[v] = first sorted position of occupied pixel v, hpos[npix] = n; pkey[v] = its key
 __global__ __launch_bounds__(kThreads) void bv_head_write(const uint32_t* __restrict__ keys, uint32_t n, const uint32_t* __restrict__ offs, uint32_t ntiles,
                                                           uint32_t* __restrict__ hpos, uint32_t* __restrict__ pkey) {
-    __shared__ uint32_t wcnt[kItems][kWaves];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const uint32_t base = blockIdx.x * kTile;
-    unsigned long long hm[kItems];
+    bool head[kItems];
     uint32_t kc[kItems];
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
         const uint32_t i = base + r * kThreads + tid;
         kc[r] = i < n ? keys[i] : 0u;
-        hm[r] = __ballot(i < n && (i == 0 || keys[i - 1] != kc[r]));
-        if (lane == 0) wcnt[r][wave] = (uint32_t)__popcll(hm[r]);
+        head[r] = i < n && (i == 0 || keys[i - 1] != kc[r]);
     }
-    __syncthreads();
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t run = offs[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < kItems; r++) {
-        uint32_t woff = 0, rtot = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) {
-            const uint32_t t = wcnt[r][w];
-            woff += (w < wave) ? t : 0u;
-            rtot += t;
-        }
-        if ((hm[r] >> lane) & 1ull) {
-            const uint32_t o = run + woff + (uint32_t)__popcll(hm[r] & lt);
-            hpos[o] = base + r * kThreads + tid;
-            pkey[o] = kc[r];
-        }
-        run += rtot;
-    }
+    compact_tile_write(head, offs, [&](int r, uint32_t o) {
+        hpos[o] = base + r * kThreads + tid;
+        pkey[o] = kc[r];
+    });
     if (blockIdx.x == 0 && tid == 0) hpos[offs[ntiles]] = n;
 }
 
@@ -189,15 +149,7 @@ __global__ __launch_bounds__(kThreads) void bv_mean(const float4* __restrict__ p
     const bool live = v < npix;
     const uint32_t a = hpos[live ? v : 0u], b = hpos[live ? v + 1u : 0u];
     const bool is_long = live && b - a >= kLongRun;
-    const unsigned long long lm = __ballot(is_long);
-    if (lm) {
-        const int lane = threadIdx.x & 63;
-        const int leader = __ffsll((long long)lm) - 1;
-        uint32_t qb = 0;
-        if (lane == leader) qb = atomicAdd(n_long, (uint32_t)__popcll(lm));
-        qb = __shfl(qb, leader);
-        if (is_long) longlist[qb + __popcll(lm & ((1ull << lane) - 1ull))] = v;
-    }
+    queue_long_run(is_long, v, longlist, n_long);
     if (!live || is_long) return;
     float si = 0.f, sz = 0.f;
     for (uint32_t j = a; j < b; j += 4) {
@@ -505,11 +457,6 @@ struct lio_bev {
 
 namespace {
 
-template <typename T>
-bool alloc(T** p, uint64_t count) {
-    return hipMalloc(p, std::max<uint64_t>(count, 1) * sizeof(T)) == hipSuccess;
-}
-
 void free_points(lio_bev* b) {
     void* all[] = {b->stage, b->ka, b->kb, b->va, b->vb, b->kept, b->hpos, b->pkey, b->longlist, b->xy, b->pI, b->pz, b->eq, b->radix, b->heads};
     for (void* p : all)
@@ -521,8 +468,6 @@ void free_points(lio_bev* b) {
     b->cap = 0;
 }
 
-uint64_t heads_words(uint64_t ntiles) { return round_words(ntiles + 1) + round_words(cloud::scan_aux_words(ntiles + 1) + 64); }
-
 int reserve(lio_bev* b, uint64_t n) {
     if (n <= b->cap) return LIO_OK;
     if (n > 0x7FFFFFFFull) { set_error("lio_bev: %llu points exceed the int index range (2^31 - 1)", (unsigned long long)n); return LIO_E_CAPACITY; }
@@ -532,7 +477,7 @@ int reserve(lio_bev* b, uint64_t n) {
     const bool ok = alloc(&b->stage, want) && alloc(&b->ka, want) && alloc(&b->kb, want) && alloc(&b->va, want) && alloc(&b->vb, want) &&
                     alloc(&b->kept, want) && alloc(&b->hpos, want + 1) && alloc(&b->pkey, want) && alloc(&b->longlist, want) && alloc(&b->xy, want) &&
                     alloc(&b->pI, want) && alloc(&b->pz, want) && alloc(&b->eq, want) && alloc(&b->radix, cloud::radix_scratch_words(want)) &&
-                    alloc(&b->heads, heads_words(tiles_of(want)));
+                    alloc(&b->heads, compact_words(want));
     if (!ok) {
         (void)hipGetLastError();
         free_points(b);
@@ -541,27 +486,6 @@ int reserve(lio_bev* b, uint64_t n) {
     }
     b->cap = want;
     return LIO_OK;
-}
-
-template <typename T>
-int grow(T** buf, uint64_t* cap, uint64_t need, hipStream_t st) {
-    if (need <= *cap && *buf) return LIO_OK;
-    LIO_HIP_TRY(hipStreamSynchronize(st));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    if (!alloc(buf, need)) {
-        (void)hipGetLastError();
-        set_error("lio_bev: %llu bytes of device memory not available", (unsigned long long)(need * sizeof(T)));
-        return LIO_E_DEVICE;
-    }
-    *cap = need;
-    return LIO_OK;
-}
-
-float elapsed_us(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f;
 }
 
 // the sizes load_pointcloud derives, and the limits of the 32-bit pixel key
@@ -598,7 +522,7 @@ int preprocess(lio_bev* b, const float4* raw, uint32_t n, double ppm) {
     const uint32_t m = hb.n_finite;
     b->info.n_dropped = n - m;
     if (m == 0) { set_error("lio_bev: no point with finite x, y and intensity among %u", n); return LIO_E_INVALID; }
-    const float xmin = ord2f_host(hb.xmin), xmax = ord2f_host(hb.xmax), ymin = ord2f_host(hb.ymin), ymax = ord2f_host(hb.ymax);
+    const float xmin = ord2f(hb.xmin), xmax = ord2f(hb.xmax), ymin = ord2f(hb.ymin), ymax = ord2f(hb.ymax);
     b->info.x_min = xmin; b->info.x_max = xmax; b->info.y_min = ymin; b->info.y_max = ymax;
     uint32_t w = 0, h = 0;
     int rc = image_size(xmin, xmax, ppm, &w);
@@ -638,16 +562,15 @@ int preprocess(lio_bev* b, const float4* raw, uint32_t n, double ppm) {
         }
         const uint32_t ntiles = tiles_of(nk);
         uint32_t* counts = b->heads;
-        LIO_HIP_TRY(hipMemsetAsync(counts + ntiles, 0, sizeof(uint32_t), st));
         LIO_HIP_TRY(hipMemsetAsync(b->d_word, 0, sizeof(uint32_t), st));
         bv_head_count<<<dim3(ntiles), dim3(kThreads), 0, st>>>(ki, nk, counts);
-        rc = cloud::exclusive_scan(st, counts, ntiles + 1ull, counts + round_words(ntiles + 1));
-        if (rc != LIO_OK) return rc;
+        const uint32_t* d_npix = compact_finish(st, counts, nk);
+        if (!d_npix) return LIO_E_DEVICE;
         bv_head_write<<<dim3(ntiles), dim3(kThreads), 0, st>>>(ki, nk, counts, ntiles, b->hpos, b->pkey);
-        bv_mean<<<dim3(blocks_of(nk)), dim3(kThreads), 0, st>>>(raw, vi, b->hpos, counts + ntiles, b->pI, b->pz, b->longlist, b->d_word);
+        bv_mean<<<dim3(blocks_of(nk)), dim3(kThreads), 0, st>>>(raw, vi, b->hpos, d_npix, b->pI, b->pz, b->longlist, b->d_word);
         bv_mean_long<<<dim3(kLongBlocks), dim3(64), 0, st>>>(raw, vi, b->hpos, b->longlist, b->d_word, b->pI, b->pz);
         LIO_HIP_TRY(hipGetLastError());
-        LIO_HIP_TRY(hipMemcpyAsync(&npix, counts + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        LIO_HIP_TRY(hipMemcpyAsync(&npix, d_npix, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     LIO_HIP_TRY(hipMemcpyAsync(&hb, b->d_bounds, sizeof(hb), hipMemcpyDeviceToHost, st));
     LIO_HIP_TRY(hipEventRecord(b->ev[1], st));
@@ -661,15 +584,7 @@ int preprocess(lio_bev* b, const float4* raw, uint32_t n, double ppm) {
 
 template <typename T>
 int64_t download(lio_bev* b, const T* src, uint64_t n, T* out, uint64_t cap) {
-    if (n > cap) return -(int64_t)n;
-    if (n == 0) return 0;
-    if (!out) return LIO_E_INVALID;
-    hipSetDevice(b->device);
-    if (hipMemcpyAsync(out, src, n * sizeof(T), hipMemcpyDeviceToHost, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) {
-        set_error("lio_bev: download failed");
-        return LIO_E_DEVICE;
-    }
-    return (int64_t)n;
+    return prims::download("lio_bev", b->device, b->stream, src, n, out, cap);
 }
 
 }  // namespace
@@ -686,19 +601,14 @@ void lio_bev_grey_table(uint16_t out[65536]) {
 }
 
 lio_bev* lio_bev_create(int device) {
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) {
-        (void)hipGetLastError();
-        set_error("lio_bev_create: no HIP device %d (there is no CPU fallback)", device);
-        return nullptr;
-    }
-    if (hipSetDevice(device) != hipSuccess) { set_error("lio_bev_create: hipSetDevice(%d) failed", device); return nullptr; }
     lio_bev* b = new lio_bev();
     memset(b, 0, sizeof(*b));
     b->device = device;
-    bool ok = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 5 && ok; i++) ok = hipEventCreate(&b->ev[i]) == hipSuccess;
-    ok = ok && alloc(&b->d_bounds, 1) && alloc(&b->d_word, 16) && alloc(&b->d_grey, 65536);
+    if (!open_device("lio_bev_create", device, &b->stream, b->ev, 5)) {
+        delete b;
+        return nullptr;
+    }
+    bool ok = alloc(&b->d_bounds, 1) && alloc(&b->d_word, 16) && alloc(&b->d_grey, 65536);
     if (ok) {
         std::vector<uint16_t> g(65536);
         lio_bev_grey_table(g.data());
@@ -805,13 +715,13 @@ int lio_bev_convert(lio_bev* b, double window, double pixel_per_meter) {
     b->info.padded_w = g.W; b->info.padded_h = g.H;
     b->info.patch = g.P; b->info.half_patch = g.hp; b->info.quarter_patch = g.q;
     b->info.nodes_x = g.nx; b->info.nodes_y = g.ny;
-    int rc = grow(&b->rows, &b->rows_cap, (uint64_t)g.h * g.nx * 2, st);
-    if (rc == LIO_OK) rc = grow(&b->ncount, &b->ncap[0], nodes, st);
-    if (rc == LIO_OK) rc = grow(&b->nstep, &b->ncap[1], nodes, st);
-    if (rc == LIO_OK) rc = grow(&b->nclip, &b->ncap[2], nodes, st);
-    if (rc == LIO_OK) rc = grow(&b->ncdf, &b->ncap[3], nodes * kBins, st);
-    if (rc == LIO_OK) rc = grow(&b->nslope, &b->ncap[4], nodes * kBins, st);
-    if (rc == LIO_OK) rc = grow(&b->image, &b->image_cap, W * H, st);
+    int rc = grow("lio_bev", &b->rows, &b->rows_cap, (uint64_t)g.h * g.nx * 2, st);
+    if (rc == LIO_OK) rc = grow("lio_bev", &b->ncount, &b->ncap[0], nodes, st);
+    if (rc == LIO_OK) rc = grow("lio_bev", &b->nstep, &b->ncap[1], nodes, st);
+    if (rc == LIO_OK) rc = grow("lio_bev", &b->nclip, &b->ncap[2], nodes, st);
+    if (rc == LIO_OK) rc = grow("lio_bev", &b->ncdf, &b->ncap[3], nodes * kBins, st);
+    if (rc == LIO_OK) rc = grow("lio_bev", &b->nslope, &b->ncap[4], nodes * kBins, st);
+    if (rc == LIO_OK) rc = grow("lio_bev", &b->image, &b->image_cap, W * H, st);
     if (rc != LIO_OK) return rc;
     LIO_HIP_TRY(hipEventRecord(b->ev[2], st));
     LIO_HIP_TRY(hipMemsetAsync(b->image, 0, W * H * sizeof(uint16_t), st));

@@ -5,7 +5,7 @@
 // the cloud of a whole drive (10^7 - 10^8 points) goes through one VoxelGrid.  The per-scan chain of voxelgrid.hip is sized for <= 10^6 points
 // (its scatter workgroups fold every tile's histogram row: O(tiles^2) reads); this file is the device-wide form:
 //
-//   append     xform + band -> [tile counts -> device-wide exclusive scan -> stable write]   (no band: one launch, in order)
+//   append     xform + band -> device_prims.h's stable compaction [tile counts -> device-wide scan -> write]   (no band: one launch, in order)
 //   bbox       per-workgroup records (grid-stride) -> one workgroup folds them and derives the grid (PCL's int32 guard included)
 //   keys       voxel index per point + the histogram of its lowest digit, [digit][tile]
 //   4 x        {tile histogram -> device-wide exclusive scan of the [digit][tile] table -> stable scatter}  (passes above the key's bits: skipped)
@@ -20,25 +20,16 @@
 // transform: per point in f64, terms left to right, no contraction (-ffp-contract=off), cast to f32; non-finite points are transformed too.
 #include <algorithm>
 
-#include "cloud_sort.h"
-#include "lio_common.h"
+#include "device_prims.h"
 
 namespace lio {
 namespace cloud {
 
-constexpr int kThreads = 256;
-constexpr int kItems = 8;
-constexpr uint32_t kTile = kThreads * kItems;  // 2048 elements per workgroup: points, keys or scan entries
-constexpr int kWaves = kThreads / 64;
+using namespace prims;
+
 constexpr uint32_t kBboxBlocks = 1024;         // workgroups of the bbox's first level (grid-stride): the fold reads 1024 records
 constexpr uint32_t kLongRun = 32;              // runs of at least this many points are summed one wave per run
 constexpr uint32_t kLongBlocks = 4096;         // one-wave workgroups of the long-run kernel (grid-stride over the queue)
-
-__device__ inline uint32_t f2ord(float f) {
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u); }
 
 // exclusive prefix of v over the 256 threads of a workgroup (fixed order); *total = the sum.  Uses `ws` (kWaves words of LDS).
 __device__ inline uint32_t block_exclusive(uint32_t v, uint32_t* ws, uint32_t* total) {
@@ -114,9 +105,6 @@ __global__ __launch_bounds__(kThreads) void cl_scan_apply(uint32_t* __restrict__
     }
 }
 
-inline uint64_t tiles_of(uint64_t m) { return (m + kTile - 1) / kTile; }
-inline uint64_t round_words(uint64_t w) { return (w + 63) & ~63ull; }  // 256-byte steps: every carved sub-buffer stays 16-byte aligned
-
 // words of scratch the scan of m entries needs for its tile sums (all levels)
 uint64_t scan_aux_words(uint64_t m) {
     uint64_t w = 0;
@@ -158,7 +146,6 @@ __device__ __forceinline__ bool keep(const float4& o, const XformArgs& a) { retu
 
 // kept points per tile (band only)
 __global__ __launch_bounds__(kThreads) void cl_append_count(const float4* __restrict__ in, uint32_t n, XformArgs a, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t ws[kWaves];
     const uint32_t base = blockIdx.x * kTile;
     float4 p[kItems];
 #pragma unroll
@@ -172,17 +159,14 @@ __global__ __launch_bounds__(kThreads) void cl_append_count(const float4* __rest
         const uint32_t i = base + r * kThreads + threadIdx.x;
         c += (i < n && keep(xform(p[r], a), a)) ? 1u : 0u;
     }
-    uint32_t tot;
-    (void)block_exclusive(c, ws, &tot);
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+    compact_tile_count(c, counts);
 }
 
-// the write: without a band every point lands at its own index; with one, item r of lane l of wave w goes to
-// tile prefix + (kept items of rounds < r) + (kept of waves < w in round r) + (kept lanes < l): input order
+// the write: without a band every point lands at its own index; with one, the kept points in input order
 __global__ __launch_bounds__(kThreads) void cl_append_write(const float4* __restrict__ in, uint32_t n, XformArgs a, const uint32_t* __restrict__ offs,
                                                             float4* __restrict__ out) {
     const uint32_t base = blockIdx.x * kTile;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     float4 p[kItems];
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
@@ -197,30 +181,14 @@ __global__ __launch_bounds__(kThreads) void cl_append_write(const float4* __rest
         }
         return;
     }
-    __shared__ uint32_t wcnt[kItems][kWaves];
-    unsigned long long km[kItems];
+    bool kept[kItems];
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
         const uint32_t i = base + r * kThreads + tid;
         p[r] = xform(p[r], a);
-        km[r] = __ballot(i < n && keep(p[r], a));
-        if (lane == 0) wcnt[r][wave] = (uint32_t)__popcll(km[r]);
+        kept[r] = i < n && keep(p[r], a);
     }
-    __syncthreads();
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t run = offs[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < kItems; r++) {
-        uint32_t woff = 0, rtot = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) {
-            const uint32_t t = wcnt[r][w];
-            woff += (w < wave) ? t : 0u;
-            rtot += t;
-        }
-        if ((km[r] >> lane) & 1ull) out[run + woff + (uint32_t)__popcll(km[r] & lt)] = p[r];
-        run += rtot;
-    }
+    compact_tile_write(kept, offs, [&](int r, uint32_t o) { out[o] = p[r]; });
 }
 
 // ---- voxel grid ------------------------------------------------------------------------------------------------------------------------------
@@ -401,17 +369,6 @@ __global__ __launch_bounds__(kThreads) void cl_hist(const uint32_t* __restrict__
     table[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
 }
 
-__device__ inline unsigned long long match_digit(uint32_t d, bool valid) {
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long m = __ballot(bit);
-        peers &= bit ? m : ~m;
-    }
-    return peers;
-}
-
 // stable scatter of one 8-bit digit: the scanned table gives every (digit, tile) its global base; inside the tile each wave owns a contiguous
 // run of 512 keys, so (wave, round, lane) order is input order, and the ranks come from eight ballots per item (the scheme of voxelgrid.hip)
 __global__ __launch_bounds__(kThreads) void cl_scatter(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, uint32_t* __restrict__ kout,
@@ -491,7 +448,6 @@ int radix_pass(hipStream_t st, const uint32_t* kin, const uint32_t* vin, uint32_
 
 // run heads (first sorted position of every occupied voxel) per tile
 __global__ __launch_bounds__(kThreads) void cl_head_count(const uint32_t* __restrict__ keys, uint32_t n, uint32_t total, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t ws[kWaves];
     const uint32_t base = blockIdx.x * kTile;
     uint32_t kc[kItems], kp[kItems];
 #pragma unroll
@@ -507,9 +463,7 @@ __global__ __launch_bounds__(kThreads) void cl_head_count(const uint32_t* __rest
         const uint32_t i = base + r * kThreads + threadIdx.x;
         c += (i < n && kc[r] < total && (i == 0 || kp[r] != kc[r])) ? 1u : 0u;
     }
-    uint32_t tot;
-    (void)block_exclusive(c, ws, &tot);
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+    compact_tile_count(c, counts);
 }
 
 // compaction of the heads in sorted order (hpos[v] = first sorted position of voxel v, hpos[n_vox] = n_valid: the non-finite points sort behind
@@ -517,7 +471,7 @@ __global__ __launch_bounds__(kThreads) void cl_head_count(const uint32_t* __rest
 __global__ __launch_bounds__(kThreads) void cl_head_write(const float4* __restrict__ in, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                           uint32_t n, uint32_t n_valid, uint32_t total, const uint32_t* __restrict__ offs, uint32_t ntiles,
                                                           uint32_t* __restrict__ hpos, float4* __restrict__ sorted) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const uint32_t base = blockIdx.x * kTile;
     uint32_t kc[kItems], kp[kItems], vv[kItems];
 #pragma unroll
@@ -528,29 +482,13 @@ __global__ __launch_bounds__(kThreads) void cl_head_write(const float4* __restri
         kp[r] = keys[ic ? ic - 1u : 0u];
         vv[r] = vals[ic];
     }
-    __shared__ uint32_t wcnt[kItems][kWaves];
-    unsigned long long hm[kItems];
+    bool head[kItems];
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
         const uint32_t i = base + r * kThreads + tid;
-        hm[r] = __ballot(i < n && kc[r] < total && (i == 0 || kp[r] != kc[r]));
-        if (lane == 0) wcnt[r][wave] = (uint32_t)__popcll(hm[r]);
+        head[r] = i < n && kc[r] < total && (i == 0 || kp[r] != kc[r]);
     }
-    __syncthreads();
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t run = offs[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < kItems; r++) {
-        uint32_t woff = 0, rtot = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) {
-            const uint32_t t = wcnt[r][w];
-            woff += (w < wave) ? t : 0u;
-            rtot += t;
-        }
-        if ((hm[r] >> lane) & 1ull) hpos[run + woff + (uint32_t)__popcll(hm[r] & lt)] = base + r * kThreads + tid;
-        run += rtot;
-    }
+    compact_tile_write(head, offs, [&](int r, uint32_t o) { hpos[o] = base + r * kThreads + tid; });
     if (blockIdx.x == 0 && tid == 0) hpos[offs[ntiles]] = n_valid;
 #pragma unroll
     for (int r0 = 0; r0 < kItems; r0 += 4) {
@@ -573,15 +511,7 @@ __global__ __launch_bounds__(kThreads) void cl_centroid(const float4* __restrict
     const bool live = v < nvox;
     const uint32_t a = hpos[live ? v : 0u], b = hpos[live ? v + 1u : 0u];
     const bool is_long = live && b - a >= kLongRun;
-    const unsigned long long lm = __ballot(is_long);
-    if (lm) {
-        const int lane = threadIdx.x & 63;
-        const int leader = __ffsll((long long)lm) - 1;
-        uint32_t qb = 0;
-        if (lane == leader) qb = atomicAdd(&g->n_long, (uint32_t)__popcll(lm));
-        qb = __shfl(qb, leader);
-        if (is_long) longlist[qb + __popcll(lm & ((1ull << lane) - 1ull))] = v;
-    }
+    queue_long_run(is_long, v, longlist, &g->n_long);
     if (!live || is_long) return;
     float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
     {
@@ -679,7 +609,7 @@ struct VgLayout {
 };
 VgLayout vg_layout(uint64_t n) {
     const uint64_t ntiles = tiles_of(n);
-    const uint64_t tab = 256ull * ntiles + 1;  // [digit][tile] (+1: the scanned total); also the head counts (ntiles + 1 <= tab)
+    const uint64_t tab = 256ull * ntiles + 1;  // [digit][tile] (+1: the scanned total)
     VgLayout L;
     uint64_t w = 0;
     L.keys_a = w; w += round_words(n + 1);     // n + 1: the other key buffer holds hpos (n_vox + 1 <= n + 1 words)
@@ -687,7 +617,7 @@ VgLayout vg_layout(uint64_t n) {
     L.vals_a = w; w += round_words(n);         // the other value buffer holds the long-run queue
     L.vals_b = w; w += round_words(n);
     L.sorted = w; w += round_words(4 * n);
-    L.table = w; w += round_words(tab);
+    L.table = w; w += std::max(round_words(tab), compact_words(n));  // also the heads' compaction scratch
     L.aux = w; w += round_words(scan_aux_words(tab) + 64);
     L.parts = w; w += round_words(8ull * kBboxBlocks);
     L.grid = w; w += round_words(sizeof(Grid) / 4);
@@ -723,21 +653,6 @@ int cloud_reserve(lio_cloud* c, uint64_t need) {
     return LIO_OK;
 }
 
-template <typename T>
-int grow_buffer(T** buf, uint64_t* cap, uint64_t need) {
-    if (need <= *cap) return LIO_OK;
-    T* p = nullptr;
-    if (hipMalloc(&p, need * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("lio_cloud: %llu bytes of device scratch not available", (unsigned long long)(need * sizeof(T)));
-        return LIO_E_DEVICE;
-    }
-    if (*buf) (void)hipFree(*buf);
-    *buf = p;
-    *cap = need;
-    return LIO_OK;
-}
-
 XformArgs make_xform(const double T[16], float scale, int z_band, double z_min, double z_max) {
     XformArgs a;
     for (int i = 0; i < 12; i++) a.m[i] = T ? T[i] : ((i % 5 == 0) ? 1.0 : 0.0);
@@ -756,17 +671,15 @@ int cloud_append(lio_cloud* c, const float4* in, uint64_t n, const XformArgs& a)
     hipEventRecord(c->ev[0], c->stream);
     uint64_t kept = n;
     if (a.band) {
-        const uint64_t words = round_words(ntiles + 1) + scan_aux_words(ntiles + 1) + 64;
-        int rc = grow_buffer(&c->aux, &c->aux_cap, words);
+        const int rc = grow("lio_cloud", &c->aux, &c->aux_cap, compact_words(n), c->stream);
         if (rc != LIO_OK) return rc;
-        LIO_HIP_TRY(hipMemsetAsync(c->aux + ntiles, 0, sizeof(uint32_t), c->stream));
         cl_append_count<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(in, nn, a, c->aux);
-        rc = exclusive_scan(c->stream, c->aux, ntiles + 1, c->aux + round_words(ntiles + 1));
-        if (rc != LIO_OK) return rc;
+        const uint32_t* d_kept = compact_finish(c->stream, c->aux, n);
+        if (!d_kept) return LIO_E_DEVICE;
         cl_append_write<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(in, nn, a, c->aux, c->pts + c->n);
         LIO_HIP_TRY(hipGetLastError());
         uint32_t k = 0;
-        LIO_HIP_TRY(hipMemcpyAsync(&k, c->aux + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        LIO_HIP_TRY(hipMemcpyAsync(&k, d_kept, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         hipEventRecord(c->ev[1], c->stream);
         LIO_HIP_TRY(hipStreamSynchronize(c->stream));
         kept = k;
@@ -776,8 +689,7 @@ int cloud_append(lio_cloud* c, const float4* in, uint64_t n, const XformArgs& a)
         hipEventRecord(c->ev[1], c->stream);
         LIO_HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->append_us = (double)ms * 1000.0;
+    c->append_us = elapsed_us(c->ev[0], c->ev[1]);
     c->n += kept;
     return LIO_OK;
 }
@@ -787,20 +699,14 @@ int cloud_append(lio_cloud* c, const float4* in, uint64_t n, const XformArgs& a)
 extern "C" {
 
 lio_cloud* lio_cloud_create(int device, uint64_t reserve_points) {
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) {
-        (void)hipGetLastError();
-        set_error("lio_cloud_create: no HIP device %d (there is no CPU fallback)", device);
-        return nullptr;
-    }
-    if (hipSetDevice(device) != hipSuccess) { set_error("lio_cloud_create: hipSetDevice(%d) failed", device); return nullptr; }
     lio_cloud* c = new lio_cloud();
     memset(c, 0, sizeof(*c));
     c->device = device;
-    bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 5 && ok; i++) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
-    if (ok && reserve_points) ok = cloud_reserve(c, reserve_points) == LIO_OK;
-    if (!ok) {
+    if (!open_device("lio_cloud_create", device, &c->stream, c->ev, 5)) {
+        delete c;
+        return nullptr;
+    }
+    if (reserve_points && cloud_reserve(c, reserve_points) != LIO_OK) {
         lio_cloud_destroy(c);
         return nullptr;
     }
@@ -852,7 +758,7 @@ int lio_cloud_append_host(lio_cloud* c, const float* xyzi, uint64_t n, const dou
     hipSetDevice(c->device);
     int rc = cloud_reserve(c, c->n + n);
     if (rc != LIO_OK) return rc;
-    rc = grow_buffer(&c->stage, &c->stage_cap, n);
+    rc = grow("lio_cloud", &c->stage, &c->stage_cap, n, c->stream);
     if (rc != LIO_OK) return rc;
     LIO_HIP_TRY(hipMemcpyAsync(c->stage, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     return cloud_append(c, c->stage, n, make_xform(T, intensity_scale, z_band, z_min, z_max));
@@ -939,14 +845,13 @@ int lio_cloud_voxel_downsample(lio_cloud* c, float leaf, uint64_t* n_out) {
         const uint32_t* vals = odd ? vb : va;
         uint32_t* hpos = odd ? ka : kb;     // the free key buffer (n + 1 words)
         uint32_t* longlist = odd ? va : vb;  // the free value buffer (n words)
-        CL_TRY(hipMemsetAsync(table + ntiles, 0, sizeof(uint32_t), c->stream));
         cl_head_count<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(keys, n, hg.total, table);
-        rc = exclusive_scan(c->stream, table, (uint64_t)ntiles + 1, aux);
-        if (rc != LIO_OK) return fail(rc);
+        const uint32_t* d_nvox = compact_finish(c->stream, table, n);
+        if (!d_nvox) return fail(LIO_E_DEVICE);
         cl_head_write<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(c->pts, keys, vals, n, hg.n_valid, hg.total, table, ntiles, hpos, sorted);
         CL_TRY(hipGetLastError());
         uint32_t nvox = 0;
-        CL_TRY(hipMemcpyAsync(&nvox, table + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        CL_TRY(hipMemcpyAsync(&nvox, d_nvox, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         CL_TRY(hipStreamSynchronize(c->stream));
         if (nvox) {
             cl_centroid<<<dim3((nvox + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream>>>(sorted, hpos, nvox, c->pts, longlist, g);
@@ -958,8 +863,7 @@ int lio_cloud_voxel_downsample(lio_cloud* c, float leaf, uint64_t* n_out) {
     CL_TRY(hipEventRecord(c->ev[3], c->stream));
     CL_TRY(hipStreamSynchronize(c->stream));
 #undef CL_TRY
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) c->voxel_us = (double)ms * 1000.0;
+    c->voxel_us = elapsed_us(c->ev[2], c->ev[3]);
     (void)hipFree(base);
     c->n = result;
     if (n_out) *n_out = result;

@@ -9,7 +9,7 @@
 //             neighbours in ascending (d2, index) order, cyclic Jacobi in f64 (registers only), the unit eigenvector of the smallest
 //             eigenvalue, and the filter |n_z| > cos(normal_thresh) |n| (:316-320).  Fewer than 3 neighbours: NaN normal, dropped.
 //             The m x 10 index table is never written.
-//   compact   flags -> tile counts -> device-wide scan -> stable write (three times: clip, filter, inliers)
+//   compact   flags -> device_prims.h's stable compaction (three times: clip, filter, inliers)
 //   ransac    pcl::RandomSampleConsensus over SampleConsensusModelPlane (ransac.hpp), 64 hypotheses per launch:
 //             gr_planes draws three distinct indices per hypothesis from the counter-based generator of include/lio_hip.h and makes the
 //             plane in separately rounded f32; gr_score holds the 64 planes in LDS, tests every point against every plane
@@ -25,23 +25,17 @@
 #include <cmath>
 #include <vector>
 
-#include "cloud_sort.h"
+#include "device_prims.h"
 #include "knn_index_dev.h"
-#include "lio_common.h"
 
 namespace lio {
 namespace ground {
 
-constexpr int kThreads = 256;
-constexpr int kItems = 8;
-constexpr uint32_t kTile = kThreads * kItems;
-constexpr int kWaves = kThreads / 64;
+using namespace prims;
+
 constexpr int kBatch = 64;  // hypotheses per launch
 constexpr int kScoreItems = 4;
 constexpr int kK = 10;      // setKSearch(10), graph_utils.cpp:309
-
-inline uint32_t tiles_of(uint64_t n) { return (uint32_t)((n + kTile - 1) / kTile); }
-inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kThreads - 1) / kThreads); }
 
 // one batch as it goes to the host
 struct Batch {
@@ -61,7 +55,6 @@ __global__ __launch_bounds__(kThreads) void gr_clip_flags(const float4* __restri
 
 // flagged items per tile of the first n (= *d_n when given, else n_max) items
 __global__ __launch_bounds__(kThreads) void gr_count(const uint8_t* __restrict__ flags, const uint32_t* __restrict__ d_n, uint32_t n_max, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t wc[kWaves];
     const uint32_t n = d_n ? *d_n : n_max;
     const uint32_t base = blockIdx.x * kTile;
     uint32_t c = 0;
@@ -70,48 +63,26 @@ __global__ __launch_bounds__(kThreads) void gr_count(const uint8_t* __restrict__
         const uint32_t i = base + r * kThreads + threadIdx.x;
         c += (i < n && flags[i]) ? 1u : 0u;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off);
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+    compact_tile_count(c, counts);
 }
 
-// stable compaction of the flagged items (knn_index.hip's kx_compact with a flag array): the point and its original index (iin = NULL:
-// the item's own position)
+// stable compaction of the flagged items: the point and its original index (iin = NULL: the item's own position)
 __global__ __launch_bounds__(kThreads) void gr_write(const uint8_t* __restrict__ flags, const uint32_t* __restrict__ d_n, uint32_t n_max,
                                                      const uint32_t* __restrict__ offs, const float4* __restrict__ pin, const uint32_t* __restrict__ iin,
                                                      float4* __restrict__ pout, uint32_t* __restrict__ iout) {
-    __shared__ uint32_t wcnt[kItems][kWaves];
     const uint32_t n = d_n ? *d_n : n_max;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const uint32_t base = blockIdx.x * kTile;
-    unsigned long long km[kItems];
+    bool flagged[kItems];
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
-        const uint32_t i = base + r * kThreads + tid;
-        km[r] = __ballot(i < n && flags[i] != 0);
-        if (lane == 0) wcnt[r][wave] = (uint32_t)__popcll(km[r]);
+        const uint32_t i = base + r * kThreads + threadIdx.x;
+        flagged[r] = i < n && flags[i] != 0;
     }
-    __syncthreads();
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t run = offs[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < kItems; r++) {
-        uint32_t woff = 0, rtot = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) {
-            const uint32_t t = wcnt[r][w];
-            woff += (w < wave) ? t : 0u;
-            rtot += t;
-        }
-        if ((km[r] >> lane) & 1ull) {
-            const uint32_t i = base + r * kThreads + tid, o = run + woff + (uint32_t)__popcll(km[r] & lt);
-            pout[o] = pin[i];
-            iout[o] = iin ? iin[i] : i;
-        }
-        run += rtot;
-    }
+    compact_tile_write(flagged, offs, [&](int r, uint32_t o) {
+        const uint32_t i = base + r * kThreads + threadIdx.x;
+        pout[o] = pin[i];
+        iout[o] = iin ? iin[i] : i;
+    });
 }
 
 // the clipped points as the index takes them: {x, y, z, position bits}
@@ -308,8 +279,8 @@ struct lio_ground {
     float4 *stage, *cpt, *kpts, *fpt, *ipt, *normals;
     uint32_t *cidx, *fidx, *iidx;
     uint8_t* flags;
-    uint32_t* aux;     // three regions: the tile counts of the clip, the filter and the inliers, each with its scan's tile sums
-    uint64_t region;   // words per region
+    uint32_t* aux;     // three compactions' scratch: the clip, the filter and the inliers
+    uint64_t region;   // words of each (compact_words)
     knn_index::DeviceIndex* index;
     Batch* d_batch;
     Batch* h_batch;    // pinned
@@ -326,11 +297,6 @@ struct lio_ground {
 
 namespace {
 
-template <typename T>
-bool alloc(T** p, uint64_t count) {
-    return hipMalloc(p, std::max<uint64_t>(count, 1) * sizeof(T)) == hipSuccess;
-}
-
 void free_buffers(lio_ground* g) {
     void* all[] = {g->stage, g->cpt, g->kpts, g->fpt, g->ipt, g->normals, g->cidx, g->fidx, g->iidx, g->flags, g->aux};
     for (void* p : all)
@@ -341,18 +307,13 @@ void free_buffers(lio_ground* g) {
     g->cap = 0;
 }
 
-uint64_t region_words(uint64_t ntiles) {
-    const uint64_t cwords = (ntiles + 1ull + 63) & ~63ull;  // the scan's tile sums start 256-byte aligned
-    return cwords + ((cloud::scan_aux_words(ntiles + 1) + 64 + 63) & ~63ull);
-}
-
 int reserve(lio_ground* g, uint64_t n) {
     if (n <= g->cap) return LIO_OK;
     if (n > 0x7FFFFFFFull) { set_error("lio_ground: %llu points exceed the int index range (2^31 - 1)", (unsigned long long)n); return LIO_E_CAPACITY; }
     const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(n, std::max<uint64_t>(2 * g->cap, 1ull << 17)), 0x7FFFFFFFull);
     LIO_HIP_TRY(hipStreamSynchronize(g->stream));
     free_buffers(g);
-    g->region = region_words(tiles_of(want));
+    g->region = compact_words(want);
     const bool ok = alloc(&g->stage, want) && alloc(&g->cpt, want) && alloc(&g->kpts, want) && alloc(&g->fpt, want) && alloc(&g->ipt, want) &&
                     alloc(&g->normals, want) && alloc(&g->cidx, want) && alloc(&g->fidx, want) && alloc(&g->iidx, want) && alloc(&g->flags, want) &&
                     alloc(&g->aux, 3 * g->region);
@@ -371,20 +332,12 @@ int compact(lio_ground* g, int which, const uint32_t* d_n, uint32_t n_max, const
             const uint32_t** d_out_n) {
     const uint32_t ntiles = tiles_of(n_max);
     uint32_t* counts = g->aux + (uint64_t)which * g->region;
-    const uint64_t cwords = (ntiles + 1ull + 63) & ~63ull;
-    LIO_HIP_TRY(hipMemsetAsync(counts + ntiles, 0, sizeof(uint32_t), g->stream));
     gr_count<<<dim3(ntiles), dim3(kThreads), 0, g->stream>>>(g->flags, d_n, n_max, counts);
-    const int rc = cloud::exclusive_scan(g->stream, counts, ntiles + 1ull, counts + cwords);
-    if (rc != LIO_OK) return rc;
+    *d_out_n = compact_finish(g->stream, counts, n_max);
+    if (!*d_out_n) return LIO_E_DEVICE;
     gr_write<<<dim3(ntiles), dim3(kThreads), 0, g->stream>>>(g->flags, d_n, n_max, counts, pin, iin, pout, iout);
     LIO_HIP_TRY(hipGetLastError());
-    *d_out_n = counts + ntiles;
     return LIO_OK;
-}
-
-float elapsed_us(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f;
 }
 
 void clear_last(lio_ground* g) {
@@ -509,15 +462,7 @@ bool params_ok(const lio_ground_params* p) {
 }
 
 int64_t download_u32(lio_ground* g, const uint32_t* src, uint64_t n, uint32_t* out, uint64_t cap) {
-    if (n > cap) return -(int64_t)n;
-    if (n == 0) return 0;
-    if (!out) return LIO_E_INVALID;
-    hipSetDevice(g->device);
-    if (hipMemcpyAsync(out, src, n * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) {
-        set_error("lio_ground: download failed");
-        return LIO_E_DEVICE;
-    }
-    return (int64_t)n;
+    return download("lio_ground", g->device, g->stream, src, n, out, cap);
 }
 
 }  // namespace
@@ -548,24 +493,19 @@ void lio_ground_draw(uint32_t seed, uint32_t j, uint32_t n, uint32_t out[3]) {
 }
 
 lio_ground* lio_ground_create(int device) {
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) {
-        (void)hipGetLastError();
-        set_error("lio_ground_create: no HIP device %d (there is no CPU fallback)", device);
-        return nullptr;
-    }
-    if (hipSetDevice(device) != hipSuccess) { set_error("lio_ground_create: hipSetDevice(%d) failed", device); return nullptr; }
     lio_ground* g = new lio_ground();
     memset(g, 0, sizeof(*g));
     g->device = device;
+    if (!open_device("lio_ground_create", device, &g->stream, g->ev, 4)) {
+        delete g;
+        return nullptr;
+    }
     g->index = new knn_index::DeviceIndex();
     g->log_draws = new std::vector<uint32_t>();
     g->log_counts = new std::vector<uint32_t>();
     g->log_planes = new std::vector<float>();
     g->winner = -1;
-    bool ok = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 4 && ok; i++) ok = hipEventCreate(&g->ev[i]) == hipSuccess;
-    ok = ok && hipMalloc(&g->d_batch, sizeof(Batch)) == hipSuccess && hipHostMalloc(&g->h_batch, sizeof(Batch)) == hipSuccess &&
+    const bool ok = alloc(&g->d_batch, 1) && hipHostMalloc(&g->h_batch, sizeof(Batch)) == hipSuccess &&
          hipHostMalloc(&g->h_word, 64) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();

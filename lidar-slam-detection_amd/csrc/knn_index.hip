@@ -2,7 +2,7 @@
 // (slam/src/graph_utils.cpp:449-501), as an implicit bounding-volume tree over Morton-ordered leaves.
 //
 //   expand    xyz (n x 3) -> float4 {x, y, z, input index bits} + the finite points per tile
-//   compact   device-wide exclusive scan of the tile counts -> stable write of the finite points (PCL's isFinite filter; input order kept)
+//   compact   device_prims.h's stable compaction of the finite points (PCL's isFinite filter; input order kept)
 //   bbox      per-workgroup records (grid-stride) -> one workgroup folds them
 //   morton    63-bit key per point, 21 bits per axis over the finite box, as a low and a high word
 //   sort      four 8-bit passes by the low word, a gather of the high word, four passes by the high word (cloud.hip's stable radix pass)
@@ -12,8 +12,8 @@
 //   query     the queries Morton-sorted the same way; one lane per query walks the tree nearer child first without a stack (the path is the
 //             node index, one bit per level says whether the lane is in the far child), the top k in registers ordered by (d2, index);
 //             knn_index_dev.h holds the same walk as a function for kernels of other files (kept apart from this kernel's own loop: inlined
-//             from a function the compiler lays it out with more branches and two more registers) and declares the build from device
-//             memory at the end of this file's namespace
+//             from a function the compiler lays it out with more branches and two more registers) and declares the build, which takes its
+//             point count from the host (lio_knn_index_build, after the compaction) or from device memory (ground.hip)
 //
 // Exactness: a point's distance is ((dx*dx) + dy*dy) + dz*dz in f32 (d = p - q, no contraction: -ffp-contract=off); a box's bound is the same
 // expression over the clamped per-axis gaps max(lo - q, q - hi, 0).  Rounding is monotone, so the bound never exceeds the distance of a point
@@ -23,29 +23,20 @@
 #include <algorithm>
 #include <vector>
 
-#include "cloud_sort.h"
+#include "device_prims.h"
 #include "knn_index_dev.h"
-#include "lio_common.h"
 
 namespace lio {
 namespace knn_index {
 
-constexpr int kThreads = 256;
-constexpr int kItems = 8;
-constexpr uint32_t kTile = kThreads * kItems;  // points per workgroup of the expand / compact
-constexpr int kWaves = kThreads / 64;
+using namespace prims;
+
 constexpr uint32_t kBoxBlocks = 1024;          // workgroups of the bbox's first level
 constexpr int kFold = 8;                       // tree levels per fold launch (256 nodes -> 1)
 constexpr uint64_t kQueryChunk = 1ull << 22;   // queries per device pass (bounds the query scratch)
 
-inline uint64_t tiles_of(uint64_t m) { return (m + kTile - 1) / kTile; }
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
 // every input point as {x, y, z, index bits}, and the finite ones per tile
 __global__ __launch_bounds__(kThreads) void kx_expand(const float* __restrict__ xyz, uint32_t n, float4* __restrict__ pts, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t wc[kWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t base = blockIdx.x * kTile;
     uint32_t c = 0;
 #pragma unroll
@@ -57,69 +48,48 @@ __global__ __launch_bounds__(kThreads) void kx_expand(const float* __restrict__ 
             c += finite3(x, y, z) ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off);
-    if (lane == 0) wc[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+    compact_tile_count(c, counts);
 }
 
-// stable compaction of the finite points: item r of lane l of wave w goes to tile prefix + (finite items of rounds < r) + (of waves < w in
-// round r) + (of lanes < l)
+// stable compaction of the finite points (input order kept)
 __global__ __launch_bounds__(kThreads) void kx_compact(const float4* __restrict__ pts, uint32_t n, const uint32_t* __restrict__ offs, float4* __restrict__ out) {
-    __shared__ uint32_t wcnt[kItems][kWaves];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const uint32_t base = blockIdx.x * kTile;
     float4 p[kItems];
-    unsigned long long km[kItems];
+    bool fin[kItems];
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
-        const uint32_t i = base + r * kThreads + tid;
+        const uint32_t i = base + r * kThreads + threadIdx.x;
         p[r] = pts[i < n ? i : n - 1u];
-        km[r] = __ballot(i < n && finite3(p[r].x, p[r].y, p[r].z));
-        if (lane == 0) wcnt[r][wave] = (uint32_t)__popcll(km[r]);
+        fin[r] = i < n && finite3(p[r].x, p[r].y, p[r].z);
     }
-    __syncthreads();
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t run = offs[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < kItems; r++) {
-        uint32_t woff = 0, rtot = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) {
-            const uint32_t t = wcnt[r][w];
-            woff += (w < wave) ? t : 0u;
-            rtot += t;
-        }
-        if ((km[r] >> lane) & 1ull) out[run + woff + (uint32_t)__popcll(km[r] & lt)] = p[r];
-        run += rtot;
-    }
+    compact_tile_write(fin, offs, [&](int r, uint32_t o) { out[o] = p[r]; });
 }
 
-// bbox of n finite points, level 1: one record {min x y z, max x y z} per workgroup (grid-stride)
-__global__ __launch_bounds__(kThreads) void kx_box_part(const float4* __restrict__ p, uint32_t n, float* __restrict__ parts) {
-    float mn0 = INFINITY, mn1 = INFINITY, mn2 = INFINITY, mx0 = -INFINITY, mx1 = -INFINITY, mx2 = -INFINITY;
+// The build's kernels take the point count as (d_n, n_max): *d_n when d_n is given (a count that never left the device, n_max its upper
+// bound), else n_max itself.
+
+// bbox of the n finite points, level 1: one record {min x y z, max x y z} per workgroup (grid-stride)
+__global__ __launch_bounds__(kThreads) void kx_box_part(const float4* __restrict__ p, const uint32_t* __restrict__ d_n, uint32_t n_max, float* __restrict__ parts) {
+    const uint32_t n = d_n ? *d_n : n_max;
+    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
         const float4 q = p[i];
-        mn0 = fminf(mn0, q.x); mn1 = fminf(mn1, q.y); mn2 = fminf(mn2, q.z);
-        mx0 = fmaxf(mx0, q.x); mx1 = fmaxf(mx1, q.y); mx2 = fmaxf(mx2, q.z);
+        v[0] = fminf(v[0], q.x); v[1] = fminf(v[1], q.y); v[2] = fminf(v[2], q.z);
+        v[3] = fmaxf(v[3], q.x); v[4] = fmaxf(v[4], q.y); v[5] = fmaxf(v[5], q.z);
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn0 = fminf(mn0, __shfl_xor(mn0, off)); mn1 = fminf(mn1, __shfl_xor(mn1, off)); mn2 = fminf(mn2, __shfl_xor(mn2, off));
-        mx0 = fmaxf(mx0, __shfl_xor(mx0, off)); mx1 = fmaxf(mx1, __shfl_xor(mx1, off)); mx2 = fmaxf(mx2, __shfl_xor(mx2, off));
-    }
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int a = 0; a < 6; a++) v[a] = a < 3 ? fminf(v[a], __shfl_xor(v[a], off)) : fmaxf(v[a], __shfl_xor(v[a], off));
     __shared__ float red[kWaves][6];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave][0] = mn0; red[wave][1] = mn1; red[wave][2] = mn2;
-        red[wave][3] = mx0; red[wave][4] = mx1; red[wave][5] = mx2;
-    }
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 6; a++) red[threadIdx.x >> 6][a] = v[a];
     __syncthreads();
     if (threadIdx.x < 6) {
-        float v = red[0][threadIdx.x];
-        for (int w = 1; w < kWaves; w++) v = threadIdx.x < 3 ? fminf(v, red[w][threadIdx.x]) : fmaxf(v, red[w][threadIdx.x]);
-        parts[6u * blockIdx.x + threadIdx.x] = v;
+        const int a = threadIdx.x;
+        float r = red[0][a];
+        for (int w = 1; w < kWaves; w++) r = a < 3 ? fminf(r, red[w][a]) : fmaxf(r, red[w][a]);
+        parts[6u * blockIdx.x + a] = r;
     }
 }
 
@@ -163,13 +133,17 @@ __device__ __forceinline__ uint64_t morton(float x, float y, float z, const floa
     return spread3(quant21(x, b[0], b[3])) | (spread3(quant21(y, b[1], b[4])) << 1) | (spread3(quant21(z, b[2], b[5])) << 2);
 }
 
-// keys of the (finite) points of the index; vals = their positions
-__global__ __launch_bounds__(kThreads) void kx_keys_points(const float4* __restrict__ p, uint32_t n, const float* __restrict__ box, uint32_t* __restrict__ klo,
-                                                           uint32_t* __restrict__ khi, uint32_t* __restrict__ vals) {
+// keys of the n points of the index (the slots from n to n_max: ~0, behind every point); vals = their positions
+__global__ __launch_bounds__(kThreads) void kx_keys_points(const float4* __restrict__ p, const uint32_t* __restrict__ d_n, uint32_t n_max,
+                                                           const float* __restrict__ box, uint32_t* __restrict__ klo, uint32_t* __restrict__ khi,
+                                                           uint32_t* __restrict__ vals) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const float4 q = p[i];
-    const uint64_t k = morton(q.x, q.y, q.z, box);
+    if (i >= n_max) return;
+    uint64_t k = ~0ull;
+    if (i < (d_n ? *d_n : n_max)) {
+        const float4 q = p[i];
+        k = morton(q.x, q.y, q.z, box);
+    }
     klo[i] = (uint32_t)k;
     khi[i] = (uint32_t)(k >> 32);
     vals[i] = i;
@@ -192,16 +166,20 @@ __global__ __launch_bounds__(kThreads) void kx_gather_u32(const uint32_t* __rest
     if (i < n) dst[i] = src[idx[i]];
 }
 
-__global__ __launch_bounds__(kThreads) void kx_gather_points(const float4* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, float4* __restrict__ dst) {
+// the n points into sorted order (the stable sort keeps them, whose keys are below ~0 or equal to it at a smaller position, first)
+__global__ __launch_bounds__(kThreads) void kx_gather_points(const float4* __restrict__ src, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ d_n,
+                                                             uint32_t n_max, float4* __restrict__ dst) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
+    if (i < (d_n ? *d_n : n_max)) dst[i] = src[idx[i]];
 }
 
 // one AABB per leaf slot l < P at heap node P + l (nodes[2 i] = lo, nodes[2 i + 1] = hi); slots past the last leaf get the empty box
 // (lo = +inf > hi = -inf)
-__global__ __launch_bounds__(kThreads) void kx_leaf_boxes(const float4* __restrict__ leaves, uint32_t nf, uint32_t nl, uint32_t P, float4* __restrict__ nodes) {
+__global__ __launch_bounds__(kThreads) void kx_leaf_boxes(const float4* __restrict__ leaves, const uint32_t* __restrict__ d_n, uint32_t n_max, uint32_t P,
+                                                          float4* __restrict__ nodes) {
     const uint32_t l = blockIdx.x * kThreads + threadIdx.x;
     if (l >= P) return;
+    const uint32_t nf = d_n ? *d_n : n_max, nl = (nf + kLeaf - 1) / kLeaf;
     float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
     if (l < nl) {
         const uint32_t a = l * kLeaf, b = min(a + kLeaf, nf);
@@ -353,8 +331,6 @@ void launch_query(int k, hipStream_t st, const float* q, uint32_t m, const uint3
     }
 }
 
-inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kThreads - 1) / kThreads); }
-
 // device allocations of one call, freed when it returns
 struct Temps {
     std::vector<void*> p;
@@ -396,70 +372,7 @@ int morton_sort(hipStream_t st, uint32_t* klo, const uint32_t* khi, uint32_t* va
     return LIO_OK;
 }
 
-// ---- the build from device memory (knn_index_dev.h): the same stages with the point count read from *d_n by every kernel, launched over
-// its upper bound n_max; the slots past the count sort last (key ~0) and end in empty leaf boxes ----
-__global__ __launch_bounds__(kThreads) void kxd_box_part(const float4* __restrict__ p, const uint32_t* __restrict__ d_n, float* __restrict__ parts) {
-    const uint32_t n = *d_n;
-    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
-        const float4 q = p[i];
-        v[0] = fminf(v[0], q.x); v[1] = fminf(v[1], q.y); v[2] = fminf(v[2], q.z);
-        v[3] = fmaxf(v[3], q.x); v[4] = fmaxf(v[4], q.y); v[5] = fmaxf(v[5], q.z);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int a = 0; a < 6; a++) v[a] = a < 3 ? fminf(v[a], __shfl_xor(v[a], off)) : fmaxf(v[a], __shfl_xor(v[a], off));
-    __shared__ float red[kWaves][6];
-    if ((threadIdx.x & 63) == 0)
-        for (int a = 0; a < 6; a++) red[threadIdx.x >> 6][a] = v[a];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int a = threadIdx.x;
-        float r = red[0][a];
-        for (int w = 1; w < kWaves; w++) r = a < 3 ? fminf(r, red[w][a]) : fmaxf(r, red[w][a]);
-        parts[6u * blockIdx.x + a] = r;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void kxd_keys_points(const float4* __restrict__ p, const uint32_t* __restrict__ d_n, uint32_t n_max,
-                                                            const float* __restrict__ box, uint32_t* __restrict__ klo, uint32_t* __restrict__ khi,
-                                                            uint32_t* __restrict__ vals) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n_max) return;
-    uint64_t k = ~0ull;
-    if (i < *d_n) {
-        const float4 q = p[i];
-        k = morton(q.x, q.y, q.z, box);
-    }
-    klo[i] = (uint32_t)k;
-    khi[i] = (uint32_t)(k >> 32);
-    vals[i] = i;
-}
-
-__global__ __launch_bounds__(kThreads) void kxd_gather_points(const float4* __restrict__ src, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ d_n,
-                                                              float4* __restrict__ dst) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i < *d_n) dst[i] = src[idx[i]];  // (the stable sort keeps the n valid slots, whose keys are below ~0 or equal to it at a smaller position, first)
-}
-
-__global__ __launch_bounds__(kThreads) void kxd_leaf_boxes(const float4* __restrict__ leaves, const uint32_t* __restrict__ d_n, uint32_t P, float4* __restrict__ nodes) {
-    const uint32_t l = blockIdx.x * kThreads + threadIdx.x;
-    if (l >= P) return;
-    const uint32_t nf = *d_n, nl = (nf + kLeaf - 1) / kLeaf;
-    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
-    if (l < nl) {
-        const uint32_t a = l * kLeaf, b = min(a + kLeaf, nf);
-        for (uint32_t j = a; j < b; j++) {
-            const float4 p = leaves[j];
-            lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
-            hi.x = fmaxf(hi.x, p.x); hi.y = fmaxf(hi.y, p.y); hi.z = fmaxf(hi.z, p.z);
-        }
-    }
-    nodes[2ull * (P + l)] = lo;
-    nodes[2ull * (P + l) + 1] = hi;
-}
-
+// ---- the build (knn_index_dev.h) ----
 static uint32_t leaf_slots(uint64_t n, int* L) {
     const uint32_t nl = (uint32_t)((std::max<uint64_t>(n, 1) + kLeaf - 1) / kLeaf);
     int l = 0;
@@ -500,16 +413,16 @@ int device_index_reserve(DeviceIndex& x, uint64_t n_max) {
 int device_index_build(hipStream_t st, DeviceIndex& x, const float4* pts, const uint32_t* d_n, uint32_t n_max) {
     if (n_max == 0 || n_max > x.cap) return LIO_E_INVALID;
     const uint32_t nb = std::min<uint32_t>(blocks_of(n_max), kBoxBlocks);
-    kxd_box_part<<<dim3(nb), dim3(kThreads), 0, st>>>(pts, d_n, x.parts);
+    kx_box_part<<<dim3(nb), dim3(kThreads), 0, st>>>(pts, d_n, n_max, x.parts);
     kx_box_fold<<<dim3(1), dim3(kThreads), 0, st>>>(x.parts, nb, x.box);
-    kxd_keys_points<<<dim3(blocks_of(n_max)), dim3(kThreads), 0, st>>>(pts, d_n, n_max, x.box, x.klo, x.khi, x.vals);
+    kx_keys_points<<<dim3(blocks_of(n_max)), dim3(kThreads), 0, st>>>(pts, d_n, n_max, x.box, x.klo, x.khi, x.vals);
     LIO_HIP_TRY(hipGetLastError());
     uint32_t* perm = nullptr;
     const int rc = morton_sort(st, x.klo, x.khi, x.vals, x.kb, x.vb, n_max, x.scratch, &perm);
     if (rc != LIO_OK) return rc;
-    kxd_gather_points<<<dim3(blocks_of(n_max)), dim3(kThreads), 0, st>>>(pts, perm, d_n, x.leaves);
+    kx_gather_points<<<dim3(blocks_of(n_max)), dim3(kThreads), 0, st>>>(pts, perm, d_n, n_max, x.leaves);
     x.P = leaf_slots(n_max, &x.L);
-    kxd_leaf_boxes<<<dim3(blocks_of(x.P)), dim3(kThreads), 0, st>>>(x.leaves, d_n, x.P, x.nodes);
+    kx_leaf_boxes<<<dim3(blocks_of(x.P)), dim3(kThreads), 0, st>>>(x.leaves, d_n, n_max, x.P, x.nodes);
     LIO_HIP_TRY(hipGetLastError());
     for (int lv = x.L; lv > 0;) {
         const int f = std::min(lv, kFold);
@@ -551,11 +464,6 @@ void release(lio_knn_index* x) {
     x->rgb = nullptr;
     x->n = x->nf = x->nl = x->P = 0;
     x->L = 0;
-}
-
-float elapsed_us(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1000.f : 0.f;
 }
 
 // the k nearest of m host queries: (idx, d2) when rgb_out is NULL, else the colours
@@ -626,20 +534,14 @@ int run_query(lio_knn_index* x, const float* q, uint64_t m, int k, int32_t* idx,
 extern "C" {
 
 lio_knn_index* lio_knn_index_create(int device) {
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) {
-        (void)hipGetLastError();
-        set_error("lio_knn_index_create: no HIP device %d (there is no CPU fallback)", device);
-        return nullptr;
-    }
-    if (hipSetDevice(device) != hipSuccess) { set_error("lio_knn_index_create: hipSetDevice(%d) failed", device); return nullptr; }
     lio_knn_index* x = new lio_knn_index();
     memset(x, 0, sizeof(*x));
     x->device = device;
-    bool ok = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 2 && ok; i++) ok = hipEventCreate(&x->ev[i]) == hipSuccess;
-    ok = ok && hipMalloc(&x->box, 8 * sizeof(float)) == hipSuccess;
-    if (!ok) {
+    if (!open_device("lio_knn_index_create", device, &x->stream, x->ev, 2)) {
+        delete x;
+        return nullptr;
+    }
+    if (!alloc(&x->box, 8)) {
         (void)hipGetLastError();
         set_error("lio_knn_index_create: stream / event / box allocation failed");
         lio_knn_index_destroy(x);
@@ -676,8 +578,7 @@ int lio_knn_index_build(lio_knn_index* x, const float* xyz, const uint32_t* rgb,
     float* dxyz = T.get<float>(3 * n);
     float4* pts = T.get<float4>(n);
     float4* cpt = T.get<float4>(n);
-    const uint64_t cwords = (ntiles + 1ull + 63) & ~63ull;  // the scan's tile sums start 256-byte aligned (it reads them as uint4)
-    uint32_t* counts = T.get<uint32_t>(cwords + cloud::scan_aux_words(ntiles + 1) + 64);
+    uint32_t* counts = T.get<uint32_t>(compact_words(n));
     float* parts = T.get<float>(6ull * kBoxBlocks);
     if (!dxyz || !pts || !cpt || !counts || !parts) return LIO_E_DEVICE;
     if (rgb && hipMalloc(&x->rgb, n * sizeof(uint32_t)) != hipSuccess) {
@@ -690,15 +591,14 @@ int lio_knn_index_build(lio_knn_index* x, const float* xyz, const uint32_t* rgb,
     if (rgb) LIO_HIP_TRY(hipMemcpyAsync(x->rgb, rgb, n * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
     LIO_HIP_TRY(hipEventRecord(x->ev[0], x->stream));
     // finite points, compacted in input order
-    LIO_HIP_TRY(hipMemsetAsync(counts + ntiles, 0, sizeof(uint32_t), x->stream));
     kx_expand<<<dim3(ntiles), dim3(kThreads), 0, x->stream>>>(dxyz, nn, pts, counts);
     LIO_HIP_TRY(hipGetLastError());
-    int rc = cloud::exclusive_scan(x->stream, counts, ntiles + 1ull, counts + cwords);
-    if (rc != LIO_OK) return rc;
+    const uint32_t* d_nf = compact_finish(x->stream, counts, n);
+    if (!d_nf) return LIO_E_DEVICE;
     kx_compact<<<dim3(ntiles), dim3(kThreads), 0, x->stream>>>(pts, nn, counts, cpt);
     LIO_HIP_TRY(hipGetLastError());
     uint32_t nf = 0;
-    LIO_HIP_TRY(hipMemcpyAsync(&nf, counts + ntiles, sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    LIO_HIP_TRY(hipMemcpyAsync(&nf, d_nf, sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
     LIO_HIP_TRY(hipStreamSynchronize(x->stream));
     if (n_finite) *n_finite = nf;
     x->n = n;
@@ -708,45 +608,26 @@ int lio_knn_index_build(lio_knn_index* x, const float* xyz, const uint32_t* rgb,
         x->build_us = elapsed_us(x->ev[0], x->ev[1]);
         return LIO_OK;
     }
-    // the box, the Morton order, the leaves
-    const uint32_t nb = std::min<uint32_t>(ntiles, kBoxBlocks);
-    kx_box_part<<<dim3(nb), dim3(kThreads), 0, x->stream>>>(cpt, nf, parts);
-    kx_box_fold<<<dim3(1), dim3(kThreads), 0, x->stream>>>(parts, nb, x->box);
-    LIO_HIP_TRY(hipGetLastError());
-    {
-        Temps S;
-        uint32_t *klo = S.get<uint32_t>(nf), *khi = S.get<uint32_t>(nf), *vals = S.get<uint32_t>(nf), *kb = S.get<uint32_t>(nf), *vb = S.get<uint32_t>(nf);
-        uint32_t* scratch = S.get<uint32_t>(cloud::radix_scratch_words(nf));
-        if (!klo || !khi || !vals || !kb || !vb || !scratch) return LIO_E_DEVICE;
-        kx_keys_points<<<dim3(blocks_of(nf)), dim3(kThreads), 0, x->stream>>>(cpt, nf, x->box, klo, khi, vals);
-        LIO_HIP_TRY(hipGetLastError());
-        uint32_t* perm = nullptr;
-        rc = morton_sort(x->stream, klo, khi, vals, kb, vb, nf, scratch, &perm);
-        if (rc != LIO_OK) return rc;
-        kx_gather_points<<<dim3(blocks_of(nf)), dim3(kThreads), 0, x->stream>>>(cpt, perm, nf, pts);  // pts (n >= nf slots) becomes the leaves
-        LIO_HIP_TRY(hipGetLastError());
-        LIO_HIP_TRY(hipStreamSynchronize(x->stream));
-    }
-    const uint32_t nl = (nf + kLeaf - 1) / kLeaf;
+    // the tree over exactly the nf compacted points: pts (n >= nf slots) becomes the leaves; the sort scratch lives for this call
+    DeviceIndex d;
+    d.cap = nf;
+    d.leaves = pts;
+    d.box = x->box;
+    d.parts = parts;
+    d.klo = T.get<uint32_t>(nf); d.khi = T.get<uint32_t>(nf); d.vals = T.get<uint32_t>(nf); d.kb = T.get<uint32_t>(nf); d.vb = T.get<uint32_t>(nf);
+    d.scratch = T.get<uint32_t>(cloud::radix_scratch_words(nf));
+    if (!d.klo || !d.khi || !d.vals || !d.kb || !d.vb || !d.scratch) return LIO_E_DEVICE;
     int L = 0;
-    while ((1u << L) < nl) L++;
-    const uint32_t P = 1u << L;
-    if (hipMalloc(&x->nodes, 4ull * P * sizeof(float4)) != hipSuccess) {
+    const uint32_t P = leaf_slots(nf, &L);
+    if (!alloc(&x->nodes, 4ull * P)) {
         (void)hipGetLastError();
         x->nodes = nullptr;
         set_error("lio_knn_index_build: %llu bytes of device memory not available for the tree", (unsigned long long)(4ull * P * sizeof(float4)));
         return LIO_E_DEVICE;
     }
-    kx_leaf_boxes<<<dim3(blocks_of(P)), dim3(kThreads), 0, x->stream>>>(pts, nf, nl, P, x->nodes);
-    LIO_HIP_TRY(hipGetLastError());
-    for (int lv = L; lv > 0;) {
-        const int f = std::min(lv, kFold);
-        const uint32_t first = 1u << lv;
-        const uint32_t blocks = std::max<uint32_t>(1u, first / kThreads);
-        kx_fold<<<dim3(blocks), dim3(kThreads), 0, x->stream>>>(x->nodes, first, f);
-        LIO_HIP_TRY(hipGetLastError());
-        lv -= f;
-    }
+    d.nodes = x->nodes;
+    const int rc = device_index_build(x->stream, d, cpt, nullptr, nf);
+    if (rc != LIO_OK) return rc;
     LIO_HIP_TRY(hipEventRecord(x->ev[1], x->stream));
     LIO_HIP_TRY(hipStreamSynchronize(x->stream));
     x->build_us = elapsed_us(x->ev[0], x->ev[1]);
@@ -754,7 +635,7 @@ int lio_knn_index_build(lio_knn_index* x, const float* xyz, const uint32_t* rgb,
     T.p.erase(std::find(T.p.begin(), T.p.end(), (void*)pts));
     x->leaves = pts;
     x->nf = nf;
-    x->nl = nl;
+    x->nl = (nf + kLeaf - 1) / kLeaf;
     x->P = P;
     x->L = L;
     return LIO_OK;

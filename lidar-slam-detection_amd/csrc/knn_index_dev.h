@@ -120,7 +120,8 @@ struct DeviceIndex {
 };
 int device_index_reserve(DeviceIndex& x, uint64_t n_max);
 void device_index_free(DeviceIndex& x);
-// pts: n_max slots of {x, y, z, index bits}, the first *d_n of them valid and finite; everything on `st`
+// pts: n_max slots of {x, y, z, index bits}, the first *d_n of them valid and finite (d_n = NULL: all n_max); everything on `st`.  The sort
+// runs over the n_max slots, those past the count keyed ~0: they sort last and end in empty leaf boxes.
 int device_index_build(hipStream_t st, DeviceIndex& x, const float4* pts, const uint32_t* d_n, uint32_t n_max);
 
 }  // namespace knn_index

@@ -19,7 +19,7 @@
 //             with the gather of the points into sorted order
 //   centroid  one lane per voxel, sequential f32 sums; runs of >= 32 points are queued and summed one wave per
 //             run (coalesced loads, v_readlane broadcast) in the same sequential order
-#include "lio_common.h"
+#include "device_prims.h"
 
 namespace lio {
 
@@ -27,12 +27,6 @@ constexpr int kThreads = 256;
 constexpr int kItems = 8;
 constexpr int kTile = kThreads * kItems;  // 2048 keys per workgroup
 constexpr int kWaves = kThreads / 64;
-
-__device__ inline uint32_t f2ord(float f) {
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u); }
 
 // the batched chain's form (64 scans per launch: the grid is full either way): 48 workgroups per scan striding over the cloud, one set of
 // ordered-uint atomics per workgroup into the scan's device record, which vg_keys reads.  (The per-tile records below cost the batched vg_keys
@@ -310,17 +304,6 @@ __device__ __forceinline__ void radix_hist_body(const uint32_t* __restrict__ ka,
     }
     __syncthreads();
     hist[bx * 256u + threadIdx.x] = h[threadIdx.x];  // [tile][digit]: one coalesced 1-KiB row per workgroup
-}
-
-__device__ inline unsigned long long match_digit(uint32_t d, bool valid) {
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long m = __ballot(bit);
-        peers &= bit ? m : ~m;
-    }
-    return peers;
 }
 
 // (Measured in round 4 and not kept: this pass also building the NEXT pass's per-tile histogram -- one global atomic per key into the row of the
