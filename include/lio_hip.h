@@ -58,8 +58,10 @@ int lio_device_count(void);
  * 7 = lio_cloud_* (the dense-map export: a device-resident cloud that grows over a drive, and the VoxelGrid of the whole cloud);
  * 8 = lio_knn_index_* (exact k nearest neighbours over a static cloud; texture_mesh);
  * 9 = lio_ground_* (the ground detector: height clip, normals, plane RANSAC, inlier cloud);
- * 10 = lio_bev_* (the bird's-eye intensity image of a dense map: noise filter, per-pixel means, patch equalisation, 16-bit image). */
-#define LIO_ABI_VERSION 10
+ * 10 = lio_bev_* (the bird's-eye intensity image of a dense map: noise filter, per-pixel means, patch equalisation, 16-bit image);
+ * 11 = lio_keyframe_* / lio_keyframer_* / lio_radius_outlier_host (the mapping mode's key frames: decision, fitness against a rolling local map,
+ * election, radius outlier and range filters). */
+#define LIO_ABI_VERSION 11
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -907,6 +909,97 @@ int64_t lio_bev_download_image(lio_bev*, uint16_t* out, uint64_t cap);
 void lio_bev_grey_table(uint16_t out[65536]);
 /* device time (HIP events on the handle's stream) of the last preprocess (the two host read-backs included) and of the last convert */
 int lio_bev_last_times(lio_bev*, double* preprocess_us, double* convert_us);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * The mapping mode's key frames on the device (csrc/keyframe.hip): HdlGraphSlamNodelet::cloud_callback
+ * (slam/backend/hdl_graph_slam/apps/hdl_graph_slam_nodelet.cpp:163-246, "NL" below; constants NL:44-45, 61-65) and the two filters
+ * SLAM::runMappingThread puts an elected frame through (slam/src/slam.cpp:105-108, 400-411).  The pose graph, loop closure and the GNSS / floor
+ * edges are not built: odom -> map is the identity.  NULL from lio_keyframer_create without a device: there is no CPU fallback.
+ *   decide   KeyframeUpdater::is_update (include/hdl_graph_slam/keyframe_updater.hpp:60-75): delta = prev^-1 * pose, dx = |t|,
+ *            da = AngleAxis(R).angle * 180 / pi in f64, both then STORED AS f32 (is_update's float& arguments) and compared as doubles:
+ *            need = !(dx < D / 2 && da < A / 2), must = need && (dx >= 1.5 D || da >= 1.5 A).  update() (:42-58) adds the f64 dx to the
+ *            accumulated distance and moves prev.  The angle is taken through the quaternion, 2 atan2(|vec|, |w|), as Eigen does.
+ *   frame    an empty cloud leads to nothing (NL:165).  First frame (NL:169-176): update, VoxelGrid(resolution) of the cloud as it came (not
+ *            undistorted), transformed by the odometry -- pcl::transformPointCloud with a Matrix4d: f64, terms left to right, cast to f32, the
+ *            rule of lio_cloud_append_* -- which becomes the local map; no key frame.  Later frames: nothing unless need; undistortion
+ *            (lio_scan_undistort_delta with delta.cast<float>() and scan_period when no poses are given, lio_scan_undistort_poses otherwise,
+ *            NL:186-191), VoxelGrid(resolution), then the score.
+ *   score    calc_fitness_score(local_map, cloud, odom, nr, 1.0) (src/hdl_graph_slam/information_matrix_calculator.cpp:110-138): the cloud
+ *            transformed by odom.cast<float>() in f32 (the rule of lio_ndt_overlap_score), the exact nearest local-map point by the rules of
+ *            lio_knn_index (d2 = ((dx*dx) + dy*dy) + dz*dz in f32), squared distances <= fitness_range summed in f64, divided by their number
+ *            nr; DBL_MAX when nr = 0.  The sum is taken per 256 consecutive points in a fixed order and then over those records in order:
+ *            run-to-run identical.  inlier = float(nr) / n.  The candidate replaces the best one iff
+ *            0.8 score + 0.2 (1 - inlier) <= 0.8 best_score + 0.2 (1 - best_inlier); best_score starts at DBL_MAX, best_inlier at 0, and
+ *            best_inlier is NOT reset with best_score (NL:224).
+ *   must     update; the best frame is emitted -- its downsampled cloud through the filters below, its odometry pose, its header stamp, the
+ *            accumulated distance -- average_score is updated, best_score reset; every max(1, round(local_map_distance / D))-th key frame
+ *            the best cloud (before the filters), transformed by its pose (Matrix4d rule), is appended to the local map, points are dropped
+ *            from the FRONT down to local_map_cap, and the tree is rebuilt (NL:211-235).
+ *   filters  pcl::RadiusOutlierRemoval(radius, min_neighbours) restated from PCL 1.9.1's published radius_outlier_removal.hpp: the search
+ *            includes the query point, and a point stays iff MORE THAN min_neighbours points, itself included, lie within the radius.
+ *            THE PROJECT'S RULES: the distance is lio_knn_index's f32 d2; "within" is d2 <= (float)(radius * radius); coincident points
+ *            count; rows with a non-finite coordinate are dropped and counted.  Then pointsDistanceFilter(0, key_frame_range)
+ *            (slam/common/slam_utils.cpp:236-241): kept iff 0 < |x| < range && 0 < |y| < range, the f32 absolute values compared strictly
+ *            with the doubles (a point with x == 0 goes).  The survivors keep the input's order.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_keyframer lio_keyframer;
+typedef struct lio_keyframer_params {
+    double key_frame_distance;   /* D: init_slam's dist_threshold (1.0) */
+    double key_frame_degree;     /* A: init_slam's degree_threshold (10.0) */
+    double resolution;           /* VoxelGrid leaf, used as f32 (0.2) */
+    double key_frame_range;      /* init_slam's frame_range (50.0); <= 0: no range filter */
+    double scan_period;          /* 0.1, slam.cpp:103 */
+    double radius;               /* 1.0, slam.cpp:106 */
+    int32_t min_neighbours;      /* 3, slam.cpp:107 */
+    uint32_t local_map_cap;      /* ODOMETRY_LOCAL_MAP_NUM = 100000 */
+    double local_map_distance;   /* ODOMETRY_LOCAL_MAP_DIST = 2.0 */
+    double fitness_range;        /* 1.0 (a squared distance), NL:202 */
+} lio_keyframer_params;
+typedef struct lio_keyframe_report {
+    int32_t first, need, must;   /* the first frame; is_update's two flags */
+    int32_t elected, emitted;    /* the frame became the best candidate; a key frame went to the queue */
+    uint32_t nr, n_downsampled;  /* calc_fitness_score's nr; points after the VoxelGrid */
+    uint32_t local_map_size;     /* points of the local map after the call */
+    double dx, da;               /* is_update's f32 values */
+    double score;                /* DBL_MAX: none */
+    double accum_distance, average_score;
+} lio_keyframe_report;
+/* keyframe_updater.hpp:60-75, host only (no device needed); prev and pose are row-major 4 x 4 rigid transforms; any output may be NULL */
+int lio_keyframe_decide(const double prev[16], const double pose[16], double dist_threshold, double degree_threshold, int* need, int* must, double* dx,
+                        double* da);
+void lio_keyframer_default_params(lio_keyframer_params*);
+/* onInit (NL:56-110); params NULL = the defaults */
+lio_keyframer* lio_keyframer_create(int device, const lio_keyframer_params* params);
+void lio_keyframer_destroy(lio_keyframer*);
+/* back to onInit's state: the next frame is a first frame, the local map and the queue are empty; device memory is kept */
+int lio_keyframer_reset(lio_keyframer*);
+/* cloud_callback (NL:163-246) for one frame: n points (x, y, z, intensity) with their stamps (us since the header stamp), the frame's header
+ * stamp, its odometry pose, and either the frame's delta pose start^-1 * end (n_poses == 0: frame.points->T, NL:186-188) or the frame's pose
+ * list as lio_scan_undistort_poses takes it (absolute stamps, n_poses x 16 doubles; NL:190).  Synchronous.  *report may be NULL. */
+int lio_keyframer_push_host(lio_keyframer*, const float* xyzi, const uint32_t* stamp_us, uint32_t n, uint64_t header_stamp_us, const double odom[16],
+                            const double delta[16], const uint64_t* pose_stamp_us, const double* poses, uint32_t n_poses, lio_keyframe_report* report);
+/* the reference's keyframe_queue (NL:215-219, unbounded) after the two filters of slam.cpp:400-411: a FIFO */
+int lio_keyframer_pending(lio_keyframer*);
+/* the oldest key frame: its points (the count, or -(count) when xyzi is NULL or cap is too small -- the frame then stays queued; LIO_E_STATE when
+ * none is pending),
+ * its odometry pose, header stamp and accumulated distance, and the sizes of its cloud before the filters and after the radius filter */
+int64_t lio_keyframer_pop(lio_keyframer*, float* xyzi, uint64_t cap, double pose[16], uint64_t* stamp_us, double* accum_distance, uint32_t* n_before_filters,
+                          uint32_t* n_after_radius);
+/* stage doors.  The radius outlier filter over n host points on the handle's device: the kept input indices, ascending (the count, or -(count)
+ * when cap is too small); lio_keyframe_filter_host: the same followed by the range filter (range <= 0: none), as an elected frame goes through
+ * both.  lio_keyframer_fitness_host: calc_fitness_score of a host cloud against the handle's local map.  lio_keyframer_append_local_map_host:
+ * the local map's append (transform by T, drop from the front, rebuild the tree) for a host cloud; returns the local map's size.
+ * lio_keyframer_download_local_map: the count, or -(count). */
+int64_t lio_radius_outlier_host(lio_keyframer*, const float* xyzi, uint64_t n, double radius, int min_neighbours, uint32_t* keep_idx, uint64_t cap,
+                                uint32_t* n_dropped_nonfinite);
+int64_t lio_keyframe_filter_host(lio_keyframer*, const float* xyzi, uint64_t n, double radius, int min_neighbours, double range, uint32_t* keep_idx, uint64_t cap,
+                                 uint32_t* n_after_radius, uint32_t* n_dropped_nonfinite);
+int lio_keyframer_fitness_host(lio_keyframer*, const float* xyzi, uint32_t n, const double T[16], double* score, uint32_t* nr);
+int lio_keyframer_append_local_map_host(lio_keyframer*, const float* xyzi, uint32_t n, const double T[16]);
+int64_t lio_keyframer_download_local_map(lio_keyframer*, float* xyzi, uint64_t cap);
+/* device time (HIP events on the handle's stream) of the stages of the last call: upload + undistortion + VoxelGrid, the fitness score, the two
+ * filters with the download, the local map's append and rebuild; 0 for a stage that did not run */
+int lio_keyframer_last_times(lio_keyframer*, double* candidate_us, double* fitness_us, double* filters_us, double* ring_us);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

@@ -104,6 +104,68 @@ __device__ __forceinline__ void walk(float qx, float qy, float qz, const float4*
     }
 }
 
+// How many of the nf indexed points lie within r2 (d2 <= r2) of the finite query, counted up to `need`: the same stackless path as walk<K>
+// (node index + one far bit per level, nearer child first, box_bound as the lower bound), but bounded from the root -- a box is entered
+// iff its bound is <= r2, whatever was found so far -- and left for good once `need` points are counted.  count >= need is exactly
+// walk<need>'s test kd[need - 1] <= r2: both ask whether `need` points have an f32 distance of at most r2.
+__device__ __forceinline__ uint32_t walk_radius(float qx, float qy, float qz, const float4* __restrict__ nodes, const float4* __restrict__ leaves,
+                                                uint32_t nf, uint32_t P, int L, float r2, uint32_t need) {
+    uint32_t node = 1, far = 0, found = 0;
+    int lvl = 0;
+    bool down = true;
+    while (true) {
+        if (down) {
+            if (lvl == L) {
+                const uint32_t a = (node - P) * kLeaf, cnt = a < nf ? min(kLeaf, nf - a) : 0u;
+                for (uint32_t t0 = 0; t0 < cnt; t0 += 8) {
+                    float4 p[8];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) p[u] = leaves[a + min(t0 + u, cnt - 1u)];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) {
+                        const float dx = p[u].x - qx, dy = p[u].y - qy, dz = p[u].z - qz;
+                        found += (t0 + u < cnt && dx * dx + dy * dy + dz * dz <= r2) ? 1u : 0u;
+                    }
+                    if (found >= need) return found;
+                }
+                down = false;
+            } else {
+                bool e0, e1;
+                float m0, m1;
+                const uint32_t c0 = 2 * node;
+                const float b0 = box_bound(nodes, c0, qx, qy, qz, &e0, &m0), b1 = box_bound(nodes, c0 + 1, qx, qy, qz, &e1, &m1);
+                const bool right = e0 || (!e1 && (b1 < b0 || (b1 == b0 && m1 < m0)));
+                const bool ne = right ? e1 : e0;
+                const float nb = right ? b1 : b0;
+                if (ne || nb > r2) {
+                    down = false;  // neither child can hold a point within the radius
+                } else {
+                    node = c0 + (right ? 1u : 0u);
+                    lvl++;
+                    far &= ~(1u << lvl);
+                }
+            }
+        } else {
+            if (lvl == 0) break;
+            if (!((far >> lvl) & 1u)) {
+                bool es;
+                float ms;
+                const uint32_t sib = node ^ 1u;
+                const float bs = box_bound(nodes, sib, qx, qy, qz, &es, &ms);
+                if (!es && !(bs > r2)) {
+                    node = sib;
+                    far |= 1u << lvl;
+                    down = true;
+                    continue;
+                }
+            }
+            node >>= 1;
+            lvl--;
+        }
+    }
+    return found;
+}
+
 // A tree over points that are already on the device, their count there too.  The caller owns the handle; reserve() grows it geometrically
 // and build() allocates nothing.  The tree is sized by n_max (the count's upper bound, known to the host): the leaf slots past the last
 // point hold empty boxes, which the walk passes by.  After build(), leaves[0 .. *d_n) are the points in Morton order, so a self-query runs

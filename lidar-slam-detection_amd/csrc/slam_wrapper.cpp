@@ -32,6 +32,7 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <fstream>
@@ -174,6 +175,14 @@ struct Slam {
     std::string dest;
     int dest_port = 0;
     uint64_t max_points = 8000000, max_voxels = 1u << 21;
+    // key-frame output (SLAM::setParams, slam.cpp:96-108): off unless set_keyframe_output(true) / LSD_AMD_KEYFRAMES=1
+    double resolution = 0.2, key_frame_distance = 1.0, key_frame_degree = 10.0, key_frame_range = 50.0;
+    bool keyframe_output = false;
+    lio_keyframer* keyframer = nullptr;
+    std::mutex kf_mtx;
+    std::vector<float> kf_points;       // the T_static-transformed cloud and stamps of the frame in flight
+    std::vector<uint32_t> kf_stamps;
+    Mat4 last_odom_start = Mat4::identity(), last_odom_end = Mat4::identity();  // the odometry pair of the last process() call
 };
 std::unique_ptr<Slam> g;  // one global instance per process, like the reference's slam_ptr (slam_wrapper.cpp:4)
 
@@ -501,7 +510,6 @@ py::array_t<float> mat4_to_numpy_f32(const Mat4& T) {  // eigen_to_numpy(Matrix4
 // ---- hot path ---------------------------------------------------------------------------------------------------------------
 py::list init_slam(const std::string mode, const std::string map_path, const std::string method, py::list& sensor_input, double resolution,
                    float dist_threshold, float degree_threshold, float frame_range) {
-    (void)degree_threshold; (void)frame_range;
     // slam.py hands in method = "Localization" when the mode is not "mapping" (slam/slam.py:12); SLAM::SLAM then builds Locate::Localization
     const bool localization = mode == "localization" || method == "Localization";
     if (!localization && method != "FastLIO")
@@ -510,6 +518,12 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
     g->mode = localization ? "localization" : mode;
     g->method = method;
     g->map_path = map_path;
+    g->resolution = resolution;                 // SLAM::setParams (slam.cpp:96-103)
+    g->key_frame_distance = dist_threshold;
+    g->key_frame_degree = degree_threshold;
+    g->key_frame_range = frame_range;
+    const char* kf_env = std::getenv("LSD_AMD_KEYFRAMES");
+    g->keyframe_output = kf_env && kf_env[0] == '1';
     std::vector<std::string> in;
     for (auto h : sensor_input) in.push_back(py::cast<std::string>(h));
     if (localization) {
@@ -576,6 +590,7 @@ void deinit_slam() {
     if (!g) return;
     if (g->running.exchange(false) && g->lio_thread.joinable()) g->lio_thread.join();
     if (g->engine) lio_engine_destroy(g->engine);
+    if (g->keyframer) lio_keyframer_destroy(g->keyframer);
     g->loc.reset(nullptr);
     g.reset(nullptr);
 }
@@ -757,13 +772,42 @@ py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, 
             dst[4 * i + 3] = src[i * cs + 3];
             dstamp[i] = (uint32_t)asrc[i * as];  // pointcloud_attr[i].stamp = ref_attr(i, 0): float -> uint32_t
         }
+        const bool keyframes = s->keyframe_output;
+        if (keyframes) {  // the staging buffers are the engine's after the commit
+            s->kf_points.assign(dst, dst + 4 * (size_t)n);
+            s->kf_stamps.assign(dstamp, dstamp + n);
+        }
         require(lio_fastlio_pcl_commit(s->engine, n, (double)header_stamp / 1000000.0) == LIO_OK, "process: enqueue failed");
         // HDL_FastLIO::getPose: wait for the LIO thread's odometry (10 s), then get_odom2map() (identity without a graph back end) * odom.first
         std::unique_lock<std::mutex> lk(s->mtx);
         got = s->cv.wait_for(lk, std::chrono::seconds(10), [&] { return !s->odom_queue.empty(); });
+        Mat4 odom_end = Mat4::identity();
         if (got) {
             out_pose = s->odom_queue.front().first;
+            odom_end = s->odom_queue.front().second;
             s->odom_queue.pop_front();
+            s->last_odom_start = out_pose;
+            s->last_odom_end = odom_end;
+        }
+        lk.unlock();
+        // SLAM::runMappingThread -> enqueue_graph -> cloud_callback (slam.cpp:398-411, hdl_graph_slam_nodelet.cpp:163-246): the frame with its
+        // odometry pose and delta = first^-1 * second; the IMU pose list of HDL_FastLIO::prediction is not fed (the delta branch)
+        if (got && keyframes) {
+            std::lock_guard<std::mutex> kl(s->kf_mtx);
+            if (!s->keyframer) {
+                lio_keyframer_params kp;
+                lio_keyframer_default_params(&kp);
+                kp.key_frame_distance = s->key_frame_distance;
+                kp.key_frame_degree = s->key_frame_degree;
+                kp.resolution = s->resolution;
+                kp.key_frame_range = s->key_frame_range;
+                kp.scan_period = s->scan_period;
+                s->keyframer = lio_keyframer_create(0, &kp);
+                require(s->keyframer != nullptr, "process: lio_keyframer_create failed");
+            }
+            const Mat4 delta = mul(rigid_inverse(out_pose), odom_end);
+            require(lio_keyframer_push_host(s->keyframer, s->kf_points.data(), s->kf_stamps.data(), n, header_stamp, out_pose.m, delta.m, nullptr, nullptr, 0,
+                                            nullptr) == LIO_OK, "process: key-frame push failed");
         }
     }
     // SLAM::run, mapping branch (slam.cpp:344-364)
@@ -834,11 +878,46 @@ py::list get_estimate_pose(double x0, double y0, double x1, double y1) {
     return py::cast(std::vector<double>{0, 0, 0, 0, 0, 0, 0});  // x, y, z, roll, pitch, -yaw, result (0 = no estimate)
 }
 void set_destination(bool enable, std::string dest, int port) { (void)enable; if (g) { g->dest = dest; g->dest_port = port; } }
+// update_odom (slam_wrapper.cpp:105-130): the key frames cloud_callback elected since the last call, as keyframe_to_pydict's entries (:114-125:
+// points N x 4 f32 with the intensity as stored, image {}, pose 4 x 4, stamp); "odoms" stays empty without a pose graph (odom -> map is the identity)
 py::dict update_odom() {
     py::dict d;
     d["odoms"] = py::dict();
-    d["keyframes"] = py::list();
+    py::list frames;
+    if (g && g->keyframer) {
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        while (lio_keyframer_pending(g->keyframer) > 0) {
+            const int64_t n = -lio_keyframer_pop(g->keyframer, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+            py::array_t<float> pts({(py::ssize_t)n, (py::ssize_t)4});
+            float dummy[4];
+            Mat4 pose;
+            uint64_t stamp = 0;
+            require(lio_keyframer_pop(g->keyframer, n ? pts.mutable_data() : dummy, (uint64_t)n, pose.m, &stamp, nullptr, nullptr, nullptr) == n,
+                    "update_odom: key-frame pop failed");
+            py::dict f;
+            f["points"] = pts;
+            f["image"] = py::dict();
+            f["pose"] = mat4_to_numpy_f32(pose);
+            f["stamp"] = stamp;
+            frames.append(f);
+        }
+    }
+    d["keyframes"] = frames;
     return d;
+}
+// not in the reference's module: key frames out of process() / update_odom() in mapping mode (off by default; LSD_AMD_KEYFRAMES=1 in the
+// environment at init_slam switches it on for an unchanged slam.py)
+// test visibility: the f64 odometry pair (start, end of the frame) the last process() call took from the filter
+py::tuple _last_odometry() {
+    require((bool)g, "init_slam first");
+    py::array_t<double> a({4, 4}), b({4, 4});
+    std::memcpy(a.mutable_data(), g->last_odom_start.m, sizeof(double) * 16);
+    std::memcpy(b.mutable_data(), g->last_odom_end.m, sizeof(double) * 16);
+    return py::make_tuple(a, b);
+}
+void set_keyframe_output(bool enable) {
+    require((bool)g, "init_slam first");
+    g->keyframe_output = enable;
 }
 py::dict get_graph_status() {
     py::dict d;
@@ -1590,6 +1669,8 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("colouration_frame", &colouration_frame, "colouration frame", py::arg("lidar_name"), py::arg("points"), py::arg("points_attr"), py::arg("image_dict"),
           py::arg("image_stream_dict"), py::arg("image_param"));
     m.def("save_render_cloud", &save_render_cloud, "save render cloud", py::arg("file"));
+    m.def("set_keyframe_output", &set_keyframe_output, "key frames from process() through update_odom()", py::arg("enable"));
+    m.def("_last_odometry", &_last_odometry);
     m.def("_engine_handle", &_engine_handle);
     m.def("_transform_from_rpyt", &_transform_from_rpyt);
     m.def("_tum_relative_poses", &_tum_relative_poses, py::arg("poses"));

@@ -43,6 +43,9 @@ SYMBOLS = [
     "lio_bev_create", "lio_bev_destroy", "lio_bev_preprocess_host", "lio_bev_preprocess_cloud", "lio_bev_upload_pixels", "lio_bev_convert", "lio_bev_get_info",
     "lio_bev_download_pixel_coords", "lio_bev_download_kept", "lio_bev_download_pixels", "lio_bev_download_nodes", "lio_bev_download_equalised",
     "lio_bev_download_image", "lio_bev_grey_table", "lio_bev_last_times",
+    "lio_keyframe_decide", "lio_keyframer_default_params", "lio_keyframer_create", "lio_keyframer_destroy", "lio_keyframer_reset", "lio_keyframer_push_host",
+    "lio_keyframer_pending", "lio_keyframer_pop", "lio_radius_outlier_host", "lio_keyframe_filter_host", "lio_keyframer_fitness_host",
+    "lio_keyframer_append_local_map_host", "lio_keyframer_download_local_map", "lio_keyframer_last_times",
     "lio_pose_estimator_create", "lio_pose_estimator_destroy", "lio_pose_estimator_predict", "lio_pose_estimator_match", "lio_pose_estimator_match_gps", "lio_pose_estimator_guess", "lio_pose_estimator_observe",
     "lio_pose_estimator_match_gps_only", "lio_pose_estimator_get_timed_pose", "lio_pose_estimator_predict_nostate",
     "lio_pose_estimator_correct", "lio_pose_estimator_get_dt", "lio_pose_estimator_get", "lio_pose_estimator_set", "lio_pose_estimator_matrix",
@@ -104,6 +107,18 @@ class GroundParams(C.Structure):  # lio_ground_params
     _fields_ = [("sensor_height", C.c_double), ("clip_low", C.c_double), ("clip_high", C.c_double), ("use_normal_filter", C.c_int32),
                 ("normal_thresh_deg", C.c_double), ("k", C.c_int32), ("distance_threshold", C.c_double), ("min_points", C.c_int32),
                 ("floor_normal_thresh_deg", C.c_double), ("max_iterations", C.c_int32), ("probability", C.c_double), ("seed", C.c_uint32)]
+
+
+class KeyframerParams(C.Structure):  # lio_keyframer_params
+    _fields_ = [("key_frame_distance", C.c_double), ("key_frame_degree", C.c_double), ("resolution", C.c_double), ("key_frame_range", C.c_double),
+                ("scan_period", C.c_double), ("radius", C.c_double), ("min_neighbours", C.c_int32), ("local_map_cap", C.c_uint32),
+                ("local_map_distance", C.c_double), ("fitness_range", C.c_double)]
+
+
+class KeyframeReport(C.Structure):  # lio_keyframe_report
+    _fields_ = [("first", C.c_int32), ("need", C.c_int32), ("must", C.c_int32), ("elected", C.c_int32), ("emitted", C.c_int32), ("nr", C.c_uint32),
+                ("n_downsampled", C.c_uint32), ("local_map_size", C.c_uint32), ("dx", C.c_double), ("da", C.c_double), ("score", C.c_double),
+                ("accum_distance", C.c_double), ("average_score", C.c_double)]
 
 
 class BevInfo(C.Structure):  # lio_bev_info
@@ -276,6 +291,21 @@ def lib():
     sig("lio_ground_download_draws", C.c_int64, vp, u32p, u32p, f32p, u64)
     sig("lio_ground_last_run", cint, vp, C.POINTER(cint), C.POINTER(cint), C.POINTER(cint), C.POINTER(cint))
     sig("lio_ground_last_times", cint, vp, f64p, f64p)
+    kp, kr, u64p = C.POINTER(KeyframerParams), C.POINTER(KeyframeReport), C.POINTER(u64)
+    sig("lio_keyframe_decide", cint, f64p, f64p, dbl, dbl, C.POINTER(cint), C.POINTER(cint), f64p, f64p)
+    sig("lio_keyframer_default_params", None, kp)
+    sig("lio_keyframer_create", vp, cint, kp)
+    sig("lio_keyframer_destroy", None, vp)
+    sig("lio_keyframer_reset", cint, vp)
+    sig("lio_keyframer_push_host", cint, vp, f32p, u32p, u32, u64, f64p, f64p, u64p, f64p, u32, kr)
+    sig("lio_keyframer_pending", cint, vp)
+    sig("lio_keyframer_pop", C.c_int64, vp, f32p, u64, f64p, u64p, f64p, u32p, u32p)
+    sig("lio_radius_outlier_host", C.c_int64, vp, f32p, u64, dbl, cint, u32p, u64, u32p)
+    sig("lio_keyframe_filter_host", C.c_int64, vp, f32p, u64, dbl, cint, dbl, u32p, u64, u32p, u32p)
+    sig("lio_keyframer_fitness_host", cint, vp, f32p, u32, f64p, f64p, u32p)
+    sig("lio_keyframer_append_local_map_host", cint, vp, f32p, u32, f64p)
+    sig("lio_keyframer_download_local_map", C.c_int64, vp, f32p, u64)
+    sig("lio_keyframer_last_times", cint, vp, f64p, f64p, f64p, f64p)
     u16p = C.POINTER(C.c_uint16)
     sig("lio_bev_create", vp, cint)
     sig("lio_bev_destroy", None, vp)

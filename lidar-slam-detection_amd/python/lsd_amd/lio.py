@@ -866,6 +866,123 @@ class GroundDetector:
         return a.value, b.value
 
 
+def keyframe_decide(prev, pose, dist_threshold, degree_threshold):
+    """lio_keyframe_decide (KeyframeUpdater::is_update, keyframe_updater.hpp:60-75) on the host: (need, must, dx, da)"""
+    a, b = f64(prev).reshape(16), f64(pose).reshape(16)
+    need, must, dx, da = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
+    check(lib().lio_keyframe_decide(ptr(a, C.c_double), ptr(b, C.c_double), float(dist_threshold), float(degree_threshold), C.byref(need), C.byref(must),
+                                    C.byref(dx), C.byref(da)), "keyframe_decide")
+    return bool(need.value), bool(must.value), dx.value, da.value
+
+
+class KeyFramer:
+    """lio_keyframer: the mapping mode's key-frame producer (HdlGraphSlamNodelet::cloud_callback + the two filters of SLAM::runMappingThread)
+    on the device; include/lio_hip.h states every rule.  push() takes one odometry frame, pop() hands out the key frames in order."""
+
+    keyframe_decide = staticmethod(keyframe_decide)
+
+    def __init__(self, device=0, **over):
+        self.params = self.default_params(**over)
+        self.h = lib().lio_keyframer_create(device, C.byref(self.params))
+        if not self.h:
+            raise capi.LioError("lio_keyframer_create failed: " + lib().lio_last_error().decode())
+
+    @staticmethod
+    def default_params(**over):
+        p = capi.KeyframerParams()
+        lib().lio_keyframer_default_params(C.byref(p))
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise ValueError(f"lio_keyframer_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_keyframer_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        check(lib().lio_keyframer_reset(self.h), "keyframer reset")
+
+    def push(self, xyzi, stamp_us, header_stamp_us, odom, delta=None, pose_stamps_us=None, poses=None):
+        """one frame: N x 4 points, their stamps (us since the header stamp), the header stamp, the odometry pose (4 x 4) and either the frame's
+        delta pose or its pose list (absolute stamps, n x 4 x 4); returns the report as a dict"""
+        pts = f32(xyzi).reshape(-1, 4)
+        st = np.ascontiguousarray(stamp_us, np.uint32).reshape(-1)
+        assert len(st) == len(pts)
+        T = f64(odom).reshape(16)
+        rep = capi.KeyframeReport()
+        if poses is not None and len(poses):
+            ps = np.ascontiguousarray(pose_stamps_us, np.uint64).reshape(-1)
+            pT = f64(poses).reshape(-1, 16)
+            assert len(ps) == len(pT)
+            rc = lib().lio_keyframer_push_host(self.h, ptr(pts, C.c_float), ptr(st, C.c_uint32), len(pts), int(header_stamp_us), ptr(T, C.c_double), None,
+                                               ptr(ps, C.c_uint64), ptr(pT, C.c_double), len(ps), C.byref(rep))
+        else:
+            D = f64(delta if delta is not None else np.eye(4)).reshape(16)
+            rc = lib().lio_keyframer_push_host(self.h, ptr(pts, C.c_float), ptr(st, C.c_uint32), len(pts), int(header_stamp_us), ptr(T, C.c_double),
+                                               ptr(D, C.c_double), None, None, 0, C.byref(rep))
+        check(rc, "keyframer push")
+        return {k: getattr(rep, k) for k, _ in capi.KeyframeReport._fields_}
+
+    def pending(self):
+        return int(lib().lio_keyframer_pending(self.h))
+
+    def pop(self):
+        """the oldest key frame: dict(points N x 4 f32, pose 4 x 4 f64, stamp, accum_distance, n_before_filters, n_after_radius); None when none is pending"""
+        if self.pending() <= 0:
+            return None
+        n = -int(lib().lio_keyframer_pop(self.h, None, 0, None, None, None, None, None))
+        out = np.zeros((max(n, 1), 4), np.float32)
+        pose, stamp, acc, nb, nr = np.zeros(16), C.c_uint64(0), C.c_double(0), C.c_uint32(0), C.c_uint32(0)
+        n = check(int(lib().lio_keyframer_pop(self.h, ptr(out, C.c_float), len(out), ptr(pose, C.c_double), C.byref(stamp), C.byref(acc), C.byref(nb),
+                                              C.byref(nr))), "keyframer pop")
+        return dict(points=out[:n].copy(), pose=pose.reshape(4, 4), stamp=int(stamp.value), accum_distance=acc.value, n_before_filters=int(nb.value),
+                    n_after_radius=int(nr.value))
+
+    def radius_outlier(self, xyzi, radius=1.0, min_neighbours=3, key_frame_range=0.0):
+        """(kept input indices ascending, rows dropped as not finite, points the radius filter alone keeps): pcl::RadiusOutlierRemoval and, with
+        key_frame_range > 0, pointsDistanceFilter(0, range) behind it"""
+        pts = f32(xyzi).reshape(-1, 4)
+        out, nrad, ndrop = np.zeros(max(len(pts), 1), np.uint32), C.c_uint32(0), C.c_uint32(0)
+        n = int(lib().lio_keyframe_filter_host(self.h, ptr(pts, C.c_float), len(pts), float(radius), int(min_neighbours), float(key_frame_range),
+                                               ptr(out, C.c_uint32), len(out), C.byref(nrad), C.byref(ndrop)))
+        check(n, "radius_outlier")
+        return out[:n].copy(), int(ndrop.value), int(nrad.value)
+
+    def fitness(self, xyzi, T):
+        """calc_fitness_score of a cloud at pose T against the local map: (score, nr); score is DBL_MAX when nr is 0"""
+        pts = f32(xyzi).reshape(-1, 4)
+        M = f64(T).reshape(16)
+        score, nr = C.c_double(0), C.c_uint32(0)
+        check(lib().lio_keyframer_fitness_host(self.h, ptr(pts, C.c_float), len(pts), ptr(M, C.c_double), C.byref(score), C.byref(nr)), "keyframer fitness")
+        return score.value, int(nr.value)
+
+    def append_local_map(self, xyzi, T):
+        """the local map's append for a host cloud (transform, drop from the front, rebuild the tree); returns the local map's size"""
+        pts = f32(xyzi).reshape(-1, 4)
+        M = f64(T).reshape(16)
+        n = lib().lio_keyframer_append_local_map_host(self.h, ptr(pts, C.c_float), len(pts), ptr(M, C.c_double))
+        check(n, "keyframer append_local_map")
+        return int(n)
+
+    def local_map(self):
+        n = -int(lib().lio_keyframer_download_local_map(self.h, None, 0))
+        out = np.zeros((max(n, 0), 4), np.float32)
+        if n > 0:
+            check(int(lib().lio_keyframer_download_local_map(self.h, ptr(out, C.c_float), n)), "keyframer local_map")
+        return out
+
+    def last_times(self):
+        """dict of device microseconds per stage of the last call: candidate, fitness, filters, ring"""
+        v = [C.c_double(0) for _ in range(4)]
+        check(lib().lio_keyframer_last_times(self.h, *[C.byref(x) for x in v]), "keyframer times")
+        return dict(candidate_us=v[0].value, fitness_us=v[1].value, filters_us=v[2].value, ring_us=v[3].value)
+
+
 class BevImage:
     """lio_bev: the bird's-eye intensity image of tools/postprocessing/convert_cloud_image.py on the device (include/lio_hip.h states every
     rule): noise filter by intensity rank, per-pixel means, patch-wise histogram equalisation, 16-bit grey image.  An invalid argument (no
