@@ -60,8 +60,10 @@ int lio_device_count(void);
  * 9 = lio_ground_* (the ground detector: height clip, normals, plane RANSAC, inlier cloud);
  * 10 = lio_bev_* (the bird's-eye intensity image of a dense map: noise filter, per-pixel means, patch equalisation, 16-bit image);
  * 11 = lio_keyframe_* / lio_keyframer_* / lio_radius_outlier_host (the mapping mode's key frames: decision, fitness against a rolling local map,
- * election, radius outlier and range filters). */
-#define LIO_ABI_VERSION 11
+ * election, radius outlier and range filters);
+ * 12 = lio_loop_* (loop detection over the key frames: candidate search, batched FAST_VGICP with the LM loop on the device, nearest-neighbour
+ * fitness, FAST_GICP verification, the loop edge with its information matrix). */
+#define LIO_ABI_VERSION 12
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1000,6 +1002,131 @@ int64_t lio_keyframer_download_local_map(lio_keyframer*, float* xyzi, uint64_t c
 /* device time (HIP events on the handle's stream) of the stages of the last call: upload + undistortion + VoxelGrid, the fitness score, the two
  * filters with the download, the local map's append and rebuild; 0 for a stage that did not run */
 int lio_keyframer_last_times(lio_keyframer*, double* candidate_us, double* fitness_us, double* filters_us, double* ring_us);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * Loop detection over the key frames on the device (csrc/loop.hip): hdl_graph_slam::LoopDetector
+ * (slam/backend/hdl_graph_slam/include/hdl_graph_slam/loop_detector.hpp, "LD" below).  The pose graph is not built: the detector stops at the
+ * loop edge -- the pair, the relative pose, the score and the information matrix -- which is what the reference hands to add_se3_edge.
+ * NULL from lio_loop_create without a device: there is no CPU fallback.
+ *   candidates  find_candidates (LD:106-140), statement for statement: nothing when new.accum - last_edge_accum < distance_from_last_edge_thresh;
+ *               a frame is passed over when new.accum - k.accum < accum_distance_thresh (strict), when k.accum - (accum of the last ACCEPTED
+ *               candidate, -100 at the start) < distance_keyframe_thresh, or when the planar distance of the two estimates is > distance_thresh
+ *               (strict: a frame exactly at the threshold stays).
+ *   detect      detect (LD:69-93) over the queued new frames in order: a frame is passed over when its accum - (accum of the last new frame that
+ *               was matched, 0 at the start of every call) < distance_new_keyframe_thresh; then matching; afterwards the new frames join the
+ *               key frames (optimization_timer_callback, apps/hdl_graph_slam_nodelet.cpp:623).
+ *   matching    (LD:148-219) the TARGET is the new frame, the sources are the candidates.  guess = new^-1 * candidate in f64, both rotations
+ *               renormalised through a quaternion first, cast to f32, then guess(2,3) = 0.  Coarse: FAST_VGICP (src/hdl_graph_slam/registrations.cpp:56-66:
+ *               resolution 1.0, translation epsilon 0.1, rotation epsilon 0.1, 64 iterations, k = 20, DIRECT1) for ALL candidates in one batch
+ *               with LsqRegistration's LM loop (lsq.h) on the device.  A candidate that did not converge is skipped; a candidate replaces the
+ *               best unless score > best_score (an equal score takes the LATER one); best_score > 2 fitness_score_thresh ends the frame.  Fine:
+ *               FAST_GICP (registrations.cpp:33-42; max correspondence distance fine_max_corr_dist = 0.5, LD:59) from the coarse result of the
+ *               best; not converged, or score > fitness_score_thresh, ends the frame; otherwise last_edge_accum_distance = new.accum.
+ *   fitness     pcl::Registration::getFitnessScore(max_range), restated from PCL 1.9.1's published registration.hpp (PCL is not in the tree): the
+ *               source transformed by the f32 final transformation (pcl::transformPointCloud with a Matrix4f: terms left to right), the exact
+ *               nearest target point, d2 <= max_range applied to the SQUARED distance (fitness_score_max_range = 25 is 5 m), the sum divided by
+ *               the number nr of such points, DBL_MAX when nr = 0.  THE PROJECT'S RULES: lio_knn_index's f32 d2 = ((dx*dx) + dy*dy) + dz*dz, ties to
+ *               the smaller index; f64 sums taken per 256 consecutive points in a fixed order and then over those records in order (the
+ *               keyframer's rule): run-to-run identical.
+ *   information InformationMatrixCalculator::calc_information_matrix(const double&) with weight() and the constructor's constants
+ *               (include/hdl_graph_slam/information_matrix_calculator.hpp:44-47, src/hdl_graph_slam/information_matrix_calculator.cpp:10-21,50-63):
+ *               var_gain_a 20, stddev x in [0.1, 5], q in [0.05, 0.2], its own fitness_score_thresh 0.5; w_x and w_q are rounded to f32 (the
+ *               reference's float locals) before the identity's diagonal is divided by them.
+ *   bank        a key frame is uploaded once; its regularised k-NN covariances (calculate_covariances, fast_gicp_impl.hpp:244-303, the path of
+ *               lio_gicp_set_source) are computed once and stay resident with the cloud (both in the caller's point order) for the frame's
+ *               life -- the reference's setInputSource computes them again every time a frame is a candidate.  A hash grid's own point order is
+ *               the arrival order inside a cell and differs from one insertion to the next; every sum over a frame (cost, fitness, the fold of
+ *               a target's Gaussian voxels) therefore runs in the frame's own order, so the same frames give the same bits after a reset.
+ * THE PROJECT'S RULES of the batch: every slot folds its own workgroup partials in workgroup order with f64 accumulators (the fold of the
+ * single-pair lio_gicp_align); no floating-point atomics; a slot's numbers do not depend on its neighbours or on its place in the batch.
+ * DEVIATIONS: the coarse matcher is the reference's non-CUDA branch (FAST_VGICP; the CUDA build's NDT_CUDA coarse step is not offered), and
+ * setMaxProcessTime(50000) does not apply (a wall-clock rule, as for lio_ndt_align_batch).  A THIRD, found while the vectors were recorded: when
+ * NO source point of a candidate meets a voxel, H and b are zero; Eigen's LDLT answers a null step, which the reference accepts, and it reports
+ * the untouched guess as CONVERGED and scores it.  lsq.h's ldlt_solve6 (shared with lio_ndt_align / lio_gicp_align) reports the zero pivot and
+ * the alignment ends NOT converged, here as in the single-pair path: the detector skips such a candidate.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_loop lio_loop;
+typedef struct lio_loop_params {
+    double distance_thresh;                 /* 15 (LD:43) */
+    double accum_distance_thresh;           /* 25 */
+    double distance_from_last_edge_thresh;  /* 15 */
+    double distance_new_keyframe_thresh;    /* 2 */
+    double distance_keyframe_thresh;        /* 2 */
+    double fitness_score_max_range;         /* 25, compared with a squared distance (LD:49) */
+    double fitness_score_thresh;            /* 1.5 */
+    double fine_max_corr_dist;              /* 0.5 (LD:59) */
+    double voxel_resolution;                /* 1.0 (registrations.cpp:59) */
+    double coarse_translation_epsilon;      /* 0.1 */
+    double coarse_rotation_epsilon_deg;     /* 0.1 */
+    double fine_translation_epsilon;        /* 0.01 (registrations.cpp:37) */
+    double fine_rotation_epsilon_deg;       /* 1e-2 (LsqRegistration's default, lsq_registration_impl.hpp:24) */
+    int32_t max_iterations;                 /* 64 */
+    int32_t k_correspondences;              /* 20 */
+    float grid_resolution;                  /* cell of the hash grids the exact searches walk (1.0); a speed knob, never a result */
+    uint32_t max_points;                    /* largest key frame taken (65536) */
+    uint32_t max_candidates;                /* candidates aligned per launch set (64); more go through in further sets, same results */
+    uint32_t pad;
+} lio_loop_params;
+typedef struct lio_loop_edge {
+    int32_t key1, key2;          /* the new frame; the matched earlier frame */
+    float relative_pose[16];     /* getFinalTransformation of the fine matcher, row-major: key2's frame -> key1's frame */
+    double score;                /* the fine fitness */
+    double information[36];      /* lio_loop_information_matrix(score) */
+} lio_loop_edge;
+#define LIO_LOOP_FOUND 0
+#define LIO_LOOP_NO_CANDIDATE 1          /* the last-edge gate, or no earlier frame passed find_candidates */
+#define LIO_LOOP_COARSE_SCORE 2          /* no candidate converged, or the best coarse score > 2 fitness_score_thresh */
+#define LIO_LOOP_FINE_NOT_CONVERGED 3
+#define LIO_LOOP_FINE_SCORE 4            /* fine score > fitness_score_thresh */
+typedef struct lio_loop_report {
+    int32_t new_id;              /* the last new frame that reached matching; -1: none since the handle was made / reset */
+    int32_t n_candidates;
+    int32_t best;                /* index into the candidate list; -1: none */
+    int32_t fine_converged, fine_iterations;
+    int32_t reason;              /* LIO_LOOP_* */
+    int32_t coarse_rounds;       /* launch sets of the coarse batch (evaluations + LM step); 0: nothing was launched */
+    int32_t pad;
+    double best_score;           /* coarse; DBL_MAX: none */
+    double fine_score;           /* DBL_MAX: not run or nr = 0 */
+} lio_loop_report;
+void lio_loop_default_params(lio_loop_params*);
+/* host only (no device needed).  find_candidates over n key frames (accumulated distance, planar position of the estimate) for a new frame:
+ * the indices of the candidates, ascending; the count, or -(count) when cap is too small */
+int lio_loop_find_candidates(const double* accum, const double* pos_xy, uint32_t n, double new_accum, const double new_xy[2], double last_edge_accum,
+                             const lio_loop_params* params, int32_t* out_idx, uint32_t cap);
+int lio_loop_information_matrix(double fitness_score, double out36[36]);
+/* params NULL = the defaults */
+lio_loop* lio_loop_create(int device, const lio_loop_params* params);
+void lio_loop_destroy(lio_loop*);
+/* no key frames, no edges, last_edge_accum_distance = 0; scratch memory is kept */
+int lio_loop_reset(lio_loop*);
+/* a key frame into the bank and the new_keyframes queue: the id (0, 1, ...), LIO_E_INVALID for n < k (as lio_gicp_set_*), LIO_E_CAPACITY for
+ * n > max_points.  pose = node->estimate(), row-major 4 x 4 */
+int lio_loop_add_keyframe_host(lio_loop*, const float* xyzi, uint32_t n, const double pose[16], double accum_distance);
+int lio_loop_set_pose(lio_loop*, int id, const double pose[16]);
+int lio_loop_num_keyframes(lio_loop*, int* n_queued);
+/* a frame's resident cloud (the order it was added in) and covariances (xx, xy, xz, yy, yz, zz); the count, or -(count) when cap is too small */
+int lio_loop_download_keyframe(lio_loop*, int id, float* xyzi, double* cov6, uint32_t cap);
+/* detect over the queued frames; the loops of THIS call into out_loops.  The count, or -(count) when cap is too small: the call has then done its
+ * work all the same and the edges are read with lio_loop_edges, which returns every edge since the last reset by the same convention.  On a
+ * device error (a negative LIO_E_* code) the queue is emptied as well: the frame that failed and those behind it become key frames that were
+ * never matched, the edges found before it stay, and a repeated call does not match the same frames twice */
+int lio_loop_detect(lio_loop*, lio_loop_edge* out_loops, uint32_t cap);
+int lio_loop_edges(lio_loop*, lio_loop_edge* out, uint32_t cap);
+/* of the last new frame that reached matching; per candidate (arrays of cap entries, any may be NULL): id, converged, iterations, coarse score
+ * (DBL_MAX where it was not taken).  The number of candidates, or -(number) when cap is too small (the record is still filled) */
+int lio_loop_last_report(lio_loop*, lio_loop_report* report, int32_t* candidate_ids, int32_t* converged, int32_t* iterations, double* scores, uint32_t cap);
+/* device time (HIP events) summed over the last detect call: target build (grid, voxels, index), coarse batch, fitness, fine step; and of the
+ * last bank insert */
+int lio_loop_last_times(lio_loop*, double* insert_us, double* target_us, double* coarse_us, double* fitness_us, double* fine_us);
+/* stage door: the coarse batch and the fitness on their own.  n alignments of bank frames source_ids[] against bank frame target_id from
+ * guesses (n x 16 f64, used as given); per job the final f64 transform, iterations, converged, fitness score (DBL_MAX when nr = 0 or not
+ * converged) and nr.  Any output may be NULL */
+int lio_loop_align_candidates(lio_loop*, int target_id, const int32_t* source_ids, uint32_t n, const double* guesses, double* out_T, int32_t* iterations,
+                              int32_t* converged, double* scores, uint32_t* nr);
+/* stage door: the fine matcher (FAST_GICP at fine_max_corr_dist) and its fitness for one pair of bank frames */
+int lio_loop_align_fine(lio_loop*, int target_id, int source_id, const double guess[16], double out_T[16], int32_t* iterations, int32_t* converged, double* score,
+                        uint32_t* nr);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

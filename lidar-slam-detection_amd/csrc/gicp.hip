@@ -20,33 +20,13 @@
 
 #include <vector>
 
+#include "gicp_dev.h"
 #include "hashgrid.h"
 #include "lio_common.h"
 #include "lsq.h"
 
 namespace lio {
 
-constexpr int kGicpThreads = 128;
-constexpr int kGicpMaxK = 32;
-constexpr int kGicpAcc = 29;  // 21 H (upper), 6 b, err, count
-
-struct GicpXform {
-    double R[9], t[3];   // trans (double)
-    float Rf[9], tf[3];  // trans.cast<float>()
-};
-
-__device__ inline bool grid_find_slot(const Slot* __restrict__ table, uint32_t mask, int cx, int cy, int cz, uint32_t& ptr, uint32_t& cnt, uint32_t& slot) {
-    const unsigned long long want = pack_key(cx, cy, cz);
-    BrickProbe bp = brick_probe(cx, cy, cz);
-    for (uint32_t probe = 0; probe <= (mask >> 6); probe++) {
-        const uint32_t h = brick_slot(bp, mask);
-        const Slot sl = table[h];
-        if (sl.key == want) { ptr = sl.ptr; cnt = sl.cnt; slot = h; return cnt > 0; }
-        if (sl.key == kEmptyKey) return false;
-        brick_next(bp);
-    }
-    return false;
-}
 
 // k nearest neighbours of every point of the cloud within the cloud itself (the point is its own nearest), their covariance, PLANE
 // regularisation.  cov6 = (xx, xy, xz, yy, yz, zz) of the regularised matrix, pool order.
@@ -273,15 +253,6 @@ __global__ void __launch_bounds__(kGicpThreads) gicp_cost_kernel(const float4* _
 // Target = Gaussian voxels of `voxel_resolution` (key floor(x / res - 0.5) in f64): mean of the points' positions and mean of their
 // (regularised, 20-NN) covariances, ADDITIVE mode; a source point corresponds to the voxel(s) its transformed position falls in (DIRECT1:
 // that voxel; DIRECT7 / 27: its neighbours too), weight sqrt(points in the voxel), Mahalanobis matrix (C_voxel + R C_A R^T)^-1.
-struct __attribute__((aligned(16))) VgicpVoxel {
-    double mean[3];
-    double cov[6];
-    double n;
-};
-struct VgicpOffsets {
-    int n;
-    int off[27][3];
-};
 
 // stamp: the voxel map's copy of the target carries the point's index in the k-NN grid's pool order (where its covariance lies)
 __global__ void __launch_bounds__(256) vgicp_stamp_kernel(const float4* __restrict__ in, float4* __restrict__ out, uint32_t n) {
@@ -314,30 +285,55 @@ __global__ void __launch_bounds__(256) vgicp_fold_kernel(const Slot* __restrict_
     vox[h] = v;
 }
 
-__device__ inline void gicp_transform_d(const GicpXform& X, const float4 a, double ta[3]) {
-    const double ax = (double)a.x, ay = (double)a.y, az = (double)a.z;
-    ta[0] = (X.R[0] * ax + X.R[1] * ay) + (X.R[2] * az + X.t[0]);
-    ta[1] = (X.R[3] * ax + X.R[4] * ay) + (X.R[5] * az + X.t[1]);
-    ta[2] = (X.R[6] * ax + X.R[7] * ay) + (X.R[8] * az + X.t[2]);
+// The fold for a target adopted with its rows (grid0[i].w = the row of the point in the caller's cloud): a voxel's points are taken by rising
+// row, not in the voxel map's pool order, which is their arrival order and differs from one build to the next.
+// Step 1, one lane per target point i (= its row in grid0, the order it was inserted into the voxel map in, so slot_of_point[i] is its voxel):
+// its rank among the rows of its voxel, and order[voxel's first + rank] = i.  Rows are distinct, so the ranks of a voxel are 0 .. cnt-1, each
+// once.  The work per lane is the voxel's count; the voxels' square sums are spread over all points' lanes.
+__global__ void __launch_bounds__(256) vgicp_rank_rows_kernel(const Slot* __restrict__ table, const uint32_t* __restrict__ slot_of_point,
+                                                              const float4* __restrict__ pool, const float4* __restrict__ grid0, uint32_t n,
+                                                              uint32_t* __restrict__ order) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t sp = slot_of_point[i];
+    if (sp == kNoIdx) return;  // (the insert has reported it: vgicp_build has returned before this launch)
+    const Slot s = table[sp & 0x7FFFFFFFu];
+    const uint32_t row = __float_as_uint(grid0[i].w);
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < s.cnt; j++) {
+        const uint32_t o = __float_as_uint(pool[s.ptr + j].w);  // a stamp of vgicp_stamp_kernel for the same n; the test keeps a damaged pool in bounds
+        if (o < n) rank += __float_as_uint(grid0[o].w) < row;
+    }
+    if (rank < s.cnt && (unsigned long long)s.ptr + rank < n) order[s.ptr + rank] = i;  // (a first batch is laid out exactly: ptr + cnt <= n)
 }
-__device__ inline void gicp_mahalanobis(const double* __restrict__ ca, const double* __restrict__ cb, const GicpXform& X, double* __restrict__ o) {
-    const double A[9] = {ca[0], ca[1], ca[2], ca[1], ca[3], ca[4], ca[2], ca[4], ca[5]};
-    double RA[9], M[9];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) { double s = 0; for (int k2 = 0; k2 < 3; k2++) s += X.R[r * 3 + k2] * A[k2 * 3 + c]; RA[r * 3 + c] = s; }
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) { double s = 0; for (int k2 = 0; k2 < 3; k2++) s += RA[r * 3 + k2] * X.R[c * 3 + k2]; M[r * 3 + c] = s; }
-    M[0] += cb[0]; M[1] += cb[1]; M[2] += cb[2]; M[3] += cb[1]; M[4] += cb[3]; M[5] += cb[4]; M[6] += cb[2]; M[7] += cb[4]; M[8] += cb[5];
-    const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
-    const double det = M[0] * c00 + M[1] * c01 + M[2] * c02;
-    const double id = 1.0 / det;
-    o[0] = c00 * id;
-    o[1] = (M[2] * M[7] - M[1] * M[8]) * id;
-    o[2] = (M[1] * M[5] - M[2] * M[4]) * id;
-    o[3] = (M[0] * M[8] - M[2] * M[6]) * id;
-    o[4] = (M[2] * M[3] - M[0] * M[5]) * id;
-    o[5] = (M[0] * M[4] - M[1] * M[3]) * id;
+
+// Step 2, AdditiveGaussianVoxel::append / finalize as vgicp_fold_kernel, one lane per occupied voxel, its points in `order`
+__global__ void __launch_bounds__(256) vgicp_fold_rows_kernel(const Slot* __restrict__ table, uint32_t table_cap, const uint32_t* __restrict__ order,
+                                                              const float4* __restrict__ grid0, uint32_t n, const double* __restrict__ tcov,
+                                                              VgicpVoxel* __restrict__ vox) {
+    const uint32_t h = blockIdx.x * 256u + threadIdx.x;
+    if (h >= table_cap) return;
+    const Slot s = table[h];
+    if (s.key == kEmptyKey || s.cnt == 0) return;
+    double m[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
+    for (uint32_t j = 0; j < s.cnt; j++) {
+        if ((unsigned long long)s.ptr + j >= n) break;
+        const uint32_t i = order[s.ptr + j];
+        if (i >= n) continue;
+        const float4 p = grid0[i];
+        m[0] += (double)p.x; m[1] += (double)p.y; m[2] += (double)p.z;
+        const double* pc = tcov + (size_t)i * 6;
+#pragma unroll
+        for (int a = 0; a < 6; a++) c[a] += pc[a];
+    }
+    const double nn = (double)s.cnt;
+    VgicpVoxel v;
+    for (int a = 0; a < 3; a++) v.mean[a] = m[a] / nn;
+    for (int a = 0; a < 6; a++) v.cov[a] = c[a] / nn;
+    v.n = nn;
+    vox[h] = v;
 }
+
 
 // update_correspondences (:72-116): one lane per (source point, neighbour offset)
 __global__ void __launch_bounds__(kGicpThreads) vgicp_corr_kernel(const Slot* __restrict__ vtable, uint32_t vmask, const VgicpVoxel* __restrict__ vox, double vres,
@@ -404,10 +400,26 @@ __global__ void __launch_bounds__(kGicpThreads) vgicp_cost_kernel(const VgicpVox
     }
 }
 
-struct GicpReport {
-    double acc[kGicpAcc];
-    uint32_t seq, pad;
-};
+
+// covariances in the order of a grid built from stamped points (pool[j].w = the row the point had)
+__global__ void __launch_bounds__(256) gicp_gather_cov_kernel(const float4* __restrict__ pool, uint32_t n, const double* __restrict__ in, double* __restrict__ out) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = __float_as_uint(pool[j].w);
+    if (i >= n) return;  // cannot be: the stamps are vgicp_stamp_kernel's for the same n, each row once; the test keeps a damaged pool in bounds
+#pragma unroll
+    for (int a = 0; a < 6; a++) out[(size_t)j * 6 + a] = in[(size_t)i * 6 + a];
+}
+
+// ... and back: covariances computed in the grid's order into the rows the points came with
+__global__ void __launch_bounds__(256) gicp_scatter_cov_kernel(const float4* __restrict__ pool, uint32_t n, const double* __restrict__ in, double* __restrict__ out) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = __float_as_uint(pool[j].w);
+    if (i >= n) return;  // (as above)
+#pragma unroll
+    for (int a = 0; a < 6; a++) out[(size_t)i * 6 + a] = in[(size_t)j * 6 + a];
+}
 
 __global__ void __launch_bounds__(1024) gicp_report_kernel(const double* __restrict__ partial, uint32_t nb, GicpReport* __restrict__ out, uint32_t seq) {
     __shared__ double acc[kGicpAcc];
@@ -429,34 +441,7 @@ __global__ void __launch_bounds__(1024) gicp_report_kernel(const double* __restr
 
 using namespace lio;
 
-struct lio_gicp {
-    int device = 0;
-    float res = 1.0f;
-    int k = 20;
-    uint32_t max_points = 0;
-    lio_map* grid[2] = {nullptr, nullptr};  // 0 target, 1 source: hash grids holding the clouds
-    uint32_t n[2] = {0, 0};
-    double* cov[2] = {nullptr, nullptr};
-    int32_t* corr = nullptr;
-    double* maha = nullptr;
-    double* partial = nullptr;
-    GicpReport* report = nullptr;
-    GicpReport* report_dev = nullptr;
-    uint32_t seq = 0;
-    float4* stage = nullptr;
-    // voxelised variant (FastVGICP): off while voxel_res == 0
-    double voxel_res = 0.0;
-    VgicpOffsets offs;
-    lio_map* vmap = nullptr;       // the target's Gaussian voxels: hash grid keyed as fast_vgicp_voxel.hpp does
-    VgicpVoxel* vvox = nullptr;    // one record per table slot
-    bool vmap_valid = false;
-    int32_t* vcorr = nullptr;      // [n_src x offsets]
-    double* vmaha = nullptr;
-    double* vpartial = nullptr;
-    uint32_t vblocks = 0;
-};
-
-namespace {
+namespace lio {
 
 GicpXform to_gx(const double T[16]) {
     GicpXform x;
@@ -489,6 +474,7 @@ int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
     int rc = lio_map_insert_device(m, g->stage, n, 0.0);
     if (rc != LIO_OK) return rc;
     g->n[which] = n;
+    g->rows[which] = false;
     if (which == 0) g->vmap_valid = false;
     hipLaunchKernelGGL(gicp_cov_kernel, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which]);
     LIO_HIP_TRY(hipGetLastError());
@@ -517,13 +503,97 @@ int vgicp_build(lio_gicp* g) {
     LIO_HIP_TRY(hipStreamSynchronize(st));
     const int rc = lio_map_insert_device(g->vmap, g->stage, n, 0.0);
     if (rc != LIO_OK) return rc;
-    hipLaunchKernelGGL(vgicp_fold_kernel, (g->vmap->table_cap + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->table_cap, g->vmap->pool, g->cov[0],
-                       g->vvox);
+    if (g->rows[0]) {
+        if (!g->vorder) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->vorder), (size_t)g->max_points * sizeof(uint32_t)));
+        LIO_HIP_TRY(hipMemsetAsync(g->vorder, 0xFF, (size_t)n * sizeof(uint32_t), g->vmap->stream));
+        hipLaunchKernelGGL(vgicp_rank_rows_kernel, (n + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->slot_of_point, g->vmap->pool, mt->pool, n, g->vorder);
+        hipLaunchKernelGGL(vgicp_fold_rows_kernel, (g->vmap->table_cap + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->table_cap, g->vorder, mt->pool, n,
+                           g->cov[0], g->vvox);
+    }
+    else
+        hipLaunchKernelGGL(vgicp_fold_kernel, (g->vmap->table_cap + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->table_cap, g->vmap->pool, g->cov[0],
+                           g->vvox);
     LIO_HIP_TRY(hipGetLastError());
     LIO_HIP_TRY(hipStreamSynchronize(g->vmap->stream));
     g->vmap_valid = true;
     return LIO_OK;
 }
+
+// the grid of one side, empty
+static int gicp_empty_grid(lio_gicp* g, int which) {
+    if (!g->grid[which]) {
+        g->grid[which] = map_create_mode(g->device, g->res, g->max_points, g->max_points, 1, 1);
+        return g->grid[which] ? LIO_OK : LIO_E_DEVICE;
+    }
+    return map_clear(g->grid[which]);
+}
+
+static int gicp_check_cloud(lio_gicp* g, int which, const void* d_pts, const void* d_cov6, uint32_t n) {
+    if (!g || !d_pts || !d_cov6 || which < 0 || which > 1) return LIO_E_INVALID;
+    if (n > g->max_points) { set_error("lio_gicp: cloud of %u points exceeds max_points %u", n, g->max_points); return LIO_E_CAPACITY; }
+    if ((int)n < g->k) { set_error("lio_gicp: a cloud needs at least k = %d points", g->k); return LIO_E_INVALID; }
+    return LIO_OK;
+}
+
+// A device cloud through gicp_set_cloud's path (grid, gicp_cov_kernel), stamped with its rows first: the covariances are also handed back in
+// the cloud's own order.  The grid's copy carries the row where the intensity was, which no kernel of this file reads as an intensity.
+int gicp_cloud_covariances(lio_gicp* g, int which, const float4* d_pts, uint32_t n, double* d_cov6_rows) {
+    int rc = gicp_check_cloud(g, which, d_pts, d_cov6_rows, n);
+    if (rc != LIO_OK) return rc;
+    hipSetDevice(g->device);
+    rc = gicp_empty_grid(g, which);
+    if (rc != LIO_OK) return rc;
+    lio_map* m = g->grid[which];
+    hipStream_t st = m->stream;
+    hipLaunchKernelGGL(vgicp_stamp_kernel, (n + 255) / 256, 256, 0, st, d_pts, g->stage, n);
+    LIO_HIP_TRY(hipGetLastError());
+    rc = lio_map_insert_device(m, g->stage, n, 0.0);
+    if (rc != LIO_OK) return rc;
+    g->n[which] = n;
+    g->rows[which] = true;
+    if (which == 0) g->vmap_valid = false;
+    hipLaunchKernelGGL(gicp_cov_kernel, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which]);
+    hipLaunchKernelGGL(gicp_scatter_cov_kernel, (n + 255) / 256, 256, 0, st, m->pool, n, g->cov[which], d_cov6_rows);
+    LIO_HIP_TRY(hipGetLastError());
+    LIO_HIP_TRY(hipStreamSynchronize(st));
+    return LIO_OK;
+}
+
+// A cloud that comes with its covariances (the loop detector's key-frame bank keeps both).  Target: stamped with its rows, laid out by the grid,
+// the covariances gathered into the grid's order.  Source: the cost kernels read a source row by row and never search it, and their sums run in
+// that order, so it is copied as it stands -- no grid, and the same order every time.
+int gicp_adopt_cloud(lio_gicp* g, int which, const float4* d_pts, const double* d_cov6, uint32_t n) {
+    int rc = gicp_check_cloud(g, which, d_pts, d_cov6, n);
+    if (rc != LIO_OK) return rc;
+    hipSetDevice(g->device);
+    rc = gicp_empty_grid(g, which);
+    if (rc != LIO_OK) return rc;
+    lio_map* m = g->grid[which];
+    hipStream_t st = m->stream;
+    if (which == 1) {
+        LIO_HIP_TRY(hipMemcpyAsync(m->pool, d_pts, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, st));
+        LIO_HIP_TRY(hipMemcpyAsync(g->cov[1], d_cov6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        g->n[1] = n;
+        g->rows[1] = false;
+        LIO_HIP_TRY(hipStreamSynchronize(st));
+        return LIO_OK;
+    }
+    hipLaunchKernelGGL(vgicp_stamp_kernel, (n + 255) / 256, 256, 0, st, d_pts, g->stage, n);
+    LIO_HIP_TRY(hipGetLastError());
+    rc = lio_map_insert_device(m, g->stage, n, 0.0);
+    if (rc != LIO_OK) return rc;
+    g->n[0] = n;
+    g->rows[0] = true;
+    g->vmap_valid = false;
+    hipLaunchKernelGGL(gicp_gather_cov_kernel, (n + 255) / 256, 256, 0, st, m->pool, n, d_cov6, g->cov[0]);
+    LIO_HIP_TRY(hipGetLastError());
+    LIO_HIP_TRY(hipStreamSynchronize(st));
+    return LIO_OK;
+}
+
+}  // namespace lio
+
+namespace {
 
 int gicp_eval(lio_gicp* g, const double T[16], double max_corr_dist, bool update, bool deriv, double* H, double* b, double* err, uint32_t* n_corr) {
     if (!g->grid[0] || !g->grid[1]) { set_error("lio_gicp: set target and source first"); return LIO_E_STATE; }
@@ -616,6 +686,7 @@ void lio_gicp_destroy(lio_gicp* g) {
     }
     if (g->vmap) lio_map_destroy(g->vmap);
     if (g->vvox) hipFree(g->vvox);
+    if (g->vorder) hipFree(g->vorder);
     if (g->vcorr) hipFree(g->vcorr);
     if (g->vmaha) hipFree(g->vmaha);
     if (g->vpartial) hipFree(g->vpartial);

@@ -183,6 +183,13 @@ struct Slam {
     std::vector<float> kf_points;       // the T_static-transformed cloud and stamps of the frame in flight
     std::vector<uint32_t> kf_stamps;
     Mat4 last_odom_start = Mat4::identity(), last_odom_end = Mat4::identity();  // the odometry pair of the last process() call
+    // loop detection over the key frames update_odom() hands out (hdl_graph_slam::LoopDetector, lio_loop_*): off unless
+    // set_loop_detection(true) / LSD_AMD_LOOP=1; guarded by kf_mtx
+    bool loop_detection = false;
+    lio_loop* loop = nullptr;
+    lio_loop_params loop_par;
+    std::atomic<bool> loop_detected{false};  // graph_loop_detected: sticky; read by get_graph_status() without the mutex
+    std::vector<lio_loop_edge> loop_edges;
 };
 std::unique_ptr<Slam> g;  // one global instance per process, like the reference's slam_ptr (slam_wrapper.cpp:4)
 
@@ -524,6 +531,10 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
     g->key_frame_range = frame_range;
     const char* kf_env = std::getenv("LSD_AMD_KEYFRAMES");
     g->keyframe_output = kf_env && kf_env[0] == '1';
+    lio_loop_default_params(&g->loop_par);
+    const char* loop_env = std::getenv("LSD_AMD_LOOP");
+    g->loop_detection = loop_env && loop_env[0] == '1';
+    if (g->loop_detection) g->keyframe_output = true;  // the detector consumes the key frames
     std::vector<std::string> in;
     for (auto h : sensor_input) in.push_back(py::cast<std::string>(h));
     if (localization) {
@@ -591,6 +602,7 @@ void deinit_slam() {
     if (g->running.exchange(false) && g->lio_thread.joinable()) g->lio_thread.join();
     if (g->engine) lio_engine_destroy(g->engine);
     if (g->keyframer) lio_keyframer_destroy(g->keyframer);
+    if (g->loop) lio_loop_destroy(g->loop);
     g->loc.reset(nullptr);
     g.reset(nullptr);
 }
@@ -880,27 +892,63 @@ py::list get_estimate_pose(double x0, double y0, double x1, double y1) {
 void set_destination(bool enable, std::string dest, int port) { (void)enable; if (g) { g->dest = dest; g->dest_port = port; } }
 // update_odom (slam_wrapper.cpp:105-130): the key frames cloud_callback elected since the last call, as keyframe_to_pydict's entries (:114-125:
 // points N x 4 f32 with the intensity as stored, image {}, pose 4 x 4, stamp); "odoms" stays empty without a pose graph (odom -> map is the identity)
+// Lock order: kf_mtx is only ever taken with the GIL RELEASED (process() does so too).  A thread that waited for the mutex while it held the GIL
+// would keep the GIL from the thread that holds the mutex and needs the GIL back: every entry below releases first, locks second, and builds its
+// Python objects after the mutex is free again.
 py::dict update_odom() {
+    struct Popped {
+        std::vector<float> pts;
+        int64_t n = 0;
+        Mat4 pose;
+        uint64_t stamp = 0;
+    };
+    std::vector<Popped> popped;
+    if (g && g->keyframer) {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        bool banked = false;
+        while (lio_keyframer_pending(g->keyframer) > 0) {
+            popped.emplace_back();
+            Popped& f = popped.back();
+            f.n = -lio_keyframer_pop(g->keyframer, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+            f.pts.resize((size_t)(f.n > 0 ? f.n : 1) * 4);
+            double accum = 0;
+            require(lio_keyframer_pop(g->keyframer, f.pts.data(), (uint64_t)f.n, f.pose.m, &f.stamp, &accum, nullptr, nullptr) == f.n,
+                    "update_odom: key-frame pop failed");
+            if (g->loop_detection) {  // the key frame joins the detector's bank (new_keyframes); one with fewer than k points is left out (lio_last_warning)
+                if (!g->loop) {
+                    g->loop = lio_loop_create(0, &g->loop_par);
+                    require(g->loop != nullptr, "update_odom: lio_loop_create failed");
+                }
+                const int id = lio_loop_add_keyframe_host(g->loop, f.pts.data(), (uint32_t)f.n, f.pose.m, accum);
+                require(id >= 0 || id == LIO_E_INVALID, "update_odom: lio_loop_add_keyframe_host failed");
+                banked = banked || id >= 0;
+            }
+        }
+        if (banked) {  // LoopDetector::detect over the frames just queued (optimization_timer_callback, hdl_graph_slam_nodelet.cpp:588-623)
+            lio_loop_edge found[8];  // (more than 8 loops in one call come back as -(count), below every error code)
+            const int n_loops = lio_loop_detect(g->loop, found, 8);
+            require(n_loops >= 0 || n_loops < -8, "update_odom: lio_loop_detect failed");
+            const int total = -lio_loop_edges(g->loop, nullptr, 0);
+            if (total > 0) {
+                g->loop_edges.resize((size_t)total);
+                require(lio_loop_edges(g->loop, g->loop_edges.data(), (uint32_t)total) == total, "update_odom: lio_loop_edges failed");
+                g->loop_detected = true;
+            }
+        }
+    }
     py::dict d;
     d["odoms"] = py::dict();
     py::list frames;
-    if (g && g->keyframer) {
-        std::lock_guard<std::mutex> kl(g->kf_mtx);
-        while (lio_keyframer_pending(g->keyframer) > 0) {
-            const int64_t n = -lio_keyframer_pop(g->keyframer, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
-            py::array_t<float> pts({(py::ssize_t)n, (py::ssize_t)4});
-            float dummy[4];
-            Mat4 pose;
-            uint64_t stamp = 0;
-            require(lio_keyframer_pop(g->keyframer, n ? pts.mutable_data() : dummy, (uint64_t)n, pose.m, &stamp, nullptr, nullptr, nullptr) == n,
-                    "update_odom: key-frame pop failed");
-            py::dict f;
-            f["points"] = pts;
-            f["image"] = py::dict();
-            f["pose"] = mat4_to_numpy_f32(pose);
-            f["stamp"] = stamp;
-            frames.append(f);
-        }
+    for (const Popped& f : popped) {
+        py::array_t<float> pts({(py::ssize_t)f.n, (py::ssize_t)4});
+        if (f.n > 0) std::memcpy(pts.mutable_data(), f.pts.data(), (size_t)f.n * 4 * sizeof(float));
+        py::dict e;
+        e["points"] = pts;
+        e["image"] = py::dict();
+        e["pose"] = mat4_to_numpy_f32(f.pose);
+        e["stamp"] = f.stamp;
+        frames.append(e);
     }
     d["keyframes"] = frames;
     return d;
@@ -919,9 +967,70 @@ void set_keyframe_output(bool enable) {
     require((bool)g, "init_slam first");
     g->keyframe_output = enable;
 }
+// not in the reference's module: loop detection over the key frames (off by default; LSD_AMD_LOOP=1 at init_slam switches it on for an unchanged
+// slam.py).  It consumes the key frames, so it switches their output on too.
+void set_loop_detection(bool enable) {
+    require((bool)g, "init_slam first");
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    g->loop_detection = enable;
+    if (enable) g->keyframe_output = true;
+}
+// the LoopDetector's thresholds (loop_detector.hpp:42-61) by their names.  A detector that already holds key frames starts over with the new
+// values: its bank is gone and frame ids begin at 0 again, so the edges found so far, which name frames of the old bank, are dropped with it
+// (get_loop_edges() is empty until the new detector finds one); get_graph_status()["loop_detected"] stays as it is -- it is sticky.
+void set_loop_config(py::dict cfg) {
+    require((bool)g, "init_slam first");
+    const char* names[] = {"distance_thresh", "accum_distance_thresh", "distance_from_last_edge_thresh", "distance_new_keyframe_thresh",
+                           "distance_keyframe_thresh", "fitness_score_max_range", "fitness_score_thresh", "fine_max_corr_dist"};
+    constexpr int kKeys = (int)(sizeof(names) / sizeof(names[0]));
+    bool have[kKeys] = {};
+    double value[kKeys] = {};
+    for (auto item : cfg) {  // read with the GIL, applied below without it
+        const std::string k = py::cast<std::string>(item.first);
+        bool known = false;
+        for (int i = 0; i < kKeys; i++)
+            if (k == names[i]) { value[i] = py::cast<double>(item.second); have[i] = true; known = true; }
+        require(known, "set_loop_config: unknown key");
+    }
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    lio_loop_params& p = g->loop_par;
+    double* field[kKeys] = {&p.distance_thresh, &p.accum_distance_thresh, &p.distance_from_last_edge_thresh, &p.distance_new_keyframe_thresh,
+                            &p.distance_keyframe_thresh, &p.fitness_score_max_range, &p.fitness_score_thresh, &p.fine_max_corr_dist};
+    for (int i = 0; i < kKeys; i++)
+        if (have[i]) *field[i] = value[i];
+    if (g->loop) { lio_loop_destroy(g->loop); g->loop = nullptr; }
+    g->loop_edges.clear();
+}
+// the loop edges found so far: what the reference hands to add_se3_edge (key1 = the new frame, key2, the relative pose, the score's information matrix)
+py::list get_loop_edges() {
+    py::list out;
+    if (!g) return out;
+    std::vector<lio_loop_edge> edges;
+    {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        edges = g->loop_edges;
+    }
+    for (const lio_loop_edge& e : edges) {
+        py::dict d;
+        d["key1"] = e.key1;
+        d["key2"] = e.key2;
+        py::array_t<float> T({4, 4});
+        std::memcpy(T.mutable_data(), e.relative_pose, sizeof(e.relative_pose));
+        d["relative_pose"] = T;
+        d["score"] = e.score;
+        py::array_t<double> I({6, 6});
+        std::memcpy(I.mutable_data(), e.information, sizeof(e.information));
+        d["information"] = I;
+        out.append(d);
+    }
+    return out;
+}
 py::dict get_graph_status() {
     py::dict d;
-    d["loop_detected"] = false;
+    d["loop_detected"] = g ? g->loop_detected.load() : false;  // graph_loop_detected: stays true after the first loop
     return d;
 }
 py::array_t<double> get_map_origin() {
@@ -1670,6 +1779,9 @@ PYBIND11_MODULE(slam_wrapper, m) {
           py::arg("image_stream_dict"), py::arg("image_param"));
     m.def("save_render_cloud", &save_render_cloud, "save render cloud", py::arg("file"));
     m.def("set_keyframe_output", &set_keyframe_output, "key frames from process() through update_odom()", py::arg("enable"));
+    m.def("set_loop_detection", &set_loop_detection, "loop detection over the key frames update_odom() hands out", py::arg("enable"));
+    m.def("set_loop_config", &set_loop_config, "LoopDetector thresholds", py::arg("dict"));
+    m.def("get_loop_edges", &get_loop_edges, "loop edges found so far");
     m.def("_last_odometry", &_last_odometry);
     m.def("_engine_handle", &_engine_handle);
     m.def("_transform_from_rpyt", &_transform_from_rpyt);

@@ -55,6 +55,9 @@ SYMBOLS = [
     "lio_ndt_create", "lio_ndt_destroy", "lio_ndt_set_target", "lio_ndt_set_target_device", "lio_ndt_num_voxels", "lio_ndt_fitness_score", "lio_ndt_overlap_score", "lio_ndt_voxel_at",
     "lio_ndt_linearize", "lio_ndt_default_params", "lio_ndt_align", "lio_ndt_align_batch", "lio_ndt_enable_kernel_timing", "lio_ndt_kernel_times",
     "lio_gicp_create", "lio_gicp_destroy", "lio_gicp_set_target", "lio_gicp_set_source", "lio_gicp_set_voxel_mode", "lio_gicp_voxel_at", "lio_gicp_download", "lio_gicp_correspondences", "lio_gicp_linearize", "lio_gicp_align",
+    "lio_loop_default_params", "lio_loop_find_candidates", "lio_loop_information_matrix", "lio_loop_create", "lio_loop_destroy", "lio_loop_reset",
+    "lio_loop_add_keyframe_host", "lio_loop_set_pose", "lio_loop_num_keyframes", "lio_loop_download_keyframe", "lio_loop_detect", "lio_loop_edges",
+    "lio_loop_last_report", "lio_loop_last_times", "lio_loop_align_candidates", "lio_loop_align_fine",
 ]
 
 
@@ -119,6 +122,24 @@ class KeyframeReport(C.Structure):  # lio_keyframe_report
     _fields_ = [("first", C.c_int32), ("need", C.c_int32), ("must", C.c_int32), ("elected", C.c_int32), ("emitted", C.c_int32), ("nr", C.c_uint32),
                 ("n_downsampled", C.c_uint32), ("local_map_size", C.c_uint32), ("dx", C.c_double), ("da", C.c_double), ("score", C.c_double),
                 ("accum_distance", C.c_double), ("average_score", C.c_double)]
+
+
+class LoopParams(C.Structure):  # lio_loop_params
+    _fields_ = [("distance_thresh", C.c_double), ("accum_distance_thresh", C.c_double), ("distance_from_last_edge_thresh", C.c_double),
+                ("distance_new_keyframe_thresh", C.c_double), ("distance_keyframe_thresh", C.c_double), ("fitness_score_max_range", C.c_double),
+                ("fitness_score_thresh", C.c_double), ("fine_max_corr_dist", C.c_double), ("voxel_resolution", C.c_double),
+                ("coarse_translation_epsilon", C.c_double), ("coarse_rotation_epsilon_deg", C.c_double), ("fine_translation_epsilon", C.c_double),
+                ("fine_rotation_epsilon_deg", C.c_double), ("max_iterations", C.c_int32), ("k_correspondences", C.c_int32), ("grid_resolution", C.c_float),
+                ("max_points", C.c_uint32), ("max_candidates", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class LoopEdge(C.Structure):  # lio_loop_edge
+    _fields_ = [("key1", C.c_int32), ("key2", C.c_int32), ("relative_pose", C.c_float * 16), ("score", C.c_double), ("information", C.c_double * 36)]
+
+
+class LoopReport(C.Structure):  # lio_loop_report
+    _fields_ = [("new_id", C.c_int32), ("n_candidates", C.c_int32), ("best", C.c_int32), ("fine_converged", C.c_int32), ("fine_iterations", C.c_int32),
+                ("reason", C.c_int32), ("coarse_rounds", C.c_int32), ("pad", C.c_int32), ("best_score", C.c_double), ("fine_score", C.c_double)]
 
 
 class BevInfo(C.Structure):  # lio_bev_info
@@ -381,6 +402,23 @@ def lib():
     sig("lio_gicp_correspondences", cint, vp, i32p, u32)
     sig("lio_gicp_linearize", cint, vp, f64p, dbl, cint, cint, f64p, f64p, f64p, C.POINTER(u32))
     sig("lio_gicp_align", cint, vp, f64p, C.POINTER(NdtParams), dbl, f64p, C.POINTER(cint), C.POINTER(cint))
+    lp, le, lr = C.POINTER(LoopParams), C.POINTER(LoopEdge), C.POINTER(LoopReport)
+    sig("lio_loop_default_params", None, lp)
+    sig("lio_loop_find_candidates", cint, f64p, f64p, u32, dbl, f64p, dbl, lp, i32p, u32)
+    sig("lio_loop_information_matrix", cint, dbl, f64p)
+    sig("lio_loop_create", vp, cint, lp)
+    sig("lio_loop_destroy", None, vp)
+    sig("lio_loop_reset", cint, vp)
+    sig("lio_loop_add_keyframe_host", cint, vp, f32p, u32, f64p, dbl)
+    sig("lio_loop_set_pose", cint, vp, cint, f64p)
+    sig("lio_loop_num_keyframes", cint, vp, C.POINTER(cint))
+    sig("lio_loop_download_keyframe", cint, vp, cint, f32p, f64p, u32)
+    sig("lio_loop_detect", cint, vp, le, u32)
+    sig("lio_loop_edges", cint, vp, le, u32)
+    sig("lio_loop_last_report", cint, vp, lr, i32p, i32p, i32p, f64p, u32)
+    sig("lio_loop_last_times", cint, vp, f64p, f64p, f64p, f64p, f64p)
+    sig("lio_loop_align_candidates", cint, vp, cint, i32p, u32, f64p, f64p, i32p, i32p, f64p, C.POINTER(u32))
+    sig("lio_loop_align_fine", cint, vp, cint, cint, f64p, f64p, i32p, i32p, f64p, C.POINTER(u32))
     sig("lio_state_boxplus", None, f64p, f64p, f64p)
     sig("lio_state_boxminus", None, f64p, f64p, f64p)
     _lib = L

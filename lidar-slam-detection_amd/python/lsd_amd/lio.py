@@ -654,6 +654,133 @@ class Gicp:
         return out, bool(conv.value), int(it.value)
 
 
+class LoopDetector:
+    """hdl_graph_slam::LoopDetector on the device (lio_loop_*): a bank of key frames with their covariances, find_candidates, all candidates
+    aligned with FAST_VGICP in one batch (the LM loop on the device), nearest-neighbour fitness, FAST_GICP verification of the best.
+    Keyword arguments override lio_loop_params."""
+
+    REASONS = {0: "found", 1: "no_candidate", 2: "coarse_score", 3: "fine_not_converged", 4: "fine_score"}
+
+    def __init__(self, device=0, **params):
+        self.params = self.default_params()
+        for k, v in params.items():
+            if not hasattr(self.params, k):
+                raise TypeError(f"lio_loop_params has no field {k!r}")
+            setattr(self.params, k, v)
+        self.h = lib().lio_loop_create(device, C.byref(self.params))
+        if not self.h:
+            raise capi.LioError("lio_loop_create failed: " + lib().lio_last_error().decode())
+
+    @staticmethod
+    def default_params():
+        p = capi.LoopParams()
+        lib().lio_loop_default_params(C.byref(p))
+        return p
+
+    @staticmethod
+    def find_candidates(accum, pos_xy, new_accum, new_xy, last_edge_accum=0.0, params=None):
+        """find_candidates (loop_detector.hpp:106-140) on the host: indices of the candidate key frames"""
+        a, xy, nxy = f64(accum).ravel(), f64(pos_xy).reshape(-1, 2), f64(new_xy).ravel()
+        out = np.zeros(max(len(a), 1), np.int32)
+        n = check(lib().lio_loop_find_candidates(ptr(a, C.c_double), ptr(xy, C.c_double), len(a), float(new_accum), ptr(nxy, C.c_double), float(last_edge_accum),
+                                                 C.byref(params) if params is not None else None, ptr(out, C.c_int32), len(out)), "loop find_candidates")
+        return out[:n].copy()
+
+    @staticmethod
+    def information_matrix(fitness):
+        out = np.zeros((6, 6))
+        check(lib().lio_loop_information_matrix(float(fitness), ptr(out, C.c_double)), "loop information_matrix")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_loop_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        check(lib().lio_loop_reset(self.h), "loop reset")
+
+    def add_keyframe(self, pts, pose, accum_distance):
+        p, T = f32(pts).reshape(-1, 4), f64(pose).reshape(4, 4)
+        return check(lib().lio_loop_add_keyframe_host(self.h, ptr(p, C.c_float), len(p), ptr(T, C.c_double), float(accum_distance)), "loop add_keyframe")
+
+    def set_pose(self, kid, pose):
+        T = f64(pose).reshape(4, 4)
+        check(lib().lio_loop_set_pose(self.h, int(kid), ptr(T, C.c_double)), "loop set_pose")
+
+    def num_keyframes(self):
+        q = C.c_int(0)
+        n = check(lib().lio_loop_num_keyframes(self.h, C.byref(q)), "loop num_keyframes")
+        return n, q.value
+
+    def download_keyframe(self, kid):
+        """(points (n, 4) in the bank's order, regularised covariances (n, 3, 3))"""
+        n = -lib().lio_loop_download_keyframe(self.h, int(kid), None, None, 0)
+        if n <= 0:
+            raise capi.LioError(f"loop download_keyframe: no frame {kid}")
+        pts, cov = np.zeros((n, 4), np.float32), np.zeros((n, 6))
+        check(lib().lio_loop_download_keyframe(self.h, int(kid), ptr(pts, C.c_float), ptr(cov, C.c_double), n), "loop download_keyframe")
+        full = np.stack([cov[:, 0], cov[:, 1], cov[:, 2], cov[:, 1], cov[:, 3], cov[:, 4], cov[:, 2], cov[:, 4], cov[:, 5]], 1).reshape(n, 3, 3)
+        return pts, full
+
+    @staticmethod
+    def _edge(e):
+        return dict(key1=int(e.key1), key2=int(e.key2), relative_pose=np.array(e.relative_pose, np.float32).reshape(4, 4), score=float(e.score),
+                    information=np.array(e.information).reshape(6, 6))
+
+    def detect(self, cap=16):
+        """detect() over the queued key frames -> the loops of this call, each a dict key1, key2, relative_pose, score, information"""
+        buf = (capi.LoopEdge * cap)()
+        n = lib().lio_loop_detect(self.h, buf, cap)
+        if n < -cap:  # more loops than cap: they are the tail of edges()
+            return self.edges()[n:]
+        check(n, "loop detect")
+        return [self._edge(buf[i]) for i in range(n)]
+
+    def edges(self):
+        n = lib().lio_loop_edges(self.h, None, 0)
+        n = -n if n < 0 else n
+        if n == 0:
+            return []
+        buf = (capi.LoopEdge * n)()
+        check(lib().lio_loop_edges(self.h, buf, n), "loop edges")
+        return [self._edge(buf[i]) for i in range(n)]
+
+    def last_report(self):
+        rep = capi.LoopReport()
+        K = abs(lib().lio_loop_last_report(self.h, C.byref(rep), None, None, None, None, 0))
+        ids, conv, it, sc = np.zeros(max(K, 1), np.int32), np.zeros(max(K, 1), np.int32), np.zeros(max(K, 1), np.int32), np.zeros(max(K, 1))
+        check(lib().lio_loop_last_report(self.h, C.byref(rep), ptr(ids, C.c_int32), ptr(conv, C.c_int32), ptr(it, C.c_int32), ptr(sc, C.c_double), max(K, 1)), "loop last_report")
+        return dict(new_id=rep.new_id, candidates=ids[:K].copy(), converged=conv[:K].astype(bool), iterations=it[:K].copy(), scores=sc[:K].copy(), best=rep.best,
+                    best_score=rep.best_score, fine_converged=bool(rep.fine_converged), fine_iterations=rep.fine_iterations, fine_score=rep.fine_score,
+                    reason=self.REASONS.get(rep.reason, str(rep.reason)), coarse_rounds=rep.coarse_rounds)
+
+    def last_times(self):
+        v = [C.c_double(0) for _ in range(5)]
+        check(lib().lio_loop_last_times(self.h, *[C.byref(x) for x in v]), "loop last_times")
+        return dict(zip(("insert_us", "target_us", "coarse_us", "fitness_us", "fine_us"), [x.value for x in v]))
+
+    def align_candidates(self, target_id, source_ids, guesses):
+        """the coarse batch + fitness: per job (T (4, 4) f64, converged, iterations, score, nr)"""
+        ids = np.ascontiguousarray(source_ids, np.int32).ravel()
+        g = f64(guesses).reshape(-1, 4, 4)
+        n = len(ids)
+        assert len(g) == n
+        T, it, conv, sc, nr = np.zeros((max(n, 1), 4, 4)), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1)), np.zeros(max(n, 1), np.uint32)
+        check(lib().lio_loop_align_candidates(self.h, int(target_id), ptr(ids, C.c_int32), n, ptr(g, C.c_double), ptr(T, C.c_double), ptr(it, C.c_int32),
+                                              ptr(conv, C.c_int32), ptr(sc, C.c_double), ptr(nr, C.c_uint32)), "loop align_candidates")
+        return [(T[i].copy(), bool(conv[i]), int(it[i]), float(sc[i]), int(nr[i])) for i in range(n)]
+
+    def align_fine(self, target_id, source_id, guess):
+        g, T = f64(guess).reshape(4, 4), np.zeros((4, 4))
+        it, conv, sc, nr = C.c_int32(0), C.c_int32(0), C.c_double(0), C.c_uint32(0)
+        check(lib().lio_loop_align_fine(self.h, int(target_id), int(source_id), ptr(g, C.c_double), ptr(T, C.c_double), C.byref(it), C.byref(conv), C.byref(sc), C.byref(nr)),
+              "loop align_fine")
+        return T, bool(conv.value), int(it.value), sc.value, nr.value
+
+
 class Cloud:
     """lio_cloud: a device-resident cloud that grows over a drive, and pcl::VoxelGrid over all of it (the dense-map export of
     graph_utils.cpp:160-200, 410-446).  Appends transform (f64, as pcl::transformPointCloud with a Matrix4d), scale the intensity, keep an
