@@ -62,8 +62,10 @@ int lio_device_count(void);
  * 11 = lio_keyframe_* / lio_keyframer_* / lio_radius_outlier_host (the mapping mode's key frames: decision, fitness against a rolling local map,
  * election, radius outlier and range filters);
  * 12 = lio_loop_* (loop detection over the key frames: candidate search, batched FAST_VGICP with the LM loop on the device, nearest-neighbour
- * fitness, FAST_GICP verification, the loop edge with its information matrix). */
-#define LIO_ABI_VERSION 12
+ * fitness, FAST_GICP verification, the loop edge with its information matrix);
+ * 13 = lio_graph_* / lio_se3_* / lio_loop_pair_information (the pose graph: SE3 edges, Huber, Levenberg-Marquardt with a conjugate-gradient solve
+ * on the device; the information matrix of two bank frames under a relative pose). */
+#define LIO_ABI_VERSION 13
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1127,6 +1129,103 @@ int lio_loop_align_candidates(lio_loop*, int target_id, const int32_t* source_id
 /* stage door: the fine matcher (FAST_GICP at fine_max_corr_dist) and its fitness for one pair of bank frames */
 int lio_loop_align_fine(lio_loop*, int target_id, int source_id, const double guess[16], double out_T[16], int32_t* iterations, int32_t* converged, double* score,
                         uint32_t* nr);
+
+/* the fitness score and information matrix of two bank frames under a given relative pose: InformationMatrixCalculator::calc_information_matrix(
+ * cloud1, cloud2, relpose) (information_matrix_calculator.cpp:25-47, 71-102).  Frame id2 is transformed by relpose.cast<float>() against frame id1's
+ * exact nearest neighbours; max_range = DBL_MAX, so every point with a neighbour counts; sums and ties by the fitness rules above; the score
+ * then goes through lio_loop_information_matrix.  score, nr, info36 may be NULL */
+int lio_loop_pair_information(lio_loop*, int id1, int id2, const double relpose[16], double* score, uint32_t* nr, double info36[36]);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * The pose graph on the device (csrc/graph.hip): what hdl_graph_slam's GraphSLAM does with g2o for SE3 pose nodes and EdgeSE3 edges
+ * (graph_slam.cpp:344-375, solver "lm_var").  g2o is not in the reference tree: THE RULES BELOW ARE RESTATED FROM g2o'S PUBLISHED SOURCE
+ * (types/slam3d/isometry3d_mappings, edge_se3, core/robust_kernel_impl, core/optimization_algorithm_levenberg) and are pinned to an f64 numpy
+ * restatement (tests/graph_cases.py), not to a compiled reference.  GNSS, floor-plane and IMU edges, the DCS2 kernel and the
+ * robust_graph_optimize modes are out of scope.  NULL from lio_graph_create without a device: there is no CPU fallback.
+ *   state       a node is an f64 translation, a unit quaternion and a fixed flag; an edge is from, to, a measurement M (given as a row-major
+ *               4 x 4, kept as translation + quaternion), an f64 6 x 6 information matrix, a kernel and its delta.  Ids count from 0 in creation
+ *               order and are never reused; a removed edge takes no part.
+ *   error       e = toVectorMQT(M^-1 X_from^-1 X_to): the translation, then x, y, z of the normalised quaternion, its sign chosen so that w >= 0.
+ *   update      X <- X fromVectorMQT(d): t += R d[0:3]; q <- q (d[3:6], w), w = sqrt(1 - |d_q|^2); the identity rotation when 1 - |d_q|^2 < 0.
+ *               THE PROJECT'S RULE: the rotation is kept as a quaternion and renormalised after every update (g2o keeps a matrix and
+ *               orthogonalises it every 1000 updates).
+ *   cost        chi2_e = e^T Omega e.  Huber: sqrt(chi2_e) <= delta: rho = chi2_e, rho' = 1; otherwise rho = 2 delta sqrt(chi2_e) - delta^2,
+ *               rho' = delta / sqrt(chi2_e).  The quadratic form uses rho' Omega with no second-order term: b += -J^T (rho' Omega) e,
+ *               H += J^T (rho' Omega) J.  The graph's chi2 is the sum of rho over the live edges.
+ *   Jacobians   analytic: the derivative of e with respect to the two nodes' d at 0.
+ *   active set  a fixed node contributes no unknowns; a node with no live edge is left out of the solve and keeps its estimate.
+ *   LM          OptimizationAlgorithmLevenberg: lambda_0 = 1e-5 max diag(H), nu = 2.  A trial solves (H + lambda I) d = b, applies the update and
+ *               re-evaluates chi2; rho = (chi2_old - chi2_new) / (d^T (lambda d + b) + 1e-3).  Accepted (rho > 0, chi2_new finite): lambda *=
+ *               max(1/3, min(2/3, 1 - (2 rho - 1)^3)), nu = 2.  Rejected: the estimates are restored, lambda *= nu, nu *= 2.  An iteration takes
+ *               trials while rho < 0, at most 10.  The optimisation stops after max_iterations, after an iteration whose tenth trial was
+ *               reached, on rho = 0, or on a non-finite lambda; every iteration begun counts in the return value.  THE PROJECT'S OWN stop rule,
+ *               off by default: chi2_rel_stop > 0 stops after an accepted step that lowers chi2 by no more than that fraction of it.
+ *   solve       THE PROJECT'S RULE: g2o factorises (CHOLMOD); this runs conjugate gradients in f64, preconditioned by the inverse of every
+ *               node's damped 6 x 6 diagonal block, until |r| <= cg_epsilon |b| or cg_max_iterations (0: 12 x active nodes).  An inexact step is
+ *               still safe: the rho test judges it.  The iterations and the final relative residual are in the report.
+ *   sums        every block of H (one diagonal block per active node, one off-diagonal block per distinct pair) and of b is the sum of its
+ *               edges' contributions in rising edge id; chi2 is summed per 256 consecutive edges and then over those records in order; the
+ *               dot products of the solve are folded in a fixed order.  No floating-point atomics: two runs give the same bits.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_graph lio_graph;
+#define LIO_GRAPH_KERNEL_NONE 0
+#define LIO_GRAPH_KERNEL_HUBER 1
+#define LIO_GRAPH_STOP_MAX_ITERATIONS 1
+#define LIO_GRAPH_STOP_TRIALS 2          /* the tenth trial of an iteration was reached */
+#define LIO_GRAPH_STOP_RHO_ZERO 3
+#define LIO_GRAPH_STOP_LAMBDA 4          /* lambda is no longer finite */
+#define LIO_GRAPH_STOP_CHI2_REL 5        /* chi2_rel_stop */
+typedef struct lio_graph_params {
+    double cg_epsilon;          /* 1e-10 */
+    double chi2_rel_stop;       /* 0: off */
+    int32_t min_edges;          /* 10 (graph_slam.cpp:346) */
+    int32_t cg_max_iterations;  /* 0: 12 x the number of active nodes */
+} lio_graph_params;
+typedef struct lio_graph_report {
+    int32_t iterations;           /* LM iterations run */
+    int32_t stop_reason;          /* LIO_GRAPH_STOP_*; 0: nothing to do */
+    int32_t trials, accepted;     /* trials in all; those accepted */
+    int32_t n_active, n_live_edges;
+    int32_t cg_iterations;        /* of the last solve */
+    int32_t cg_iterations_total;
+    double chi2_initial, chi2_final, lambda;
+    double cg_residual;           /* |r| / |b| at the end of the last solve */
+} lio_graph_report;
+void lio_graph_default_params(lio_graph_params*);
+/* params NULL = the defaults */
+lio_graph* lio_graph_create(int device, const lio_graph_params* params);
+void lio_graph_destroy(lio_graph*);
+/* no nodes, no edges; memory is kept */
+int lio_graph_reset(lio_graph*);
+/* poses are row-major 4 x 4 f64; the rotation goes through Eigen's matrix -> quaternion conversion and is normalised.  The id */
+int lio_graph_add_node(lio_graph*, const double pose16[16]);
+int lio_graph_set_fixed(lio_graph*, int id, int flag);
+int lio_graph_set_estimate(lio_graph*, int id, const double pose16[16]);
+int lio_graph_num_nodes(lio_graph*);
+/* the fixed flags of all nodes; the count, or -(count) when cap is too small */
+int lio_graph_get_fixed(lio_graph*, uint8_t* out, uint32_t cap);
+/* the id; LIO_E_INVALID for from == to, an unknown node or kernel, Huber with delta <= 0, or an information matrix that is not finite or not
+ * symmetric to 1e-9 of its largest entry */
+int lio_graph_add_edge(lio_graph*, int from, int to, const double M16[16], const double info36[36], int kernel, double delta);
+int lio_graph_remove_edge(lio_graph*, int id);
+/* the iterations run; -1 with nothing touched when fewer than min_edges live edges exist (GraphSLAM::optimize); other negative values are
+ * LIO_E_* (a NULL handle is LIO_E_INVALID = -1 as well).  report may be NULL */
+int lio_graph_optimize(lio_graph*, int max_iterations, lio_graph_report* report);
+/* all estimates as row-major 4 x 4 (cap in nodes); the count, or -(count) when cap is too small */
+int lio_graph_estimates(lio_graph*, double* out16, uint32_t cap);
+/* the live edges in rising id (any array may be NULL); the count, or -(count) when cap is too small */
+int lio_graph_edges(lio_graph*, int32_t* from, int32_t* to, int32_t* id, uint32_t cap);
+int lio_graph_chi2(lio_graph*, double* chi2);
+/* stage door: one linearisation at the current estimate, no step taken.  Per edge id (removed edges: zeros) the error, chi2_e and rho'; per node
+ * id (fixed or unconnected nodes: zeros) b and the diagonal block of H.  Any output may be NULL; the number of edge ids, LIO_E_CAPACITY when a
+ * cap is too small */
+int lio_graph_linearize(lio_graph*, double* errors, double* chi2, double* rho1, uint32_t edge_cap, double* b, double* Hdiag, uint32_t node_cap);
+/* device time (HIP events) of the last lio_graph_optimize in us: linearise, assemble, solve, update (update + chi2 + the LM bookkeeping) */
+int lio_graph_last_times(lio_graph*, double* linearize_us, double* assemble_us, double* solve_us, double* update_us);
+/* host only (no device needed): g2o's fromVectorMQT / toVectorMQT on row-major 4 x 4, and the edge error of three poses */
+void lio_se3_from_mqt(const double v6[6], double T16[16]);
+void lio_se3_to_mqt(const double T16[16], double v6[6]);
+int lio_graph_edge_error(const double Xfrom16[16], const double Xto16[16], const double M16[16], double e6[6]);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

@@ -410,8 +410,9 @@ int prepare_target(lio_loop* h, int id) {
     return LIO_OK;
 }
 
-// getFitnessScore of n (source frame, f64 transform) pairs against the prepared target: one launch (per max_candidates pairs)
-int fitness_batch(lio_loop* h, const int32_t* src_ids, const double* T16, uint32_t n, double* score, uint32_t* nr) {
+// getFitnessScore of n (source frame, f64 transform) pairs against the prepared target: one launch (per max_candidates pairs); max_range < 0: the
+// detector's fitness_score_max_range
+int fitness_batch(lio_loop* h, const int32_t* src_ids, const double* T16, uint32_t n, double* score, uint32_t* nr, double max_range = -1.0) {
     const Frame& tgt = h->frames[h->target_id];
     for (uint32_t base = 0; base < n; base += h->par.max_candidates) {
         const uint32_t B = n - base < h->par.max_candidates ? n - base : h->par.max_candidates;
@@ -431,7 +432,7 @@ int fitness_batch(lio_loop* h, const int32_t* src_ids, const double* T16, uint32
         LIO_HIP_TRY(hipMemcpyAsync(h->d_fit, h->h_fit, sizeof(FitSlot) * B, hipMemcpyHostToDevice, h->st));
         LIO_HIP_TRY(hipMemcpyAsync(h->d_tab, h->h_tab, sizeof(uint2) * b, hipMemcpyHostToDevice, h->st));
         hipLaunchKernelGGL(loop_fitness, b, kFitThreads, 0, h->st, h->d_tab, h->d_fit, h->index.leaves, h->index.nodes, tgt.n, h->index.P, h->index.L,
-                           h->par.fitness_score_max_range, h->d_fitp);
+                           max_range < 0 ? h->par.fitness_score_max_range : max_range, h->d_fitp);
         LIO_HIP_TRY(hipGetLastError());
         LIO_HIP_TRY(hipMemcpyAsync(h->h_fitp, h->d_fitp, sizeof(double) * 2 * b, hipMemcpyDeviceToHost, h->st));
         LIO_HIP_TRY(hipStreamSynchronize(h->st));
@@ -903,6 +904,22 @@ int lio_loop_align_fine(lio_loop* h, int target_id, int source_id, const double 
     if (converged) *converged = fo.converged;
     if (score) *score = fo.score;
     if (nr) *nr = fo.nr;
+    return LIO_OK;
+}
+
+int lio_loop_pair_information(lio_loop* h, int id1, int id2, const double relpose[16], double* score, uint32_t* nr, double info36[36]) {
+    if (!id_ok(h, id1) || !id_ok(h, id2) || !relpose) return LIO_E_INVALID;
+    hipSetDevice(h->device);
+    int rc = prepare_target(h, id1);
+    if (rc != LIO_OK) return rc;
+    const int32_t sid = id2;
+    double sc = DBL_MAX;
+    uint32_t n = 0;
+    rc = fitness_batch(h, &sid, relpose, 1, &sc, &n, DBL_MAX);  // calc_fitness_score's max_range = std::numeric_limits<double>::max()
+    if (rc != LIO_OK) return rc;
+    if (score) *score = sc;
+    if (nr) *nr = n;
+    if (info36) return lio_loop_information_matrix(sc, info36);
     return LIO_OK;
 }
 

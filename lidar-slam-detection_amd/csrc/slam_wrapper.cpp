@@ -190,6 +190,17 @@ struct Slam {
     lio_loop_params loop_par;
     std::atomic<bool> loop_detected{false};  // graph_loop_detected: sticky; read by get_graph_status() without the mutex
     std::vector<lio_loop_edge> loop_edges;
+    // the pose graph over the key frames (hdl_graph_slam_nodelet.cpp:293-334, 600-651; lio_graph_*): off unless set_pose_graph(true) /
+    // LSD_AMD_GRAPH=1; guarded by kf_mtx.  Key frame k is node k of the graph and frame k of the detector's bank.
+    bool pose_graph = false;
+    lio_graph* graph = nullptr;
+    std::vector<Mat4> graph_odom;         // keyframe->odom of every key frame in the graph
+    std::vector<Mat4> graph_pose;         // keyframe->node->estimate() after the last optimisation
+    Mat4 odom2map = Mat4::identity();     // trans_odom2map (the values of a Matrix4f)
+    bool graph_updated = false;
+    size_t graph_loops = 0;               // loop edges of loop_edges already in the graph
+    struct InjectedKeyFrame { std::vector<float> pts; Mat4 pose; uint64_t stamp; double accum; };
+    std::deque<InjectedKeyFrame> injected;  // test visibility: key frames handed to update_odom() without the front end (_push_keyframe)
 };
 std::unique_ptr<Slam> g;  // one global instance per process, like the reference's slam_ptr (slam_wrapper.cpp:4)
 
@@ -534,6 +545,9 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
     lio_loop_default_params(&g->loop_par);
     const char* loop_env = std::getenv("LSD_AMD_LOOP");
     g->loop_detection = loop_env && loop_env[0] == '1';
+    const char* graph_env = std::getenv("LSD_AMD_GRAPH");
+    g->pose_graph = graph_env && graph_env[0] == '1';
+    if (g->pose_graph) g->loop_detection = true;       // the graph consumes the loops
     if (g->loop_detection) g->keyframe_output = true;  // the detector consumes the key frames
     std::vector<std::string> in;
     for (auto h : sensor_input) in.push_back(py::cast<std::string>(h));
@@ -603,6 +617,7 @@ void deinit_slam() {
     if (g->engine) lio_engine_destroy(g->engine);
     if (g->keyframer) lio_keyframer_destroy(g->keyframer);
     if (g->loop) lio_loop_destroy(g->loop);
+    if (g->graph) lio_graph_destroy(g->graph);
     g->loc.reset(nullptr);
     g.reset(nullptr);
 }
@@ -821,6 +836,10 @@ py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, 
             require(lio_keyframer_push_host(s->keyframer, s->kf_points.data(), s->kf_stamps.data(), n, header_stamp, out_pose.m, delta.m, nullptr, nullptr, 0,
                                             nullptr) == LIO_OK, "process: key-frame push failed");
         }
+        if (got && s->pose_graph) {  // HDL_FastLIO::getPose: get_odom2map() * odom.first (the key frame above carries the odometry itself)
+            std::lock_guard<std::mutex> kl(s->kf_mtx);
+            out_pose = mul(s->odom2map, out_pose);
+        }
     }
     // SLAM::run, mapping branch (slam.cpp:344-364)
     double heading, pitch, roll;
@@ -890,6 +909,34 @@ py::list get_estimate_pose(double x0, double y0, double x1, double y1) {
     return py::cast(std::vector<double>{0, 0, 0, 0, 0, 0, 0});  // x, y, z, roll, pitch, -yaw, result (0 = no estimate)
 }
 void set_destination(bool enable, std::string dest, int port) { (void)enable; if (g) { g->dest = dest; g->dest_port = port; } }
+// GraphSLAM::optimize(1024) and what optimization_timer_callback does with the result (hdl_graph_slam_nodelet.cpp:634-651): the estimates, trans_odom2map
+// = last.node * last.odom^-1 through a Matrix4f, and the detector's poses.  kf_mtx is held.  false: the optimisation did not run (fewer than 10 edges)
+bool graph_optimize_locked(Slam* s, const char* who) {
+    (void)who;
+    if (!s->graph || s->graph_odom.empty()) return false;
+    const int it = lio_graph_optimize(s->graph, 1024, nullptr);
+    require(it >= -1, "lio_graph_optimize failed");
+    const size_t n = s->graph_odom.size();
+    std::vector<double> est(16 * n);
+    require(lio_graph_estimates(s->graph, est.data(), (uint32_t)n) == (int)n, "lio_graph_estimates failed");
+    for (size_t k = 0; k < n; k++) {
+        std::memcpy(s->graph_pose[k].m, &est[16 * k], sizeof(double) * 16);
+        if (s->loop) require(lio_loop_set_pose(s->loop, (int)k, s->graph_pose[k].m) == LIO_OK, "lio_loop_set_pose failed");
+    }
+    const Mat4 trans = mul(s->graph_pose[n - 1], rigid_inverse(s->graph_odom[n - 1]));
+    for (int k = 0; k < 16; k++) s->odom2map.m[k] = (double)(float)trans.m[k];
+    return it >= 0;
+}
+// map_to_pydict (py_utils.cpp:50-56): str(id) -> 4 x 4 f64
+py::dict odoms_to_pydict(const std::vector<std::pair<int, Mat4>>& odoms) {
+    py::dict d;
+    for (const auto& o : odoms) {
+        py::array_t<double> a({4, 4});
+        std::memcpy(a.mutable_data(), o.second.m, sizeof(double) * 16);
+        d[std::to_string(o.first).c_str()] = a;
+    }
+    return d;
+}
 // update_odom (slam_wrapper.cpp:105-130): the key frames cloud_callback elected since the last call, as keyframe_to_pydict's entries (:114-125:
 // points N x 4 f32 with the intensity as stored, image {}, pose 4 x 4, stamp); "odoms" stays empty without a pose graph (odom -> map is the identity)
 // Lock order: kf_mtx is only ever taken with the GIL RELEASED (process() does so too).  A thread that waited for the mutex while it held the GIL
@@ -903,19 +950,56 @@ py::dict update_odom() {
         uint64_t stamp = 0;
     };
     std::vector<Popped> popped;
-    if (g && g->keyframer) {
+    std::vector<std::pair<int, Mat4>> odoms;
+    if (g && (g->keyframer || !g->injected.empty())) {
         py::gil_scoped_release rel;
         std::lock_guard<std::mutex> kl(g->kf_mtx);
         bool banked = false;
-        while (lio_keyframer_pending(g->keyframer) > 0) {
+        const bool graph_on = g->pose_graph && g->loop_detection;
+        while ((g->keyframer && lio_keyframer_pending(g->keyframer) > 0) || !g->injected.empty()) {
             popped.emplace_back();
             Popped& f = popped.back();
-            f.n = -lio_keyframer_pop(g->keyframer, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
-            f.pts.resize((size_t)(f.n > 0 ? f.n : 1) * 4);
             double accum = 0;
-            require(lio_keyframer_pop(g->keyframer, f.pts.data(), (uint64_t)f.n, f.pose.m, &f.stamp, &accum, nullptr, nullptr) == f.n,
-                    "update_odom: key-frame pop failed");
-            if (g->loop_detection) {  // the key frame joins the detector's bank (new_keyframes); one with fewer than k points is left out (lio_last_warning)
+            if (g->keyframer && lio_keyframer_pending(g->keyframer) > 0) {
+                f.n = -lio_keyframer_pop(g->keyframer, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+                f.pts.resize((size_t)(f.n > 0 ? f.n : 1) * 4);
+                require(lio_keyframer_pop(g->keyframer, f.pts.data(), (uint64_t)f.n, f.pose.m, &f.stamp, &accum, nullptr, nullptr) == f.n,
+                        "update_odom: key-frame pop failed");
+            } else {
+                Slam::InjectedKeyFrame& in = g->injected.front();
+                f.n = (int64_t)(in.pts.size() / 4);
+                f.pts = std::move(in.pts);
+                f.pose = in.pose; f.stamp = in.stamp; accum = in.accum;
+                g->injected.pop_front();
+            }
+            if (graph_on) {  // flush_keyframe_queue (hdl_graph_slam_nodelet.cpp:293-334) for this key frame
+                if (!g->loop) {
+                    g->loop = lio_loop_create(0, &g->loop_par);
+                    require(g->loop != nullptr, "update_odom: lio_loop_create failed");
+                }
+                if (!g->graph) {
+                    g->graph = lio_graph_create(0, nullptr);
+                    require(g->graph != nullptr, "update_odom: lio_graph_create failed");
+                }
+                const Mat4 node_pose = mul(g->odom2map, f.pose);
+                // the detector searches from the graph's estimates: the frame enters the bank with its node's pose.  A frame the bank does not take
+                // (fewer than k points, lio_last_warning) stays out of the graph as well: its edges' information needs the bank's cloud
+                const int id = lio_loop_add_keyframe_host(g->loop, f.pts.data(), (uint32_t)f.n, node_pose.m, accum);
+                require(id >= 0 || id == LIO_E_INVALID, "update_odom: lio_loop_add_keyframe_host failed");
+                if (id < 0) continue;
+                banked = true;
+                const int node = lio_graph_add_node(g->graph, node_pose.m);
+                require(node == id && (size_t)node == g->graph_odom.size(), "update_odom: lio_graph_add_node failed");
+                if (node == 0) require(lio_graph_set_fixed(g->graph, 0, 1) == LIO_OK, "update_odom: lio_graph_set_fixed failed");  // fix_first_node
+                g->graph_odom.push_back(f.pose);
+                g->graph_pose.push_back(node_pose);
+                if (node > 0) {  // the edge key frame -> previous: relative_pose = odom^-1 * prev.odom, the pair's information, no kernel
+                    const Mat4 relp = mul(rigid_inverse(f.pose), g->graph_odom[(size_t)node - 1]);
+                    double info[36];
+                    require(lio_loop_pair_information(g->loop, node, node - 1, relp.m, nullptr, nullptr, info) == LIO_OK, "update_odom: lio_loop_pair_information failed");
+                    require(lio_graph_add_edge(g->graph, node, node - 1, relp.m, info, LIO_GRAPH_KERNEL_NONE, 1.0) >= 0, "update_odom: lio_graph_add_edge failed");
+                }
+            } else if (g->loop_detection) {  // the key frame joins the detector's bank (new_keyframes); one with fewer than k points is left out (lio_last_warning)
                 if (!g->loop) {
                     g->loop = lio_loop_create(0, &g->loop_par);
                     require(g->loop != nullptr, "update_odom: lio_loop_create failed");
@@ -935,10 +1019,25 @@ py::dict update_odom() {
                 require(lio_loop_edges(g->loop, g->loop_edges.data(), (uint32_t)total) == total, "update_odom: lio_loop_edges failed");
                 g->loop_detected = true;
             }
+            if (graph_on) {  // optimization_timer_callback (hdl_graph_slam_nodelet.cpp:610-651)
+                for (; g->graph_loops < g->loop_edges.size(); g->graph_loops++) {  // every new loop: key1 -> key2, Huber 1.0
+                    const lio_loop_edge& e = g->loop_edges[g->graph_loops];
+                    Mat4 relp;
+                    for (int k = 0; k < 16; k++) relp.m[k] = (double)e.relative_pose[k];
+                    double info[36];
+                    require(lio_loop_pair_information(g->loop, e.key1, e.key2, relp.m, nullptr, nullptr, info) == LIO_OK, "update_odom: lio_loop_pair_information failed");
+                    require(lio_graph_add_edge(g->graph, e.key1, e.key2, relp.m, info, LIO_GRAPH_KERNEL_HUBER, 1.0) >= 0, "update_odom: lio_graph_add_edge failed");
+                }
+                if (graph_optimize_locked(g.get(), "update_odom")) g->graph_updated = true;
+            }
+        }
+        if (g->graph_updated) {  // graph_update_odom (hdl_graph_slam_nodelet.cpp:821-833)
+            for (size_t k = 0; k < g->graph_pose.size(); k++) odoms.emplace_back((int)k, g->graph_pose[k]);
+            g->graph_updated = false;
         }
     }
     py::dict d;
-    d["odoms"] = py::dict();
+    d["odoms"] = odoms_to_pydict(odoms);
     py::list frames;
     for (const Popped& f : popped) {
         py::array_t<float> pts({(py::ssize_t)f.n, (py::ssize_t)4});
@@ -976,6 +1075,29 @@ void set_loop_detection(bool enable) {
     g->loop_detection = enable;
     if (enable) g->keyframe_output = true;
 }
+// not in the reference's module: the pose graph over the key frames and the loops (off by default; LSD_AMD_GRAPH=1 at init_slam switches it on for
+// an unchanged slam.py).  It consumes the loops and the key frames, so it switches both on too.
+void set_pose_graph(bool enable) {
+    require((bool)g, "init_slam first");
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    g->pose_graph = enable;
+    if (enable) { g->loop_detection = true; g->keyframe_output = true; }
+}
+// test visibility: a key frame (points N x 4 f32, odometry pose 4 x 4 f64, stamp, accumulated distance) for the next update_odom(), as if the
+// front end had elected it
+void _push_keyframe(py::array_t<float, py::array::c_style | py::array::forcecast> points, py::array_t<double, py::array::c_style | py::array::forcecast> pose,
+                    uint64_t stamp, double accum_distance) {
+    require((bool)g, "init_slam first");
+    require(points.ndim() == 2 && points.shape(1) == 4 && pose.size() == 16, "_push_keyframe: points N x 4, pose 4 x 4");
+    Slam::InjectedKeyFrame in;
+    in.pts.assign(points.data(), points.data() + points.size());
+    std::memcpy(in.pose.m, pose.data(), sizeof(double) * 16);
+    in.stamp = stamp; in.accum = accum_distance;
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    g->injected.push_back(std::move(in));
+}
 // the LoopDetector's thresholds (loop_detector.hpp:42-61) by their names.  A detector that already holds key frames starts over with the new
 // values: its bank is gone and frame ids begin at 0 again, so the edges found so far, which name frames of the old bank, are dropped with it
 // (get_loop_edges() is empty until the new detector finds one); get_graph_status()["loop_detected"] stays as it is -- it is sticky.
@@ -1002,6 +1124,11 @@ void set_loop_config(py::dict cfg) {
         if (have[i]) *field[i] = value[i];
     if (g->loop) { lio_loop_destroy(g->loop); g->loop = nullptr; }
     g->loop_edges.clear();
+    // the graph's nodes are the old bank's frames: it starts over with the detector (odom -> map keeps its value)
+    if (g->graph) { lio_graph_destroy(g->graph); g->graph = nullptr; }
+    g->graph_odom.clear(); g->graph_pose.clear();
+    g->graph_loops = 0;
+    g->graph_updated = false;
 }
 // the loop edges found so far: what the reference hands to add_se3_edge (key1 = the new frame, key2, the relative pose, the score's information matrix)
 py::list get_loop_edges() {
@@ -1072,8 +1199,60 @@ py::dict get_graph_map() {
     return d;
 }
 py::array_t<float> get_color_map() { return py::array_t<float>(std::vector<py::ssize_t>{0, 6}); }
-py::dict get_graph_edges() { return py::dict(); }
-py::dict get_graph_meta() { return py::dict(); }
+// the graph's live edges (graph_get_edges, hdl_graph_slam_nodelet.cpp:842-860; vector_to_pydict, py_utils.cpp:29-48): str(id) -> [prev, next]; {} without a graph
+namespace {
+struct GraphEdges { std::vector<int32_t> from, to, id; std::vector<uint8_t> fixed; };
+GraphEdges graph_edges_snapshot() {
+    GraphEdges e;
+    if (!g) return e;
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    if (!g->graph) return e;
+    const int n = -lio_graph_edges(g->graph, nullptr, nullptr, nullptr, 0);
+    if (n > 0) {
+        e.from.resize(n); e.to.resize(n); e.id.resize(n);
+        require(lio_graph_edges(g->graph, e.from.data(), e.to.data(), e.id.data(), (uint32_t)n) == n, "lio_graph_edges failed");
+    }
+    const int nn = lio_graph_num_nodes(g->graph);
+    if (nn > 0) {
+        e.fixed.resize(nn);
+        require(lio_graph_get_fixed(g->graph, e.fixed.data(), (uint32_t)nn) == nn, "lio_graph_get_fixed failed");
+    }
+    return e;
+}
+}  // namespace
+py::dict get_graph_edges() {
+    const GraphEdges e = graph_edges_snapshot();
+    py::dict d;
+    for (size_t k = 0; k < e.id.size(); k++) d[std::to_string(e.id[k]).c_str()] = py::cast(std::vector<int>{e.from[k], e.to[k]});
+    return d;
+}
+// graph_get_info's shape (graph_utils.cpp:70-90): vertex str(id) -> {fix, edge_num}, edge str(id) -> {vertex_num}, and -- this module's
+// addition -- the edge's ends as prev / next; {} without a graph
+py::dict get_graph_meta() {
+    const GraphEdges e = graph_edges_snapshot();
+    if (e.fixed.empty()) return py::dict();
+    std::vector<int> deg(e.fixed.size(), 0);
+    for (size_t k = 0; k < e.id.size(); k++) { deg[e.from[k]]++; deg[e.to[k]]++; }
+    py::dict vertex, edge;
+    for (size_t n = 0; n < e.fixed.size(); n++) {
+        py::dict v;
+        v["fix"] = (bool)e.fixed[n];
+        v["edge_num"] = deg[n];
+        vertex[std::to_string(n).c_str()] = v;
+    }
+    for (size_t k = 0; k < e.id.size(); k++) {
+        py::dict v;
+        v["vertex_num"] = 2;
+        v["prev"] = e.from[k];
+        v["next"] = e.to[k];
+        edge[std::to_string(e.id[k]).c_str()] = v;
+    }
+    py::dict d;
+    d["vertex"] = vertex;
+    d["edge"] = edge;
+    return d;
+}
 // pointcloud_align (graph_utils.cpp:20-46): Generalized-ICP of two clouds from a guess, the guess's translation reset when it is 50 m or
 // more.  The reference calls PCL's GeneralizedIterativeClosestPoint (third-party, source not in the tree) with 20 neighbours, 64 iterations,
 // transformation epsilon 1e-2; here the same cost on the device (lio_gicp_*, the FastGICP formulation the reference's other GICP call
@@ -1120,12 +1299,48 @@ bool get_mapping_ground_constraint() { return g ? g->ground_constraint : false; 
 void set_mapping_constraint(bool loop_closure, bool gravity_constraint) { if (g) { g->loop_closure = loop_closure; g->gravity_constraint = gravity_constraint; } }
 void set_map_colouration(bool enable) { if (g) g->colouration = enable; }
 void del_graph_vertex(int id) { (void)id; }
+// graph_add_edge (hdl_graph_slam_nodelet.cpp:893-912) with score <= 0: calc_information_matrix(prev, next, relative) -- taken on the bank's frames
+// prev_id and next_id, which hold the two clouds -- and Huber 1.0; nothing without a graph
 void add_graph_edge(py::array_t<float>& prev, int prev_id, py::array_t<float>& next, int next_id, py::array_t<float>& relative) {
+    if (g && relative.size() == 16) {
+        py::array_t<float, py::array::c_style | py::array::forcecast> r(relative);
+        Mat4 relp;
+        for (int k = 0; k < 16; k++) relp.m[k] = (double)r.data()[k];
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        if (g->graph && g->loop) {
+            double info[36];
+            require(lio_loop_pair_information(g->loop, prev_id, next_id, relp.m, nullptr, nullptr, info) == LIO_OK, "add_graph_edge: lio_loop_pair_information failed");
+            require(lio_graph_add_edge(g->graph, prev_id, next_id, relp.m, info, LIO_GRAPH_KERNEL_HUBER, 1.0) >= 0, "add_graph_edge: lio_graph_add_edge failed");
+        }
+    }
     (void)prev; (void)prev_id; (void)next; (void)next_id; (void)relative;
 }
-void del_graph_edge(int id) { (void)id; }
-void set_graph_vertex_fix(int id, bool fix) { (void)id; (void)fix; }
-py::dict run_graph_optimization() { return py::dict(); }
+void del_graph_edge(int id) {
+    if (!g) return;
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    if (g->graph) require(lio_graph_remove_edge(g->graph, id) == LIO_OK, "del_graph_edge: no such edge");
+}
+void set_graph_vertex_fix(int id, bool fix) {
+    if (!g) return;
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    if (g->graph) require(lio_graph_set_fixed(g->graph, id, fix ? 1 : 0) == LIO_OK, "set_graph_vertex_fix: no such vertex");
+}
+// graph_optimize: optimize(1024), then every key frame's estimate as str(id) -> 4 x 4; {} without a graph
+py::dict run_graph_optimization() {
+    std::vector<std::pair<int, Mat4>> odoms;
+    if (g) {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        if (g->graph && !g->graph_odom.empty()) {
+            graph_optimize_locked(g.get(), "run_graph_optimization");
+            for (size_t k = 0; k < g->graph_pose.size(); k++) odoms.emplace_back((int)k, g->graph_pose[k]);
+        }
+    }
+    return odoms_to_pydict(odoms);
+}
 py::dict run_robust_graph_optimization(std::string mode) { (void)mode; return py::dict(); }
 // dump_keyframe (graph_utils.cpp:123-131): KeyFrame(stamp, id, pose, numpy_to_pointcloud(points, 255.0)).save(directory) -- `data` + `cloud.pcd`,
 // the files the localisation mode loads its map from
@@ -1780,6 +1995,8 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("save_render_cloud", &save_render_cloud, "save render cloud", py::arg("file"));
     m.def("set_keyframe_output", &set_keyframe_output, "key frames from process() through update_odom()", py::arg("enable"));
     m.def("set_loop_detection", &set_loop_detection, "loop detection over the key frames update_odom() hands out", py::arg("enable"));
+    m.def("set_pose_graph", &set_pose_graph, "the pose graph over the key frames and the loops", py::arg("enable"));
+    m.def("_push_keyframe", &_push_keyframe, "test hook: a key frame for the next update_odom()", py::arg("points"), py::arg("pose"), py::arg("stamp"), py::arg("accum_distance"));
     m.def("set_loop_config", &set_loop_config, "LoopDetector thresholds", py::arg("dict"));
     m.def("get_loop_edges", &get_loop_edges, "loop edges found so far");
     m.def("_last_odometry", &_last_odometry);

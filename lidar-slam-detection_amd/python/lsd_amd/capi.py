@@ -57,7 +57,10 @@ SYMBOLS = [
     "lio_gicp_create", "lio_gicp_destroy", "lio_gicp_set_target", "lio_gicp_set_source", "lio_gicp_set_voxel_mode", "lio_gicp_voxel_at", "lio_gicp_download", "lio_gicp_correspondences", "lio_gicp_linearize", "lio_gicp_align",
     "lio_loop_default_params", "lio_loop_find_candidates", "lio_loop_information_matrix", "lio_loop_create", "lio_loop_destroy", "lio_loop_reset",
     "lio_loop_add_keyframe_host", "lio_loop_set_pose", "lio_loop_num_keyframes", "lio_loop_download_keyframe", "lio_loop_detect", "lio_loop_edges",
-    "lio_loop_last_report", "lio_loop_last_times", "lio_loop_align_candidates", "lio_loop_align_fine",
+    "lio_loop_last_report", "lio_loop_last_times", "lio_loop_align_candidates", "lio_loop_align_fine", "lio_loop_pair_information",
+    "lio_graph_default_params", "lio_graph_create", "lio_graph_destroy", "lio_graph_reset", "lio_graph_add_node", "lio_graph_set_fixed", "lio_graph_set_estimate",
+    "lio_graph_num_nodes", "lio_graph_get_fixed", "lio_graph_add_edge", "lio_graph_remove_edge", "lio_graph_optimize", "lio_graph_estimates", "lio_graph_edges",
+    "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
 ]
 
 
@@ -140,6 +143,19 @@ class LoopEdge(C.Structure):  # lio_loop_edge
 class LoopReport(C.Structure):  # lio_loop_report
     _fields_ = [("new_id", C.c_int32), ("n_candidates", C.c_int32), ("best", C.c_int32), ("fine_converged", C.c_int32), ("fine_iterations", C.c_int32),
                 ("reason", C.c_int32), ("coarse_rounds", C.c_int32), ("pad", C.c_int32), ("best_score", C.c_double), ("fine_score", C.c_double)]
+
+
+class GraphParams(C.Structure):  # lio_graph_params
+    _fields_ = [("cg_epsilon", C.c_double), ("chi2_rel_stop", C.c_double), ("min_edges", C.c_int32), ("cg_max_iterations", C.c_int32)]
+
+
+class GraphReport(C.Structure):  # lio_graph_report
+    _fields_ = [("iterations", C.c_int32), ("stop_reason", C.c_int32), ("trials", C.c_int32), ("accepted", C.c_int32), ("n_active", C.c_int32),
+                ("n_live_edges", C.c_int32), ("cg_iterations", C.c_int32), ("cg_iterations_total", C.c_int32), ("chi2_initial", C.c_double),
+                ("chi2_final", C.c_double), ("lambda_", C.c_double), ("cg_residual", C.c_double)]
+
+
+GRAPH_KERNEL_NONE, GRAPH_KERNEL_HUBER = 0, 1
 
 
 class BevInfo(C.Structure):  # lio_bev_info
@@ -419,6 +435,28 @@ def lib():
     sig("lio_loop_last_times", cint, vp, f64p, f64p, f64p, f64p, f64p)
     sig("lio_loop_align_candidates", cint, vp, cint, i32p, u32, f64p, f64p, i32p, i32p, f64p, C.POINTER(u32))
     sig("lio_loop_align_fine", cint, vp, cint, cint, f64p, f64p, i32p, i32p, f64p, C.POINTER(u32))
+    sig("lio_loop_pair_information", cint, vp, cint, cint, f64p, f64p, C.POINTER(u32), f64p)
+    gp, gr = C.POINTER(GraphParams), C.POINTER(GraphReport)
+    sig("lio_graph_default_params", None, gp)
+    sig("lio_graph_create", vp, cint, gp)
+    sig("lio_graph_destroy", None, vp)
+    sig("lio_graph_reset", cint, vp)
+    sig("lio_graph_add_node", cint, vp, f64p)
+    sig("lio_graph_set_fixed", cint, vp, cint, cint)
+    sig("lio_graph_set_estimate", cint, vp, cint, f64p)
+    sig("lio_graph_num_nodes", cint, vp)
+    sig("lio_graph_get_fixed", cint, vp, u8p, u32)
+    sig("lio_graph_add_edge", cint, vp, cint, cint, f64p, f64p, cint, dbl)
+    sig("lio_graph_remove_edge", cint, vp, cint)
+    sig("lio_graph_optimize", cint, vp, cint, gr)
+    sig("lio_graph_estimates", cint, vp, f64p, u32)
+    sig("lio_graph_edges", cint, vp, i32p, i32p, i32p, u32)
+    sig("lio_graph_chi2", cint, vp, f64p)
+    sig("lio_graph_linearize", cint, vp, f64p, f64p, f64p, u32, f64p, f64p, u32)
+    sig("lio_graph_last_times", cint, vp, f64p, f64p, f64p, f64p)
+    sig("lio_se3_from_mqt", None, f64p, f64p)
+    sig("lio_se3_to_mqt", None, f64p, f64p)
+    sig("lio_graph_edge_error", cint, f64p, f64p, f64p, f64p)
     sig("lio_state_boxplus", None, f64p, f64p, f64p)
     sig("lio_state_boxminus", None, f64p, f64p, f64p)
     _lib = L

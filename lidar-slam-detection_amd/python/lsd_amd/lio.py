@@ -780,6 +780,140 @@ class LoopDetector:
               "loop align_fine")
         return T, bool(conv.value), int(it.value), sc.value, nr.value
 
+    def pair_information(self, id1, id2, relpose):
+        """calc_information_matrix(cloud1, cloud2, relpose): frame id2 moved by relpose (cast to f32) against frame id1's exact nearest
+        neighbours, every point counting -> (score, nr, information (6, 6))"""
+        T, info = f64(relpose).reshape(4, 4), np.zeros((6, 6))
+        sc, nr = C.c_double(0), C.c_uint32(0)
+        check(lib().lio_loop_pair_information(self.h, int(id1), int(id2), ptr(T, C.c_double), C.byref(sc), C.byref(nr), ptr(info, C.c_double)), "loop pair_information")
+        return sc.value, nr.value, info
+
+
+class PoseGraph:
+    """The pose graph on the device (lio_graph_*): SE3 nodes, EdgeSE3 edges with an optional Huber kernel, Levenberg-Marquardt as g2o's
+    OptimizationAlgorithmLevenberg runs it, the linear solve by block-Jacobi conjugate gradients.  Keyword arguments override lio_graph_params."""
+
+    NONE, HUBER = capi.GRAPH_KERNEL_NONE, capi.GRAPH_KERNEL_HUBER
+    STOPS = {0: "none", 1: "max_iterations", 2: "trials", 3: "rho_zero", 4: "lambda", 5: "chi2_rel"}
+
+    def __init__(self, device=0, **params):
+        self.params = self.default_params()
+        for k, v in params.items():
+            if not hasattr(self.params, k):
+                raise TypeError(f"lio_graph_params has no field {k!r}")
+            setattr(self.params, k, v)
+        self.h = lib().lio_graph_create(device, C.byref(self.params))
+        if not self.h:
+            raise capi.LioError("lio_graph_create failed: " + lib().lio_last_error().decode())
+
+    @staticmethod
+    def default_params():
+        p = capi.GraphParams()
+        lib().lio_graph_default_params(C.byref(p))
+        return p
+
+    @staticmethod
+    def from_mqt(v6):
+        v, T = f64(v6).ravel(), np.zeros((4, 4))
+        lib().lio_se3_from_mqt(ptr(v, C.c_double), ptr(T, C.c_double))
+        return T
+
+    @staticmethod
+    def to_mqt(T):
+        M, v = f64(T).reshape(4, 4), np.zeros(6)
+        lib().lio_se3_to_mqt(ptr(M, C.c_double), ptr(v, C.c_double))
+        return v
+
+    @staticmethod
+    def edge_error(x_from, x_to, m):
+        a, b, c, e = f64(x_from).reshape(4, 4), f64(x_to).reshape(4, 4), f64(m).reshape(4, 4), np.zeros(6)
+        check(lib().lio_graph_edge_error(ptr(a, C.c_double), ptr(b, C.c_double), ptr(c, C.c_double), ptr(e, C.c_double)), "graph edge_error")
+        return e
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_graph_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        check(lib().lio_graph_reset(self.h), "graph reset")
+
+    def add_node(self, pose, fixed=False):
+        T = f64(pose).reshape(4, 4)
+        nid = check(lib().lio_graph_add_node(self.h, ptr(T, C.c_double)), "graph add_node")
+        if fixed:
+            self.set_fixed(nid, True)
+        return nid
+
+    def set_fixed(self, nid, flag=True):
+        check(lib().lio_graph_set_fixed(self.h, int(nid), int(bool(flag))), "graph set_fixed")
+
+    def set_estimate(self, nid, pose):
+        T = f64(pose).reshape(4, 4)
+        check(lib().lio_graph_set_estimate(self.h, int(nid), ptr(T, C.c_double)), "graph set_estimate")
+
+    def add_edge(self, i, j, measurement, information, kernel=0, delta=1.0):
+        M, W = f64(measurement).reshape(4, 4), f64(information).reshape(6, 6)
+        return check(lib().lio_graph_add_edge(self.h, int(i), int(j), ptr(M, C.c_double), ptr(W, C.c_double), int(kernel), float(delta)), "graph add_edge")
+
+    def remove_edge(self, eid):
+        check(lib().lio_graph_remove_edge(self.h, int(eid)), "graph remove_edge")
+
+    @property
+    def num_nodes(self):
+        return check(lib().lio_graph_num_nodes(self.h), "graph num_nodes")
+
+    def fixed(self):
+        n = self.num_nodes
+        out = np.zeros(max(n, 1), np.uint8)
+        check(lib().lio_graph_get_fixed(self.h, ptr(out, C.c_uint8), len(out)), "graph get_fixed")
+        return out[:n].astype(bool)
+
+    def optimize(self, max_iterations=1024):
+        """-> (iterations run, or -1 when the graph has fewer than min_edges live edges and nothing was touched; the report as a dict)"""
+        rep = capi.GraphReport()
+        n = lib().lio_graph_optimize(self.h, int(max_iterations), C.byref(rep))
+        if n < -1 or (n == -1 and len(self.edges()[0]) >= self.params.min_edges):
+            check(n, "graph optimize")
+        d = {k: getattr(rep, k) for k, _ in capi.GraphReport._fields_}
+        d["lambda"] = d.pop("lambda_")
+        d["stop"] = self.STOPS.get(rep.stop_reason, str(rep.stop_reason))
+        return n, d
+
+    def estimates(self):
+        n = self.num_nodes
+        out = np.zeros((max(n, 1), 4, 4))
+        check(lib().lio_graph_estimates(self.h, ptr(out, C.c_double), len(out)), "graph estimates")
+        return out[:n]
+
+    def edges(self):
+        """the live edges: (from, to, id)"""
+        n = abs(lib().lio_graph_edges(self.h, None, None, None, 0))
+        a, b, c = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        check(lib().lio_graph_edges(self.h, ptr(a, C.c_int32), ptr(b, C.c_int32), ptr(c, C.c_int32), max(n, 1)), "graph edges")
+        return a[:n], b[:n], c[:n]
+
+    def chi2(self):
+        v = C.c_double(0)
+        check(lib().lio_graph_chi2(self.h, C.byref(v)), "graph chi2")
+        return v.value
+
+    def linearize(self, n_edge_ids):
+        """one linearisation at the current estimate: errors (E, 6), chi2 (E,), rho' (E,), b (N, 6), the diagonal blocks (N, 6, 6)"""
+        E, N = int(n_edge_ids), self.num_nodes
+        err, c2, r1, b, Hd = np.zeros((max(E, 1), 6)), np.zeros(max(E, 1)), np.zeros(max(E, 1)), np.zeros((max(N, 1), 6)), np.zeros((max(N, 1), 6, 6))
+        got = check(lib().lio_graph_linearize(self.h, ptr(err, C.c_double), ptr(c2, C.c_double), ptr(r1, C.c_double), len(c2), ptr(b, C.c_double), ptr(Hd, C.c_double),
+                                              len(b)), "graph linearize")
+        assert got == E, (got, E)
+        return err[:E], c2[:E], r1[:E], b[:N], Hd[:N]
+
+    def last_times(self):
+        v = [C.c_double(0) for _ in range(4)]
+        check(lib().lio_graph_last_times(self.h, *[C.byref(x) for x in v]), "graph last_times")
+        return dict(zip(("linearize_us", "assemble_us", "solve_us", "update_us"), [x.value for x in v]))
+
 
 class Cloud:
     """lio_cloud: a device-resident cloud that grows over a drive, and pcl::VoxelGrid over all of it (the dense-map export of
