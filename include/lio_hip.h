@@ -64,8 +64,9 @@ int lio_device_count(void);
  * 12 = lio_loop_* (loop detection over the key frames: candidate search, batched FAST_VGICP with the LM loop on the device, nearest-neighbour
  * fitness, FAST_GICP verification, the loop edge with its information matrix);
  * 13 = lio_graph_* / lio_se3_* / lio_loop_pair_information (the pose graph: SE3 edges, Huber, Levenberg-Marquardt with a conjugate-gradient solve
- * on the device; the information matrix of two bank frames under a relative pose). */
-#define LIO_ABI_VERSION 13
+ * on the device; the information matrix of two bank frames under a relative pose);
+ * 14 = lio_scan_undistort_imu (test visibility: the FastLIO front half's point filter and IMU backward propagation on caller-supplied poses). */
+#define LIO_ABI_VERSION 14
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -175,6 +176,19 @@ int lio_scan_download_raw(lio_scan*, float* out_xyzi, uint32_t cap);
  * The interval ends must not decrease (LIO_E_INVALID otherwise); at most 64 poses. */
 int lio_scan_undistort_poses(lio_scan*, const uint32_t* stamp_us, int stamps_on_device, uint64_t header_stamp_us, const uint64_t* pose_stamp_us,
                              const double* pose_T, uint32_t n_poses);
+/* test visibility for the front half: Preprocess::velodyne_handler's point filter and ImuProcess::UndistortPcl's backward propagation
+ * (preprocess.cpp:395-451, IMU_Processing.hpp:371-404) on the uploaded cloud with CALLER-SUPPLIED IMU poses -- the very launcher and kernels
+ * lio_fastlio_main runs after its forward propagation, without the filter state in between.  poses: n_poses x 22 doubles, each
+ * (offset_time s, acc[3], gyr[3], vel[3], pos[3], R[9] row-major), offsets not decreasing, poses[0] the scan start; end_pos3 /
+ * end_rot_xyzw / ril_xyzw / til3: position, attitude and lidar-IMU extrinsics of the state at the scan end; a point whose f32
+ * x*x + y*y + z*z is not above blind^2, or whose index is no multiple of filter_num (> 1), becomes NaN (intensity kept); undistort = 0:
+ * the filters alone (stamps, poses and the end state are not read and may be NULL).  stamp_us as for lio_scan_undistort_delta, staged in
+ * the downsample's second key buffer; the per-workgroup minima of the kernel go to its first key buffer (2 words per 256 points; both
+ * are free until lio_scan_voxel_downsample runs on the same stream); the pose table is uploaded per call.  n_poses outside 2..128 with
+ * undistort on: LIO_E_CAPACITY, the cloud is left as it was.  Waits for the result; it replaces the scan's raw cloud as
+ * lio_scan_undistort_delta's does. */
+int lio_scan_undistort_imu(lio_scan*, const uint32_t* stamp_us, int stamps_on_device, const double* poses, uint32_t n_poses, const double* end_pos3,
+                           const double* end_rot_xyzw, const double* ril_xyzw, const double* til3, double blind, int filter_num, int undistort);
 int lio_scan_voxel_downsample(lio_scan*, float leaf, int sync, uint32_t* n_ds);
 /* the same filter over n scans (each holding its raw cloud: lio_scan_upload / lio_scan_set_device) with ONE set of launches -- the batched
  * chain of lio_batch, blockIdx.y = scan -- for callers that hold many clouds at once (the candidate key frames of the map-merge tools,

@@ -722,6 +722,50 @@ int lio_scan_undistort_poses(lio_scan* s, const uint32_t* stamp_us, int stamps_o
     return LIO_OK;
 }
 
+// test visibility for the front half: the launcher fe_undistort (engine.hip) calls, on poses the caller supplies
+int lio_scan_undistort_imu(lio_scan* s, const uint32_t* stamp_us, int stamps_on_device, const double* poses, uint32_t n_poses, const double* end_pos3,
+                           const double* end_rot_xyzw, const double* ril_xyzw, const double* til3, double blind, int filter_num, int undistort) {
+    if (!s) return LIO_E_INVALID;
+    if (undistort && (!poses || !end_pos3 || !end_rot_xyzw || !ril_xyzw || !til3 || (!stamp_us && s->n_raw))) return LIO_E_INVALID;
+    if (s->n_raw == 0) return LIO_OK;
+    static_assert(sizeof(ImuPoseDev) == 22 * sizeof(double), "the pose rows of lio_scan_undistort_imu are ImuPoseDev");
+    const uint32_t blocks = (s->n_raw + 255) / 256;
+    if ((uint64_t)blocks * 2 > s->max_raw) { set_error("undistort: a scan handle of %u points has no room for the workgroup minima", s->max_raw); return LIO_E_CAPACITY; }
+    UndistortArgs A;
+    memset(&A, 0, sizeof(A));
+    A.blind2 = blind * blind;
+    A.filter_num = filter_num;
+    A.undistort = undistort ? 1 : 0;
+    A.n_poses = undistort ? (int)std::min<uint32_t>(n_poses, 1u << 20) : 0;  // the launcher refuses what is outside 2..kMaxImuPoses
+    hipSetDevice(s->device);
+    const uint32_t* d_stamp = stamp_us;
+    ImuPoseDev* d_poses = nullptr;
+    if (undistort) {
+        for (int i = 0; i < 3; i++) { A.pos_e[i] = end_pos3[i]; A.til[i] = til3[i]; }
+        for (int i = 0; i < 4; i++) { A.rot_e[i] = end_rot_xyzw[i]; A.ril[i] = ril_xyzw[i]; }
+        if (!stamps_on_device) {
+            LIO_HIP_TRY(hipMemcpyAsync(s->keys_b, stamp_us, (size_t)s->n_raw * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+            d_stamp = s->keys_b;
+        }
+        const uint32_t rows = std::min<uint32_t>(std::max<uint32_t>(n_poses, 1u), (uint32_t)kMaxImuPoses);
+        LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_poses), sizeof(ImuPoseDev) * rows));
+        if (hipMemcpyAsync(d_poses, poses, sizeof(ImuPoseDev) * std::min<uint32_t>(n_poses, rows), hipMemcpyHostToDevice, s->stream) != hipSuccess) {
+            hipFree(d_poses);
+            set_error("undistort: pose upload failed: %s", hipGetErrorString(hipGetLastError()));
+            return LIO_E_DEVICE;
+        }
+    }
+    int rc = undistort_launch(s->stream, s->raw, d_stamp, s->n_raw, s->raw_own, d_poses, A, reinterpret_cast<unsigned long long*>(s->keys_a));
+    if (hipStreamSynchronize(s->stream) != hipSuccess && rc == LIO_OK) {  // the pose table and the caller's arrays may go away
+        set_error("undistort: %s", hipGetErrorString(hipGetLastError()));
+        rc = LIO_E_DEVICE;
+    }
+    if (d_poses) hipFree(d_poses);
+    if (rc != LIO_OK) return rc;
+    s->raw = s->raw_own;
+    return LIO_OK;
+}
+
 int lio_scan_download_raw(lio_scan* s, float* out_xyzi, uint32_t cap) {
     if (!s || !out_xyzi) return LIO_E_INVALID;
     if (s->n_raw > cap) { set_error("raw cloud of %u points exceeds cap %u", s->n_raw, cap); return LIO_E_CAPACITY; }

@@ -194,6 +194,15 @@ class Scan:
         check(lib().lio_scan_undistort_poses(self.h, C.c_void_p(self._stamps.ctypes.data), 0, int(header_stamp_us), ps.ctypes.data_as(C.POINTER(C.c_uint64)),
                                              pt.ctypes.data_as(C.POINTER(C.c_double)), len(ps)), "undistort_poses")
 
+    def undistort_imu(self, stamp_us, poses, end_pos, end_rot_xyzw, ril_xyzw, til, blind=0.1, filter_num=1, undistort=True):
+        """the FastLIO front half's point filter and IMU backward propagation (IMU_Processing.hpp:371-404) on the uploaded cloud with the
+        caller's poses: rows of 22 doubles (offset s, acc, gyr, vel, pos, R row-major); host stamps.  Dropped points come back NaN."""
+        self._stamps = np.ascontiguousarray(stamp_us, np.uint32)
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 22)
+        a = [np.ascontiguousarray(v, np.float64).reshape(k) for v, k in ((end_pos, 3), (end_rot_xyzw, 4), (ril_xyzw, 4), (til, 3))]
+        check(lib().lio_scan_undistort_imu(self.h, C.c_void_p(self._stamps.ctypes.data), 0, ptr(P, C.c_double), len(P), *[ptr(v, C.c_double) for v in a],
+                                           float(blind), int(filter_num), int(bool(undistort))), "undistort_imu")
+
     def download_raw(self, cap=1 << 18):
         out = np.zeros((cap, 4), np.float32)
         n = lib().lio_scan_download_raw(self.h, out.ctypes.data_as(C.POINTER(C.c_float)), cap)

@@ -137,6 +137,10 @@ def test_host_only_entry_points_reject_bad_arguments():
         getattr(L, name)(None)
     assert L.lio_scan_upload(None, None, 0) == capi.LIO_E_INVALID
     assert L.lio_scan_undistort_delta(None, None, 0, None, 0.1) == capi.LIO_E_INVALID
+    z3, q4 = np.zeros(3), np.array([0, 0, 0, 1.0])
+    assert L.lio_scan_undistort_imu(None, None, 0, np.zeros(44).ctypes.data_as(f64p), 2, z3.ctypes.data_as(f64p), q4.ctypes.data_as(f64p), q4.ctypes.data_as(f64p),
+                                    z3.ctypes.data_as(f64p), 0.1, 1, 1) == capi.LIO_E_INVALID
+    assert L.lio_scan_undistort_imu(None, None, 0, None, 0, None, None, None, None, 0.1, 1, 0) == capi.LIO_E_INVALID
     assert L.lio_engine_process_scan(None, None, 0, 0.0) < 0
     assert L.lio_fastlio_main(None) < 0
     assert L.lio_ndt_align(None, None, None, None, None, None, None) == capi.LIO_E_INVALID
