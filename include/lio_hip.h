@@ -65,8 +65,10 @@ int lio_device_count(void);
  * fitness, FAST_GICP verification, the loop edge with its information matrix);
  * 13 = lio_graph_* / lio_se3_* / lio_loop_pair_information (the pose graph: SE3 edges, Huber, Levenberg-Marquardt with a conjugate-gradient solve
  * on the device; the information matrix of two bank frames under a relative pose);
- * 14 = lio_scan_undistort_imu (test visibility: the FastLIO front half's point filter and IMU backward propagation on caller-supplied poses). */
-#define LIO_ABI_VERSION 14
+ * 14 = lio_scan_undistort_imu (test visibility: the FastLIO front half's point filter and IMU backward propagation on caller-supplied poses).
+ * 15 = lio_graph_add_prior / set_kernel / priors / prior_error / remove_gnss_outliers, LIO_GRAPH_KERNEL_DCS2 (the pose graph's unary edges: GNSS
+ *      position, orientation and floor-plane priors, the DCS2 kernel, the GNSS outlier stage of robust_graph_optimize). */
+#define LIO_ABI_VERSION 15
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1154,8 +1156,10 @@ int lio_loop_pair_information(lio_loop*, int id1, int id2, const double relpose[
  * The pose graph on the device (csrc/graph.hip): what hdl_graph_slam's GraphSLAM does with g2o for SE3 pose nodes and EdgeSE3 edges
  * (graph_slam.cpp:344-375, solver "lm_var").  g2o is not in the reference tree: THE RULES BELOW ARE RESTATED FROM g2o'S PUBLISHED SOURCE
  * (types/slam3d/isometry3d_mappings, edge_se3, core/robust_kernel_impl, core/optimization_algorithm_levenberg) and are pinned to an f64 numpy
- * restatement (tests/graph_cases.py), not to a compiled reference.  GNSS, floor-plane and IMU edges, the DCS2 kernel and the
- * robust_graph_optimize modes are out of scope.  NULL from lio_graph_create without a device: there is no CPU fallback.
+ * restatement (tests/graph_cases.py, tests/graph_prior_cases.py), not to a compiled reference.  Out of scope: the reference's
+ * EdgeSE3PriorVec (its only producer, imu_callback, returns at once: hdl_graph_slam_nodelet.cpp:462-463) and the "GNSS moment" stage of
+ * robust_graph_optimize's mode `mapping` (:1039-1081), which needs a 3-DoF point vertex.  NULL from lio_graph_create without a device: there is
+ * no CPU fallback.
  *   state       a node is an f64 translation, a unit quaternion and a fixed flag; an edge is from, to, a measurement M (given as a row-major
  *               4 x 4, kept as translation + quaternion), an f64 6 x 6 information matrix, a kernel and its delta.  Ids count from 0 in creation
  *               order and are never reused; a removed edge takes no part.
@@ -1167,6 +1171,28 @@ int lio_loop_pair_information(lio_loop*, int id1, int id2, const double relpose[
  *               rho' = delta / sqrt(chi2_e).  The quadratic form uses rho' Omega with no second-order term: b += -J^T (rho' Omega) e,
  *               H += J^T (rho' Omega) J.  The graph's chi2 is the sum of rho over the live edges.
  *   Jacobians   analytic: the derivative of e with respect to the two nodes' d at 0.
+ *   priors      a prior is a unary edge of three rows on one node (hdl_graph_slam's EdgeSE3PriorXYZ, EdgeSE3PriorQuat, EdgeSE3Plane; the plane
+ *               vertex of the last is always fixed in the reference, :563, so the edge carries its world plane and there is no plane vertex).
+ *               It takes the next id of the same counter as the binary edges (graph_slam.cpp's max_edge_id++), ids are never reused,
+ *               lio_graph_remove_edge removes either kind, a prior counts towards min_edges and gives its node a live edge: a free node whose only
+ *               live edges are priors is active.  A prior on a fixed node adds its rho to chi2 and nothing to H or b.  With R, t, q = (v, w) of
+ *               the node:
+ *                 XYZ    (edge_se3_priorxyz.hpp:39-44)  e = t - m;  J = [R, 0]
+ *                 QUAT   (edge_se3_priorquat.hpp:39-55) the measurement is normalised on entry (THE PROJECT'S RULE) and flipped so that w_m >= 0;
+ *                        s = -1 if m . q < 0 else +1;  e = s v - v_m;  J = [0, s (w I + [v]x)]
+ *                 PLANE  (edge_se3_plane.hpp:40-47, g2o's Plane3D) the world plane (n, d) and the measurement (n_m, d_m) are each divided by
+ *                        the norm of their normal on entry;  n_l = R^T n, d_l = d + t . n;  az(x) = atan2(x_y, x_x), el(x) = atan2(x_z,
+ *                        hypot(x_x, x_y));  A = Rz(az(n_m)) Ry(-el(n_m)), u = A^T n_l;  e = (az(u), el(u), d_m - d_l).  With r^2 = u_x^2 + u_y^2
+ *                        and D = 2 A^T [n_l]x: row 0 of J is [0, (-u_y, u_x, 0) / r^2 D], row 1 is [0, (-u_x u_z / r, -u_y u_z / r, r) D], row 2 is
+ *                        [-n_l^T, 0].  THE PROJECT'S RULE: rows 0 and 1 are zero when r^2 == 0.
+ *               g2o differentiates these edges numerically (central differences, 1e-9); THE ANALYTIC JACOBIANS ARE THE PROJECT'S RULE.
+ *               chi2_e = e^T Omega e with a symmetric 3 x 3 Omega, refused by the same test as the 6 x 6.
+ *   DCS2        (robust_kernel_dcs2.hpp, either kind of edge) phi = delta, s = 2 phi / (phi + chi2_e).  s >= 1: rho = chi2_e, rho' = 1; otherwise
+ *               rho = s^2 chi2_e, rho' = 4 phi^2 (phi - chi2_e) / (phi + chi2_e)^3.  rho' is negative for chi2_e > phi and is used as it is (g2o
+ *               does the same); a diagonal block that stops being positive definite fails the trial (CHOLMOD would fail there too).
+ *   outliers    THE PROJECT'S NAME for the first stage of robust_graph_optimize (:1004-1038), lio_graph_remove_gnss_outliers: every live XYZ prior
+ *               gets DCS2 with delta = max_err^2 Omega(0,0); optimise; every XYZ prior with 2 phi / (phi + chi2_e) < 0.1 (the unrobustified
+ *               chi2_e) is removed; optimise again.  The priors that stay keep DCS2.
  *   active set  a fixed node contributes no unknowns; a node with no live edge is left out of the solve and keeps its estimate.
  *   LM          OptimizationAlgorithmLevenberg: lambda_0 = 1e-5 max diag(H), nu = 2.  A trial solves (H + lambda I) d = b, applies the update and
  *               re-evaluates chi2; rho = (chi2_old - chi2_new) / (d^T (lambda d + b) + 1e-3).  Accepted (rho > 0, chi2_new finite): lambda *=
@@ -1178,12 +1204,17 @@ int lio_loop_pair_information(lio_loop*, int id1, int id2, const double relpose[
  *               node's damped 6 x 6 diagonal block, until |r| <= cg_epsilon |b| or cg_max_iterations (0: 12 x active nodes).  An inexact step is
  *               still safe: the rho test judges it.  The iterations and the final relative residual are in the report.
  *   sums        every block of H (one diagonal block per active node, one off-diagonal block per distinct pair) and of b is the sum of its
- *               edges' contributions in rising edge id; chi2 is summed per 256 consecutive edges and then over those records in order; the
+ *               edges' contributions in rising edge id, binary and unary interleaved by id; chi2 is summed per 256 consecutive edge ids (of
+ *               either kind) and then over those records in order; the
  *               dot products of the solve are folded in a fixed order.  No floating-point atomics: two runs give the same bits.
  * ------------------------------------------------------------------------------------------------------------- */
 typedef struct lio_graph lio_graph;
 #define LIO_GRAPH_KERNEL_NONE 0
 #define LIO_GRAPH_KERNEL_HUBER 1
+#define LIO_GRAPH_KERNEL_DCS2 2
+#define LIO_GRAPH_PRIOR_XYZ 0
+#define LIO_GRAPH_PRIOR_QUAT 1
+#define LIO_GRAPH_PRIOR_PLANE 2
 #define LIO_GRAPH_STOP_MAX_ITERATIONS 1
 #define LIO_GRAPH_STOP_TRIALS 2          /* the tenth trial of an iteration was reached */
 #define LIO_GRAPH_STOP_RHO_ZERO 3
@@ -1218,19 +1249,33 @@ int lio_graph_set_estimate(lio_graph*, int id, const double pose16[16]);
 int lio_graph_num_nodes(lio_graph*);
 /* the fixed flags of all nodes; the count, or -(count) when cap is too small */
 int lio_graph_get_fixed(lio_graph*, uint8_t* out, uint32_t cap);
-/* the id; LIO_E_INVALID for from == to, an unknown node or kernel, Huber with delta <= 0, or an information matrix that is not finite or not
+/* the id; LIO_E_INVALID for from == to, an unknown node or kernel, a kernel with delta <= 0, or an information matrix that is not finite or not
  * symmetric to 1e-9 of its largest entry */
 int lio_graph_add_edge(lio_graph*, int from, int to, const double M16[16], const double info36[36], int kernel, double delta);
 int lio_graph_remove_edge(lio_graph*, int id);
+/* a prior on one node: type LIO_GRAPH_PRIOR_*; m4 = x, y, z (XYZ; m4[3] is not read), a quaternion x, y, z, w (QUAT) or a plane n, d in the node's
+ * frame (PLANE); plane4 = the world plane of a PLANE prior (NULL otherwise); info9 row-major 3 x 3.  The id; LIO_E_INVALID for an unknown node,
+ * type or kernel, a kernel with delta <= 0, a value that is not finite, a zero normal or quaternion, or an information matrix that is not
+ * symmetric to 1e-9 of its largest entry */
+int lio_graph_add_prior(lio_graph*, int node, int type, const double m4[4], const double* plane4, const double info9[9], int kernel, double delta);
+/* the robust kernel of a live edge of either kind */
+int lio_graph_set_kernel(lio_graph*, int edge_id, int kernel, double delta);
+/* the live priors in rising id, as the graph keeps them (any array may be NULL; m4 and plane4 4 per prior, info9 9); the count, or -(count) when
+ * cap is too small */
+int lio_graph_priors(lio_graph*, int32_t* id, int32_t* node, int32_t* type, double* m4, double* plane4, double* info9, int32_t* kernel, double* delta, uint32_t cap);
+/* the GNSS outlier stage (the rules above, "outliers"): the number of priors removed, their ids into removed_ids (the first cap of them; may be
+ * NULL); -1 with nothing touched when fewer than min_edges live edges exist.  report (may be NULL) is of the second optimisation */
+int lio_graph_remove_gnss_outliers(lio_graph*, double max_distance_error, int max_iterations, int32_t* removed_ids, uint32_t cap, lio_graph_report* report);
 /* the iterations run; -1 with nothing touched when fewer than min_edges live edges exist (GraphSLAM::optimize); other negative values are
  * LIO_E_* (a NULL handle is LIO_E_INVALID = -1 as well).  report may be NULL */
 int lio_graph_optimize(lio_graph*, int max_iterations, lio_graph_report* report);
 /* all estimates as row-major 4 x 4 (cap in nodes); the count, or -(count) when cap is too small */
 int lio_graph_estimates(lio_graph*, double* out16, uint32_t cap);
-/* the live edges in rising id (any array may be NULL); the count, or -(count) when cap is too small */
+/* the live edges in rising id (any array may be NULL); a prior has from = its node and to = -1; the count, or -(count) when cap is too small */
 int lio_graph_edges(lio_graph*, int32_t* from, int32_t* to, int32_t* id, uint32_t cap);
 int lio_graph_chi2(lio_graph*, double* chi2);
-/* stage door: one linearisation at the current estimate, no step taken.  Per edge id (removed edges: zeros) the error, chi2_e and rho'; per node
+/* stage door: one linearisation at the current estimate, no step taken.  Per edge id (removed edges: zeros; a prior's error in the first three
+ * of its six slots) the error, chi2_e and rho'; per node
  * id (fixed or unconnected nodes: zeros) b and the diagonal block of H.  Any output may be NULL; the number of edge ids, LIO_E_CAPACITY when a
  * cap is too small */
 int lio_graph_linearize(lio_graph*, double* errors, double* chi2, double* rho1, uint32_t edge_cap, double* b, double* Hdiag, uint32_t node_cap);
@@ -1240,6 +1285,8 @@ int lio_graph_last_times(lio_graph*, double* linearize_us, double* assemble_us, 
 void lio_se3_from_mqt(const double v6[6], double T16[16]);
 void lio_se3_to_mqt(const double T16[16], double v6[6]);
 int lio_graph_edge_error(const double Xfrom16[16], const double Xto16[16], const double M16[16], double e6[6]);
+/* host only: a prior's error at the pose X; m4 and plane4 as lio_graph_add_prior takes them (normalised here the same way) */
+int lio_graph_prior_error(const double X16[16], int type, const double m4[4], const double* plane4, double e3[3]);
 
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);

@@ -10,6 +10,11 @@
 //              lanes, dot products folded in a fixed order, __syncthreads between the phases; no grid-wide barrier
 //   update     graph_update (backup + X <- X fromVectorMQT(d), q renormalised), graph_chi2 (rho per edge, one partial per 256 edges),
 //              graph_decide (one workgroup: folds the partials in order, the LM bookkeeping, restores a rejected trial)
+//   priors     unary 3-row edges (GNSS position, orientation, floor plane) live in a compact array of their own (PriorDev); a prior takes
+//              the next id of the one edge counter, and the edge array keeps a placeholder (live = kPriorSlot, from = the prior's index) at
+//              that id.  graph_linearize_prior (one lane per prior) writes e, chi2, rho', J^T W J and -J^T W e into the id's Hii / bi slots, so
+//              graph_assemble and the node -> edges lists take both kinds in rising id as they are; graph_chi2<true> follows the placeholder,
+//              so a prior's rho joins the partial of its 256 ids.  Without priors neither the extra launch nor graph_chi2<true> is used.
 // The host enqueues, per LM iteration, linearise + assemble + kMaxTrials trials; a kernel whose trial is not wanted (the iteration was decided, or
 // the optimisation stopped) leaves at once.  The host reads one LmState per iteration.
 #include <cfloat>
@@ -34,6 +39,16 @@ struct EdgeDev {
     double mt[3], mq[4];  // the measurement: translation, unit quaternion (x, y, z, w)
     double info[36];
 };
+
+// a unary edge on one node: LIO_GRAPH_PRIOR_*; m = xyz / unit quaternion (x, y, z, w >= 0) / unit plane (n, d); plane = the world plane of PLANE
+struct PriorDev {
+    int32_t node, type, kernel, live;
+    int32_t id, pad;  // its edge id
+    double delta;
+    double m[4], plane[4];
+    double info[9];
+};
+constexpr int32_t kPriorSlot = 2;  // EdgeDev::live of the placeholder a prior leaves in the edge array; EdgeDev::from is then the prior's index
 
 struct LmState {
     double lambda, nu, chi2, chi2_new, rho, scale, cg_relres;
@@ -138,7 +153,61 @@ HD void robustify(double chi2, int kernel, double delta, double* rho, double* rh
     if (kernel == LIO_GRAPH_KERNEL_HUBER) {
         const double s = sqrt(chi2);
         if (!(s <= delta)) { *rho = 2.0 * delta * s - delta * delta; *rho1 = delta / s; }
+    } else if (kernel == LIO_GRAPH_KERNEL_DCS2) {  // RobustKernelDCS2: phi = delta
+        const double p = delta + chi2, s = (2.0 * delta) / p;
+        if (!(s >= 1.0)) { *rho = s * chi2 * s; *rho1 = (4.0 * delta * delta * (delta - chi2)) / (p * p * p); }
     }
+}
+
+HD double az_of(const double x[3]) { return atan2(x[1], x[0]); }
+HD double el_of(const double x[3]) { return atan2(x[2], hypot(x[0], x[1])); }
+// the error of a prior on the node (t, q); for PLANE also what its Jacobian needs: A = Rz(az(n_m)) Ry(-el(n_m)) row-major, n_l = R^T n, u = A^T n_l;
+// for QUAT sgn = the sign that brought q to the measurement's side
+HD void prior_eval(int type, const double t[3], const double q[4], const double m[4], const double plane[4], double e[3], double A[9], double nl[3], double u[3],
+                   double* sgn) {
+    if (type == LIO_GRAPH_PRIOR_XYZ) {
+        e[0] = t[0] - m[0]; e[1] = t[1] - m[1]; e[2] = t[2] - m[2];
+    } else if (type == LIO_GRAPH_PRIOR_QUAT) {
+        const double s = (((m[0] * q[0] + m[1] * q[1]) + m[2] * q[2]) + m[3] * q[3]) < 0 ? -1.0 : 1.0;
+        *sgn = s;
+        e[0] = s * q[0] - m[0]; e[1] = s * q[1] - m[1]; e[2] = s * q[2] - m[2];
+    } else {
+        double R[9];
+        q_to_R(q, R);
+#pragma unroll
+        for (int c = 0; c < 3; c++) nl[c] = (R[c] * plane[0] + R[3 + c] * plane[1]) + R[6 + c] * plane[2];
+        const double dl = plane[3] + ((t[0] * plane[0] + t[1] * plane[1]) + t[2] * plane[2]);
+        // cos and sin of az(n_m) and el(n_m) of the unit normal, without the angles: el's are (h, m_z), az's (m_x, m_y) / h, and (1, 0) when h = 0
+        const double h = hypot(m[0], m[1]);
+        const double cb = h, sb = m[2], ca = h > 0 ? m[0] / h : 1.0, sa = h > 0 ? m[1] / h : 0.0;
+        A[0] = ca * cb; A[1] = -sa; A[2] = -ca * sb;
+        A[3] = sa * cb; A[4] = ca;  A[5] = -sa * sb;
+        A[6] = sb;      A[7] = 0.0; A[8] = cb;
+#pragma unroll
+        for (int c = 0; c < 3; c++) u[c] = (A[c] * nl[0] + A[3 + c] * nl[1]) + A[6 + c] * nl[2];
+        e[0] = az_of(u); e[1] = el_of(u); e[2] = m[3] - dl;
+    }
+}
+HD double prior_chi2(const double e[3], const double* __restrict__ info, double We[3]) {
+    double chi2 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const double s = (info[r * 3] * e[0] + info[r * 3 + 1] * e[1]) + info[r * 3 + 2] * e[2];
+        We[r] = s;
+        chi2 += e[r] * s;
+    }
+    return chi2;
+}
+// rho of a live prior at the current estimate
+HD double prior_rho(const PriorDev& pr, const double* __restrict__ nt, const double* __restrict__ nq) {
+    double t[3], q[4], m[4], pl[4], e[3], A[9], nl[3], u[3], We[3], sgn = 1.0, rho, rho1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] = nt[pr.node * 3ull + k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { q[k] = nq[pr.node * 4ull + k]; m[k] = pr.m[k]; pl[k] = pr.plane[k]; }
+    prior_eval(pr.type, t, q, m, pl, e, A, nl, u, &sgn);
+    robustify(prior_chi2(e, pr.info, We), pr.kernel, pr.delta, &rho, &rho1);
+    return rho;
 }
 // X <- X fromVectorMQT(d), the quaternion renormalised
 HD void apply_delta(double t[3], double q[4], const double d[6]) {
@@ -176,7 +245,7 @@ __global__ void __launch_bounds__(kEdgeThreads) graph_linearize(const EdgeDev* _
     if (!wanted(st, tag)) return;
     for (uint32_t id = blockIdx.x * kEdgeThreads + threadIdx.x; id < E; id += gridDim.x * kEdgeThreads) {
         const EdgeDev& ed = edges[id];
-        if (!ed.live) {
+        if (ed.live != 1) {  // removed, or a prior's placeholder: graph_linearize_prior fills a live prior's slots after this kernel
 #pragma unroll
             for (int k = 0; k < 6; k++) L.err[id * 6ull + k] = 0.0;
             L.chi2[id] = 0.0; L.rho1[id] = 0.0;
@@ -269,6 +338,87 @@ __global__ void __launch_bounds__(kEdgeThreads) graph_linearize(const EdgeDev* _
             }
         }
         atb_store(Ji, T, L.Hii + id * 36ull);
+    }
+}
+
+// one lane per prior (grid-stride): e (three of the id's six slots), chi2, rho', and into the id's Hii / bi slots the 6 x 6 J^T (rho' Omega) J and
+// -J^T (rho' Omega) e of its node.  J is 3 x 6 with one non-zero 3 x 3 half (PLANE: the rotation half and a translation row), so the product is
+// taken on 3 x 3 pieces and the 6 x 6 is never held in registers
+__global__ void __launch_bounds__(kEdgeThreads) graph_linearize_prior(const PriorDev* __restrict__ priors, uint32_t n, const double* __restrict__ nt,
+                                                                      const double* __restrict__ nq, const LmState* __restrict__ st, int tag, LinBuf L) {
+    if (!wanted(st, tag)) return;
+    for (uint32_t k0 = blockIdx.x * kEdgeThreads + threadIdx.x; k0 < n; k0 += gridDim.x * kEdgeThreads) {
+        const PriorDev& pr = priors[k0];
+        if (!pr.live) continue;  // (graph_linearize has zeroed the id's error, chi2 and rho')
+        const uint64_t id = (uint64_t)pr.id;
+        double t[3], q[4], m[4], pl[4], e[3], A[9], nl[3], u[3], We[3], sgn = 1.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) t[k] = nt[pr.node * 3ull + k];
+#pragma unroll
+        for (int k = 0; k < 4; k++) { q[k] = nq[pr.node * 4ull + k]; m[k] = pr.m[k]; pl[k] = pr.plane[k]; }
+        prior_eval(pr.type, t, q, m, pl, e, A, nl, u, &sgn);
+        const double chi2 = prior_chi2(e, pr.info, We);
+        double rho, rho1;
+        robustify(chi2, pr.kernel, pr.delta, &rho, &rho1);
+#pragma unroll
+        for (int k = 0; k < 3; k++) { L.err[id * 6 + k] = e[k]; L.err[id * 6 + 3 + k] = 0.0; }
+        L.chi2[id] = chi2; L.rho1[id] = rho1;
+        // J = [Jt | Jr], each 3 x 3
+        double Jt[9], Jr[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) { Jt[k] = 0.0; Jr[k] = 0.0; }
+        if (pr.type == LIO_GRAPH_PRIOR_XYZ) {
+            q_to_R(q, Jt);
+        } else if (pr.type == LIO_GRAPH_PRIOR_QUAT) {  // s (w I + [v]x)
+            Jr[0] = sgn * q[3];  Jr[1] = -sgn * q[2]; Jr[2] = sgn * q[1];
+            Jr[3] = sgn * q[2];  Jr[4] = sgn * q[3];  Jr[5] = -sgn * q[0];
+            Jr[6] = -sgn * q[1]; Jr[7] = sgn * q[0];  Jr[8] = sgn * q[3];
+        } else {
+            // D = 2 A^T [n_l]x; rows 0 and 1 of Jr are g0 D and g1 D; they stay zero when r^2 = 0
+            const double X[9] = {0.0, -nl[2], nl[1], nl[2], 0.0, -nl[0], -nl[1], nl[0], 0.0};
+            const double r2 = u[0] * u[0] + u[1] * u[1];
+            if (r2 > 0) {
+                const double r = sqrt(r2);
+                const double g0[3] = {-u[1] / r2, u[0] / r2, 0.0};
+                const double g1[3] = {-u[0] * u[2] / r, -u[1] * u[2] / r, r};
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    double D[3];
+#pragma unroll
+                    for (int a = 0; a < 3; a++) D[a] = 2.0 * ((A[a] * X[c] + A[3 + a] * X[3 + c]) + A[6 + a] * X[6 + c]);
+                    Jr[c] = (g0[0] * D[0] + g0[1] * D[1]) + g0[2] * D[2];
+                    Jr[3 + c] = (g1[0] * D[0] + g1[1] * D[1]) + g1[2] * D[2];
+                }
+            }
+            Jt[6] = -nl[0]; Jt[7] = -nl[1]; Jt[8] = -nl[2];
+        }
+        // b = -J^T (rho' Omega e);  H = J^T (rho' Omega) J by halves
+        double* bo = L.bi + id * 6;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            bo[c] = -((Jt[c] * (rho1 * We[0]) + Jt[3 + c] * (rho1 * We[1])) + Jt[6 + c] * (rho1 * We[2]));
+            bo[3 + c] = -((Jr[c] * (rho1 * We[0]) + Jr[3 + c] * (rho1 * We[1])) + Jr[6 + c] * (rho1 * We[2]));
+        }
+        double Tt[9], Tr[9];  // (rho' Omega) Jt, (rho' Omega) Jr
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                Tt[r * 3 + c] = ((rho1 * pr.info[r * 3]) * Jt[c] + (rho1 * pr.info[r * 3 + 1]) * Jt[3 + c]) + (rho1 * pr.info[r * 3 + 2]) * Jt[6 + c];
+                Tr[r * 3 + c] = ((rho1 * pr.info[r * 3]) * Jr[c] + (rho1 * pr.info[r * 3 + 1]) * Jr[3 + c]) + (rho1 * pr.info[r * 3 + 2]) * Jr[6 + c];
+            }
+        }
+        double* Ho = L.Hii + id * 36;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                Ho[r * 6 + c] = (Jt[r] * Tt[c] + Jt[3 + r] * Tt[3 + c]) + Jt[6 + r] * Tt[6 + c];
+                Ho[r * 6 + 3 + c] = (Jt[r] * Tr[c] + Jt[3 + r] * Tr[3 + c]) + Jt[6 + r] * Tr[6 + c];
+                Ho[(3 + r) * 6 + c] = (Jr[r] * Tt[c] + Jr[3 + r] * Tt[3 + c]) + Jr[6 + r] * Tt[6 + c];
+                Ho[(3 + r) * 6 + 3 + c] = (Jr[r] * Tr[c] + Jr[3 + r] * Tr[3 + c]) + Jr[6 + r] * Tr[6 + c];
+            }
+        }
     }
 }
 
@@ -501,14 +651,19 @@ __global__ void __launch_bounds__(256) graph_update(const LmState* __restrict__ 
     for (int k = 0; k < 4; k++) nq[n * 4ull + k] = q[k];
 }
 
-// rho of every edge; one partial per 256 consecutive edges
+// rho of every edge; one partial per 256 consecutive edge ids.  kPriors: an id may be a prior's placeholder, whose rho is taken from the prior
+template <bool kPriors>
 __global__ void __launch_bounds__(kEdgeThreads) graph_chi2(const LmState* __restrict__ st, int tag, const EdgeDev* __restrict__ edges, uint32_t E,
-                                                           const double* __restrict__ nt, const double* __restrict__ nq, double* __restrict__ partial) {
+                                                           const PriorDev* __restrict__ priors, const double* __restrict__ nt, const double* __restrict__ nq,
+                                                           double* __restrict__ partial) {
     if (!wanted(st, tag)) return;
     __shared__ double sh[kEdgeThreads / 64];
     const uint32_t id = blockIdx.x * kEdgeThreads + threadIdx.x;
     double rho = 0.0;
-    if (id < E && edges[id].live) {
+    if (kPriors && id < E && edges[id].live == kPriorSlot) {
+        const PriorDev& pr = priors[edges[id].from];
+        if (pr.live) rho = prior_rho(pr, nt, nq);
+    } else if (id < E && edges[id].live) {
         const EdgeDev& ed = edges[id];
         double ti[3], qi[4], tj[3], qj[4], mt[3], mq[4];
 #pragma unroll
@@ -594,9 +749,12 @@ struct lio_graph {
     lio_graph_params par;
     hipStream_t st = nullptr;
     hipEvent_t ev[kEvents] = {};
-    // host mirror of the topology
-    std::vector<int32_t> from, to;
+    // host mirror of the topology; a prior has to = -1, and pslot = its index in priors (-1 for a binary edge)
+    std::vector<int32_t> from, to, pslot;
     std::vector<uint8_t> live, fixed;
+    std::vector<PriorDev> priors;  // host mirror of every prior ever added; the first n_dev_priors are on the device
+    uint32_t n_dev_priors = 0, prior_cap = 0;
+    PriorDev* d_priors = nullptr;
     // not yet on the device: nodes as 7 doubles, edges
     std::vector<double> pend_nodes;
     std::vector<EdgeDev> pend_edges;
@@ -698,6 +856,18 @@ int flush(lio_graph* g) {
         g->n_dev_edges = E;
         g->pend_edges.clear();
     }
+    const uint32_t NP = (uint32_t)g->priors.size();
+    if (NP > g->n_dev_priors) {
+        if (NP > g->prior_cap) {
+            uint32_t c = g->prior_cap ? g->prior_cap : 256;
+            while (c < NP) c *= 2;
+            int rc = grow_copy(&g->d_priors, g->n_dev_priors, c, g->st);
+            if (rc != LIO_OK) return rc;
+            g->prior_cap = c;
+        }
+        LIO_HIP_TRY(hipMemcpy(g->d_priors + g->n_dev_priors, g->priors.data() + g->n_dev_priors, (NP - g->n_dev_priors) * sizeof(PriorDev), hipMemcpyHostToDevice));
+        g->n_dev_priors = NP;
+    }
     const uint32_t nb = (E + kEdgeThreads - 1) / kEdgeThreads;
     if (nb > g->partial_cap) {
         uint32_t c = g->partial_cap ? g->partial_cap : 64;
@@ -720,7 +890,7 @@ int build_topology(lio_graph* g) {
     std::vector<uint32_t> deg(N, 0);
     g->n_live = 0;
     for (uint32_t e = 0; e < E; e++)
-        if (g->live[e]) { deg[g->from[e]]++; deg[g->to[e]]++; g->n_live++; }
+        if (g->live[e]) { deg[g->from[e]]++; if (g->to[e] >= 0) deg[g->to[e]]++; g->n_live++; }
     std::vector<int32_t> aidx(N, -1);
     g->act.clear();
     for (uint32_t n = 0; n < N; n++)
@@ -730,7 +900,7 @@ int build_topology(lio_graph* g) {
     std::map<std::pair<uint32_t, uint32_t>, std::vector<uint32_t>> pairs;  // (lo, hi) in active indices
     for (uint32_t e = 0; e < E; e++) {
         if (!g->live[e]) continue;
-        const int32_t ai = aidx[g->from[e]], aj = aidx[g->to[e]];
+        const int32_t ai = aidx[g->from[e]], aj = g->to[e] >= 0 ? aidx[g->to[e]] : -1;  // a prior: its block sits in the id's Hii / bi slots
         if (ai >= 0) dl[ai].push_back(e << 1);
         if (aj >= 0) dl[aj].push_back(e << 1 | 1u);
         if (ai >= 0 && aj >= 0) {
@@ -811,7 +981,18 @@ int launch_linearize(lio_graph* g, int tag) {
     if (!E) return LIO_OK;
     hipLaunchKernelGGL(graph_linearize, grid_for(E, kEdgeThreads), kEdgeThreads, 0, g->st, g->d_edges, E, g->d_t, g->d_q, g->d_state, tag, g->lin);
     LIO_HIP_TRY(hipGetLastError());
+    const uint32_t NP = (uint32_t)g->priors.size();
+    if (NP) {  // after graph_linearize on the same stream: it overwrites the zeros that kernel left at the priors' ids
+        hipLaunchKernelGGL(graph_linearize_prior, grid_for(NP, kEdgeThreads), kEdgeThreads, 0, g->st, g->d_priors, NP, g->d_t, g->d_q, g->d_state, tag, g->lin);
+        LIO_HIP_TRY(hipGetLastError());
+    }
     return LIO_OK;
+}
+void launch_chi2(lio_graph* g, int tag, uint32_t nb, uint32_t E) {
+    if (g->priors.empty())
+        hipLaunchKernelGGL(graph_chi2<false>, nb, kEdgeThreads, 0, g->st, g->d_state, tag, g->d_edges, E, g->d_priors, g->d_t, g->d_q, g->d_partial);
+    else
+        hipLaunchKernelGGL(graph_chi2<true>, nb, kEdgeThreads, 0, g->st, g->d_state, tag, g->d_edges, E, g->d_priors, g->d_t, g->d_q, g->d_partial);
 }
 int launch_assemble(lio_graph* g, int tag) {
     if (!g->Na) return LIO_OK;
@@ -827,7 +1008,7 @@ int chi2_now(lio_graph* g, double* out) {
     double c = 0.0;
     if (E) {
         const uint32_t nb = (E + kEdgeThreads - 1) / kEdgeThreads;
-        hipLaunchKernelGGL(graph_chi2, nb, kEdgeThreads, 0, g->st, g->d_state, -1, g->d_edges, E, g->d_t, g->d_q, g->d_partial);
+        launch_chi2(g, -1, nb, E);
         LIO_HIP_TRY(hipGetLastError());
         LIO_HIP_TRY(hipMemcpyAsync(g->h_partial, g->d_partial, nb * sizeof(double), hipMemcpyDeviceToHost, g->st));
         LIO_HIP_TRY(hipStreamSynchronize(g->st));
@@ -843,8 +1024,22 @@ bool pose_ok(const double T[16]) {
     return true;
 }
 
+bool kernel_ok(const char* who, int kernel, double delta) {
+    if (kernel != LIO_GRAPH_KERNEL_NONE && kernel != LIO_GRAPH_KERNEL_HUBER && kernel != LIO_GRAPH_KERNEL_DCS2) { set_error("%s: unknown kernel %d", who, kernel); return false; }
+    if (kernel != LIO_GRAPH_KERNEL_NONE && !(delta > 0)) { set_error("%s: a robust kernel needs a positive delta", who); return false; }
+    return true;
+}
+
+// kernel, delta and live of one prior: the host mirror, and the device's record when it is there already
+int prior_set(lio_graph* g, uint32_t slot, int kernel, double delta, int live) {
+    PriorDev& p = g->priors[slot];
+    p.kernel = kernel; p.delta = delta; p.live = live;
+    if (slot < g->n_dev_priors) LIO_HIP_TRY(hipMemcpy(g->d_priors + slot, &p, sizeof(PriorDev), hipMemcpyHostToDevice));
+    return LIO_OK;
+}
+
 void free_all(lio_graph* g) {
-    hipFree(g->d_t); hipFree(g->d_q); hipFree(g->d_edges); hipFree(g->d_lin); hipFree(g->d_topo); hipFree(g->d_sys); hipFree(g->d_partial); hipFree(g->d_state);
+    hipFree(g->d_t); hipFree(g->d_q); hipFree(g->d_edges); hipFree(g->d_priors); hipFree(g->d_lin); hipFree(g->d_topo); hipFree(g->d_sys); hipFree(g->d_partial); hipFree(g->d_state);
     if (g->h_partial) hipHostFree(g->h_partial);
     if (g->h_state) hipHostFree(g->h_state);
 }
@@ -916,8 +1111,8 @@ int lio_graph_reset(lio_graph* g) {
     if (!g) return LIO_E_INVALID;
     hipSetDevice(g->device);
     LIO_HIP_TRY(hipStreamSynchronize(g->st));
-    g->from.clear(); g->to.clear(); g->live.clear(); g->fixed.clear(); g->pend_nodes.clear(); g->pend_edges.clear();
-    g->n_dev_nodes = g->n_dev_edges = 0;
+    g->from.clear(); g->to.clear(); g->pslot.clear(); g->live.clear(); g->fixed.clear(); g->pend_nodes.clear(); g->pend_edges.clear(); g->priors.clear();
+    g->n_dev_nodes = g->n_dev_edges = g->n_dev_priors = 0;
     g->topo_dirty = true;
     g->Na = g->P = g->n_live = 0;
     memset(&g->rep, 0, sizeof(g->rep));
@@ -960,8 +1155,7 @@ int lio_graph_set_estimate(lio_graph* g, int id, const double pose16[16]) {
 int lio_graph_add_edge(lio_graph* g, int from, int to, const double M16[16], const double info36[36], int kernel, double delta) {
     if (!g || !M16 || !info36 || from < 0 || to < 0 || (uint32_t)from >= num_nodes(g) || (uint32_t)to >= num_nodes(g) || !pose_ok(M16)) return LIO_E_INVALID;
     if (from == to) { set_error("lio_graph_add_edge: an edge from node %d to itself", from); return LIO_E_INVALID; }
-    if (kernel != LIO_GRAPH_KERNEL_NONE && kernel != LIO_GRAPH_KERNEL_HUBER) { set_error("lio_graph_add_edge: unknown kernel %d", kernel); return LIO_E_INVALID; }
-    if (kernel == LIO_GRAPH_KERNEL_HUBER && !(delta > 0)) { set_error("lio_graph_add_edge: Huber needs a positive delta"); return LIO_E_INVALID; }
+    if (!kernel_ok("lio_graph_add_edge", kernel, delta)) return LIO_E_INVALID;
     double amax = 0.0;
     for (int k = 0; k < 36; k++) {
         if (!(info36[k] - info36[k] == 0.0)) { set_error("lio_graph_add_edge: the information matrix is not finite"); return LIO_E_INVALID; }
@@ -970,20 +1164,131 @@ int lio_graph_add_edge(lio_graph* g, int from, int to, const double M16[16], con
     for (int r = 0; r < 6; r++)
         for (int c = r + 1; c < 6; c++)
             if (fabs(info36[r * 6 + c] - info36[c * 6 + r]) > 1e-9 * amax) { set_error("lio_graph_add_edge: the information matrix is not symmetric"); return LIO_E_INVALID; }
-    EdgeDev e;
+    EdgeDev e{};
     e.from = from; e.to = to; e.kernel = kernel; e.live = 1; e.delta = delta;
     T_to_tq(M16, e.mt, e.mq);
     memcpy(e.info, info36, sizeof(e.info));
     g->pend_edges.push_back(e);
-    g->from.push_back(from); g->to.push_back(to); g->live.push_back(1);
+    g->from.push_back(from); g->to.push_back(to); g->pslot.push_back(-1); g->live.push_back(1);
     g->topo_dirty = true;
     return (int)g->from.size() - 1;
+}
+
+int lio_graph_add_prior(lio_graph* g, int node, int type, const double m4[4], const double plane4[4], const double info9[9], int kernel, double delta) {
+    if (!g || !m4 || !info9 || node < 0 || (uint32_t)node >= num_nodes(g)) return LIO_E_INVALID;
+    if (type != LIO_GRAPH_PRIOR_XYZ && type != LIO_GRAPH_PRIOR_QUAT && type != LIO_GRAPH_PRIOR_PLANE) { set_error("lio_graph_add_prior: unknown type %d", type); return LIO_E_INVALID; }
+    if (type == LIO_GRAPH_PRIOR_PLANE && !plane4) { set_error("lio_graph_add_prior: a PLANE prior needs its world plane"); return LIO_E_INVALID; }
+    if (!kernel_ok("lio_graph_add_prior", kernel, delta) || !(delta - delta == 0.0)) return LIO_E_INVALID;
+    PriorDev p{};
+    p.node = node; p.type = type; p.kernel = kernel; p.live = 1; p.delta = delta;
+    const int nm = type == LIO_GRAPH_PRIOR_XYZ ? 3 : 4;
+    for (int k = 0; k < nm; k++) {
+        if (!(m4[k] - m4[k] == 0.0)) { set_error("lio_graph_add_prior: the measurement is not finite"); return LIO_E_INVALID; }
+        p.m[k] = m4[k];
+    }
+    if (type == LIO_GRAPH_PRIOR_QUAT) {  // normalised, w >= 0
+        const double n = sqrt(((p.m[0] * p.m[0] + p.m[1] * p.m[1]) + p.m[2] * p.m[2]) + p.m[3] * p.m[3]);
+        if (!(n > 0) || !(n - n == 0.0)) { set_error("lio_graph_add_prior: a zero quaternion"); return LIO_E_INVALID; }
+        const double s = p.m[3] < 0 ? -1.0 : 1.0;
+        for (int k = 0; k < 4; k++) p.m[k] = s * (p.m[k] / n);
+    } else if (type == LIO_GRAPH_PRIOR_PLANE) {  // both planes divided by the norm of their normal
+        for (int k = 0; k < 4; k++) {
+            if (!(plane4[k] - plane4[k] == 0.0)) { set_error("lio_graph_add_prior: the world plane is not finite"); return LIO_E_INVALID; }
+            p.plane[k] = plane4[k];
+        }
+        for (double* v : {p.m, p.plane}) {
+            const double n = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+            if (!(n > 0) || !(n - n == 0.0)) { set_error("lio_graph_add_prior: a plane with a zero normal"); return LIO_E_INVALID; }
+            for (int k = 0; k < 4; k++) v[k] /= n;
+        }
+    }
+    double amax = 0.0;
+    for (int k = 0; k < 9; k++) {
+        if (!(info9[k] - info9[k] == 0.0)) { set_error("lio_graph_add_prior: the information matrix is not finite"); return LIO_E_INVALID; }
+        amax = fmax(amax, fabs(info9[k]));
+    }
+    for (int r = 0; r < 3; r++)
+        for (int c = r + 1; c < 3; c++)
+            if (fabs(info9[r * 3 + c] - info9[c * 3 + r]) > 1e-9 * amax) { set_error("lio_graph_add_prior: the information matrix is not symmetric"); return LIO_E_INVALID; }
+    memcpy(p.info, info9, sizeof(p.info));
+    p.id = (int32_t)g->from.size();
+    EdgeDev hole{};  // the id's place in the edge array
+    hole.from = (int32_t)g->priors.size(); hole.to = -1; hole.live = kPriorSlot;
+    g->pend_edges.push_back(hole);
+    g->priors.push_back(p);
+    g->from.push_back(node); g->to.push_back(-1); g->pslot.push_back(hole.from); g->live.push_back(1);
+    g->topo_dirty = true;
+    return p.id;
+}
+
+int lio_graph_set_kernel(lio_graph* g, int id, int kernel, double delta) {
+    if (!g || id < 0 || (uint32_t)id >= num_edges(g) || !g->live[id]) return LIO_E_INVALID;
+    if (!kernel_ok("lio_graph_set_kernel", kernel, delta) || !(delta - delta == 0.0)) return LIO_E_INVALID;
+    hipSetDevice(g->device);
+    if (g->pslot[id] >= 0) return prior_set(g, (uint32_t)g->pslot[id], kernel, delta, 1);
+    if ((uint32_t)id >= g->n_dev_edges) {
+        EdgeDev& e = g->pend_edges[(uint32_t)id - g->n_dev_edges];
+        e.kernel = kernel; e.delta = delta;
+        return LIO_OK;
+    }
+    const int32_t k = kernel;
+    LIO_HIP_TRY(hipMemcpy(&g->d_edges[id].kernel, &k, sizeof(k), hipMemcpyHostToDevice));
+    LIO_HIP_TRY(hipMemcpy(&g->d_edges[id].delta, &delta, sizeof(delta), hipMemcpyHostToDevice));
+    return LIO_OK;
+}
+
+int lio_graph_priors(lio_graph* g, int32_t* id, int32_t* node, int32_t* type, double* m4, double* plane4, double* info9, int32_t* kernel, double* delta, uint32_t cap) {
+    if (!g) return LIO_E_INVALID;
+    uint32_t n = 0;
+    for (const PriorDev& p : g->priors) n += p.live ? 1 : 0;
+    if (n > cap) return -(int)n;
+    uint32_t k = 0;
+    for (const PriorDev& p : g->priors) {
+        if (!p.live) continue;
+        if (id) id[k] = p.id;
+        if (node) node[k] = p.node;
+        if (type) type[k] = p.type;
+        if (m4) memcpy(m4 + 4ull * k, p.m, sizeof(p.m));
+        if (plane4) memcpy(plane4 + 4ull * k, p.plane, sizeof(p.plane));
+        if (info9) memcpy(info9 + 9ull * k, p.info, sizeof(p.info));
+        if (kernel) kernel[k] = p.kernel;
+        if (delta) delta[k] = p.delta;
+        k++;
+    }
+    return (int)n;
+}
+
+int lio_graph_prior_error(const double X16[16], int type, const double m4[4], const double plane4[4], double e3[3]) {
+    if (!X16 || !m4 || !e3 || (type != LIO_GRAPH_PRIOR_XYZ && type != LIO_GRAPH_PRIOR_QUAT && type != LIO_GRAPH_PRIOR_PLANE) || (type == LIO_GRAPH_PRIOR_PLANE && !plane4))
+        return LIO_E_INVALID;
+    double t[3], q[4], m[4] = {m4[0], m4[1], m4[2], type == LIO_GRAPH_PRIOR_XYZ ? 0.0 : m4[3]}, pl[4] = {0, 0, 0, 0}, A[9], nl[3], u[3], sgn = 1.0;
+    T_to_tq(X16, t, q);
+    if (type == LIO_GRAPH_PRIOR_QUAT) {
+        const double n = sqrt(((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) + m[3] * m[3]);
+        if (!(n > 0)) return LIO_E_INVALID;
+        const double s = m[3] < 0 ? -1.0 : 1.0;
+        for (int k = 0; k < 4; k++) m[k] = s * (m[k] / n);
+    } else if (type == LIO_GRAPH_PRIOR_PLANE) {
+        memcpy(pl, plane4, sizeof(pl));
+        for (double* v : {m, pl}) {
+            const double n = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+            if (!(n > 0)) return LIO_E_INVALID;
+            for (int k = 0; k < 4; k++) v[k] /= n;
+        }
+    }
+    prior_eval(type, t, q, m, pl, e3, A, nl, u, &sgn);
+    return LIO_OK;
 }
 
 int lio_graph_remove_edge(lio_graph* g, int id) {
     if (!g || id < 0 || (uint32_t)id >= num_edges(g) || !g->live[id]) return LIO_E_INVALID;
     g->live[id] = 0;
     g->topo_dirty = true;
+    if (g->pslot[id] >= 0) {  // the placeholder stays; the prior's own record goes dead
+        hipSetDevice(g->device);
+        const PriorDev& p = g->priors[g->pslot[id]];
+        return prior_set(g, (uint32_t)g->pslot[id], p.kernel, p.delta, 0);
+    }
     if ((uint32_t)id >= g->n_dev_edges) { g->pend_edges[(uint32_t)id - g->n_dev_edges].live = 0; return LIO_OK; }
     hipSetDevice(g->device);
     const int32_t zero = 0;
@@ -1104,7 +1409,7 @@ int lio_graph_optimize(lio_graph* g, int max_iterations, lio_graph_report* repor
                                g->par.cg_epsilon, cg_max);
             hipEventRecord(g->ev[ne++], g->st);
             hipLaunchKernelGGL(graph_update, (Na + 255) / 256, 256, 0, g->st, g->d_state, it, Na, g->d_act, g->d_vec, g->d_t, g->d_q, g->d_bak);
-            hipLaunchKernelGGL(graph_chi2, nb, kEdgeThreads, 0, g->st, g->d_state, it, g->d_edges, E, g->d_t, g->d_q, g->d_partial);
+            launch_chi2(g, it, nb, E);
             hipLaunchKernelGGL(graph_decide, 1, 256, 0, g->st, g->d_state, it, g->d_partial, nb, Na, g->d_act, g->d_bak, g->d_t, g->d_q, max_iterations, g->par.chi2_rel_stop);
             hipEventRecord(g->ev[ne++], g->st);
         }
@@ -1131,6 +1436,47 @@ int lio_graph_optimize(lio_graph* g, int max_iterations, lio_graph_report* repor
     if (report) *report = R;
     if (S.batch != S.iteration) { set_error("lio_graph_optimize: an iteration did not finish on the device"); return LIO_E_STATE; }
     return S.iteration;
+}
+
+int lio_graph_remove_gnss_outliers(lio_graph* g, double max_distance_error, int max_iterations, int32_t* removed_ids, uint32_t cap, lio_graph_report* report) {
+    if (!g || !(max_distance_error > 0)) return LIO_E_INVALID;
+    uint32_t n_live = 0;
+    for (uint32_t e = 0; e < num_edges(g); e++) n_live += g->live[e];
+    if ((int64_t)n_live < (int64_t)g->par.min_edges) return -1;
+    hipSetDevice(g->device);
+    std::vector<uint32_t> gnss;
+    for (uint32_t k = 0; k < g->priors.size(); k++) {
+        const PriorDev& p = g->priors[k];
+        if (!p.live || p.type != LIO_GRAPH_PRIOR_XYZ) continue;
+        const double phi = max_distance_error * max_distance_error * p.info[0];
+        if (!(phi > 0)) { set_error("lio_graph_remove_gnss_outliers: prior %d has no positive information(0, 0)", p.id); return LIO_E_INVALID; }
+        gnss.push_back(k);
+    }
+    for (uint32_t k : gnss) {
+        const PriorDev& p = g->priors[k];
+        int rc = prior_set(g, k, LIO_GRAPH_KERNEL_DCS2, max_distance_error * max_distance_error * p.info[0], 1);
+        if (rc != LIO_OK) return rc;
+    }
+    int rc = lio_graph_optimize(g, max_iterations, report);
+    if (rc < 0) return rc == -1 ? LIO_E_STATE : rc;
+    int removed = 0;
+    if (!gnss.empty()) {
+        const uint32_t E = num_edges(g);
+        std::vector<double> chi2(E);
+        rc = lio_graph_linearize(g, nullptr, chi2.data(), nullptr, E, nullptr, nullptr, 0);
+        if (rc < 0) return rc;
+        for (uint32_t k : gnss) {
+            const PriorDev& p = g->priors[k];
+            if (!((2.0 * p.delta) / (p.delta + chi2[p.id]) < 0.1)) continue;
+            if (removed_ids && (uint32_t)removed < cap) removed_ids[removed] = p.id;
+            rc = lio_graph_remove_edge(g, p.id);
+            if (rc != LIO_OK) return rc;
+            removed++;
+        }
+    }
+    rc = lio_graph_optimize(g, max_iterations, report);
+    if (rc < -1) return rc;
+    return removed;
 }
 
 int lio_graph_last_times(lio_graph* g, double* linearize_us, double* assemble_us, double* solve_us, double* update_us) {

@@ -199,6 +199,14 @@ struct Slam {
     Mat4 odom2map = Mat4::identity();     // trans_odom2map (the values of a Matrix4f)
     bool graph_updated = false;
     size_t graph_loops = 0;               // loop edges of loop_edges already in the graph
+    // the graph's priors (flush_floor_queue, flush_gps_queue: hdl_graph_slam_nodelet.cpp:358-460, 536-594); guarded by kf_mtx
+    bool fix_first_node = true;           // the reference's flag: the first floor or GNSS edge releases node 0
+    lio_ground* floor_ground = nullptr;   // the floor detector of the key frames (a handle of its own: update_odom runs without the GIL)
+    bool floor_plane = false;             // floor_plane_node exists
+    double floor_world[4] = {0, 0, 1, 0}; // its (fixed) estimate
+    double floor_last_distance = 0;       // floor_last_update_distance
+    double gnss_last[3] = {0, 0, 0};      // gps_last_update_pose
+    std::vector<uint8_t> graph_has_gnss;  // keyframe->utm_coord is set
     struct InjectedKeyFrame { std::vector<float> pts; Mat4 pose; uint64_t stamp; double accum; };
     std::deque<InjectedKeyFrame> injected;  // test visibility: key frames handed to update_odom() without the front end (_push_keyframe)
 };
@@ -618,6 +626,7 @@ void deinit_slam() {
     if (g->keyframer) lio_keyframer_destroy(g->keyframer);
     if (g->loop) lio_loop_destroy(g->loop);
     if (g->graph) lio_graph_destroy(g->graph);
+    if (g->floor_ground) lio_ground_destroy(g->floor_ground);
     g->loc.reset(nullptr);
     g.reset(nullptr);
 }
@@ -937,6 +946,50 @@ py::dict odoms_to_pydict(const std::vector<std::pair<int, Mat4>>& odoms) {
     }
     return d;
 }
+uint32_t ground_seed_now();  // the seed of set_ground_extraction (below)
+// the graph starts over: so do its priors' bookkeeping
+void graph_prior_state_reset(Slam* s) {
+    s->fix_first_node = true;
+    s->floor_plane = false;
+    s->floor_last_distance = 0;
+    s->gnss_last[0] = s->gnss_last[1] = s->gnss_last[2] = 0;
+    s->graph_has_gnss.clear();
+}
+// "Release the first node" (hdl_graph_slam_nodelet.cpp:448-455, 581-588)
+void release_first_node(Slam* s, const char* who) {
+    if (!s->fix_first_node) return;
+    s->fix_first_node = false;
+    if (lio_graph_num_nodes(s->graph) > 0) require(lio_graph_set_fixed(s->graph, 0, 0) == LIO_OK, who);
+}
+// flush_floor_queue (hdl_graph_slam_nodelet.cpp:536-594) for one key frame that has just entered the graph.  The reference's floor detector is a
+// thread of its own that fills floor_coeffs_queue; here the key frame's cloud as popped goes through lio_ground_detect_host (preset 1: the floor
+// detector's parameters, the seed of set_ground_extraction) at this point.  The plane vertex is always fixed in the reference (:563), so the
+// edge carries the world plane and the graph has no plane vertex
+void floor_constraint(Slam* s, int node, const float* pts, uint64_t n, double accum) {
+    if (!s->floor_ground) {
+        s->floor_ground = lio_ground_create(0);
+        require(s->floor_ground != nullptr, "update_odom: lio_ground_create failed");
+    }
+    lio_ground_params gp;
+    lio_ground_default_params(&gp, 1);
+    gp.seed = ground_seed_now();
+    int found = 0;
+    float coeffs[4];
+    require(lio_ground_detect_host(s->floor_ground, pts, n, &gp, &found, coeffs, nullptr, nullptr, nullptr) == LIO_OK, "update_odom: floor detection failed");
+    if (!found) return;
+    if (s->floor_plane && (accum - s->floor_last_distance) < 100.0) return;
+    if (!s->floor_plane) {
+        const double h = s->fix_first_node ? 0.0 : s->graph_pose[(size_t)node].m[11];  // floor_height
+        s->floor_world[0] = 0; s->floor_world[1] = 0; s->floor_world[2] = 1; s->floor_world[3] = -h;
+        s->floor_plane = true;
+    }
+    s->floor_last_distance = accum;
+    const double m[4] = {coeffs[0], coeffs[1], coeffs[2], coeffs[3]};
+    const double info[9] = {0.1, 0, 0, 0, 0.1, 0, 0, 0, 0.1};  // Identity / floor_edge_stddev (10.0)
+    require(lio_graph_add_prior(s->graph, node, LIO_GRAPH_PRIOR_PLANE, m, s->floor_world, info, LIO_GRAPH_KERNEL_HUBER, 1.0) >= 0, "update_odom: lio_graph_add_prior failed");
+    release_first_node(s, "update_odom: lio_graph_set_fixed failed");
+}
+
 // update_odom (slam_wrapper.cpp:105-130): the key frames cloud_callback elected since the last call, as keyframe_to_pydict's entries (:114-125:
 // points N x 4 f32 with the intensity as stored, image {}, pose 4 x 4, stamp); "odoms" stays empty without a pose graph (odom -> map is the identity)
 // Lock order: kf_mtx is only ever taken with the GIL RELEASED (process() does so too).  A thread that waited for the mutex while it held the GIL
@@ -993,12 +1046,14 @@ py::dict update_odom() {
                 if (node == 0) require(lio_graph_set_fixed(g->graph, 0, 1) == LIO_OK, "update_odom: lio_graph_set_fixed failed");  // fix_first_node
                 g->graph_odom.push_back(f.pose);
                 g->graph_pose.push_back(node_pose);
+                g->graph_has_gnss.push_back(0);
                 if (node > 0) {  // the edge key frame -> previous: relative_pose = odom^-1 * prev.odom, the pair's information, no kernel
                     const Mat4 relp = mul(rigid_inverse(f.pose), g->graph_odom[(size_t)node - 1]);
                     double info[36];
                     require(lio_loop_pair_information(g->loop, node, node - 1, relp.m, nullptr, nullptr, info) == LIO_OK, "update_odom: lio_loop_pair_information failed");
                     require(lio_graph_add_edge(g->graph, node, node - 1, relp.m, info, LIO_GRAPH_KERNEL_NONE, 1.0) >= 0, "update_odom: lio_graph_add_edge failed");
                 }
+                if (g->ground_constraint) floor_constraint(g.get(), node, f.pts.data(), (uint64_t)f.n, accum);
             } else if (g->loop_detection) {  // the key frame joins the detector's bank (new_keyframes); one with fewer than k points is left out (lio_last_warning)
                 if (!g->loop) {
                     g->loop = lio_loop_create(0, &g->loop_par);
@@ -1129,6 +1184,7 @@ void set_loop_config(py::dict cfg) {
     g->graph_odom.clear(); g->graph_pose.clear();
     g->graph_loops = 0;
     g->graph_updated = false;
+    graph_prior_state_reset(g.get());
 }
 // the loop edges found so far: what the reference hands to add_se3_edge (key1 = the new frame, key2, the relative pose, the score's information matrix)
 py::list get_loop_edges() {
@@ -1212,6 +1268,10 @@ GraphEdges graph_edges_snapshot() {
     if (n > 0) {
         e.from.resize(n); e.to.resize(n); e.id.resize(n);
         require(lio_graph_edges(g->graph, e.from.data(), e.to.data(), e.id.data(), (uint32_t)n) == n, "lio_graph_edges failed");
+        size_t k = 0;  // EdgeSE3 only (hdl_graph_slam_nodelet.cpp:849): a prior (to = -1) is not listed
+        for (int i = 0; i < n; i++)
+            if (e.to[i] >= 0) { e.from[k] = e.from[i]; e.to[k] = e.to[i]; e.id[k] = e.id[i]; k++; }
+        e.from.resize(k); e.to.resize(k); e.id.resize(k);
     }
     const int nn = lio_graph_num_nodes(g->graph);
     if (nn > 0) {
@@ -1294,7 +1354,14 @@ py::array_t<float> pointcloud_align(py::array_t<float>& source_point, py::array_
         for (int i = 0; i < 16; i++) o(i / 4, i % 4) = (float)T[i];
     return out;
 }
-void set_mapping_ground_constraint(bool enable) { if (g) g->ground_constraint = enable; }
+// set_ground_constraint (hdl_graph_slam_nodelet.cpp:773-781): a toggle starts a new floor plane with the next floor edge
+void set_mapping_ground_constraint(bool enable) {
+    if (!g) return;
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    if (g->ground_constraint != enable) g->floor_plane = false;
+    g->ground_constraint = enable;
+}
 bool get_mapping_ground_constraint() { return g ? g->ground_constraint : false; }
 void set_mapping_constraint(bool loop_closure, bool gravity_constraint) { if (g) { g->loop_closure = loop_closure; g->gravity_constraint = gravity_constraint; } }
 void set_map_colouration(bool enable) { if (g) g->colouration = enable; }
@@ -1320,7 +1387,15 @@ void del_graph_edge(int id) {
     if (!g) return;
     py::gil_scoped_release rel;
     std::lock_guard<std::mutex> kl(g->kf_mtx);
-    if (g->graph) require(lio_graph_remove_edge(g->graph, id) == LIO_OK, "del_graph_edge: no such edge");
+    if (!g->graph) return;
+    const int np = -lio_graph_priors(g->graph, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    if (np > 0) {  // EdgeSE3 only (hdl_graph_slam_nodelet.cpp:961): a prior's id is ignored
+        std::vector<int32_t> ids((size_t)np);
+        require(lio_graph_priors(g->graph, ids.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t)np) == np, "del_graph_edge: lio_graph_priors failed");
+        for (int32_t p : ids)
+            if (p == id) return;
+    }
+    require(lio_graph_remove_edge(g->graph, id) == LIO_OK, "del_graph_edge: no such edge");
 }
 void set_graph_vertex_fix(int id, bool fix) {
     if (!g) return;
@@ -1341,7 +1416,100 @@ py::dict run_graph_optimization() {
     }
     return odoms_to_pydict(odoms);
 }
-py::dict run_robust_graph_optimization(std::string mode) { (void)mode; return py::dict(); }
+// robust_graph_optimize (hdl_graph_slam_nodelet.cpp:1000-1038): the GNSS outlier stage at 1.0 m (DCS2 on every GNSS prior, optimise, drop the
+// priors whose scale fell below 0.1, optimise), then what run_graph_optimization does; {} without a graph.  The "GNSS moment" stage of mode
+// "mapping" (:1039-1081) needs a 3-DoF point vertex and is not built: both modes run the same stage
+py::dict run_robust_graph_optimization(std::string mode) {
+    (void)mode;
+    std::vector<std::pair<int, Mat4>> odoms;
+    if (g) {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        if (g->graph && !g->graph_odom.empty()) {
+            require(lio_graph_remove_gnss_outliers(g->graph, 1.0, 1024, nullptr, 0, nullptr) >= -1, "run_robust_graph_optimization: lio_graph_remove_gnss_outliers failed");
+            graph_optimize_locked(g.get(), "run_robust_graph_optimization");
+            for (size_t k = 0; k < g->graph_pose.size(); k++) odoms.emplace_back((int)k, g->graph_pose[k]);
+        }
+    }
+    return odoms_to_pydict(odoms);
+}
+// not in the reference's module: one GNSS fix for key frame `id`, what flush_gps_queue (hdl_graph_slam_nodelet.cpp:398-455) does once it has
+// matched a fix to a key frame -- xyz (metres, already in the map's projection; z ignored for dimension 2), the fix's precision and dimension
+// (2, 3 or 6), for dimension 6 the orientation as a quaternion (x, y, z, w).  The distance gate against the last accepted fix (10 / 20 / 50 m by
+// precision), the information matrices, Huber 1.0, the release of node 0.  The UTM projection, the RTK queue and the interpolation between two
+// fixes in time stay out of scope.  The ids of the edges added: [] when the gate refuses the fix, the key frame has one already, or there is no graph
+std::vector<int> add_graph_gnss(int id, py::array_t<double, py::array::c_style | py::array::forcecast> xyz_in, double precision, int dimension, py::object orientation) {
+    std::vector<int> added;
+    if (!g) return added;
+    require(xyz_in.size() == 3, "add_graph_gnss: xyz has 3 entries");
+    require(dimension == 2 || dimension == 3 || dimension == 6, "add_graph_gnss: dimension is 2, 3 or 6");
+    require(precision > 0, "add_graph_gnss: precision must be positive");
+    double xyz[3] = {xyz_in.data()[0], xyz_in.data()[1], dimension == 2 ? 0.0 : xyz_in.data()[2]};
+    double quat[4] = {0, 0, 0, 1};
+    if (dimension == 6) {
+        require(!orientation.is_none(), "add_graph_gnss: dimension 6 needs an orientation (x, y, z, w)");
+        auto q = py::cast<py::array_t<double, py::array::c_style | py::array::forcecast>>(orientation);
+        require(q.size() == 4, "add_graph_gnss: the orientation is a quaternion (x, y, z, w)");
+        for (int k = 0; k < 4; k++) quat[k] = q.data()[k];
+    }
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    if (!g->graph || id < 0 || (size_t)id >= g->graph_has_gnss.size() || g->graph_has_gnss[(size_t)id]) return added;
+    const double threshold = precision < 100.0 ? 10.0 : (precision < 1000.0 ? 20.0 : 50.0);
+    const double* last = g->gnss_last;
+    const double d[3] = {last[0] - xyz[0], last[1] - xyz[1], last[2] - xyz[2]};
+    if (std::sqrt(last[0] * last[0] + last[1] * last[1] + last[2] * last[2]) > 0 && std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) < threshold) return added;
+    double info[9] = {1.0 / precision, 0, 0, 0, 1.0 / precision, 0, 0, 0, 1.0 / precision};
+    if (dimension == 2) {
+        const double n2 = xyz[0] * xyz[0] + xyz[1] * xyz[1] + xyz[2] * xyz[2];
+        require(n2 > 0, "add_graph_gnss: a 2-D fix at the origin has no information for z");
+        info[8] = 1.0 / n2;  // 1 / (xyz.norm() * xyz.norm())
+    }
+    const double m[4] = {xyz[0], xyz[1], xyz[2], 0.0};
+    int e = lio_graph_add_prior(g->graph, id, LIO_GRAPH_PRIOR_XYZ, m, nullptr, info, LIO_GRAPH_KERNEL_HUBER, 1.0);
+    require(e >= 0, "add_graph_gnss: lio_graph_add_prior failed");
+    added.push_back(e);
+    if (dimension == 6) {
+        const double r = 1.0 / (precision * 10.0);  // gps_rot_stddev
+        const double rinfo[9] = {r, 0, 0, 0, r, 0, 0, 0, r};
+        e = lio_graph_add_prior(g->graph, id, LIO_GRAPH_PRIOR_QUAT, quat, nullptr, rinfo, LIO_GRAPH_KERNEL_HUBER, 1.0);
+        require(e >= 0, "add_graph_gnss: lio_graph_add_prior failed");
+        added.push_back(e);
+    }
+    g->graph_has_gnss[(size_t)id] = 1;
+    for (int k = 0; k < 3; k++) g->gnss_last[k] = xyz[k];
+    release_first_node(g.get(), "add_graph_gnss: lio_graph_set_fixed failed");
+    return added;
+}
+// test visibility: the graph's live priors as lio_graph_priors returns them
+py::list _graph_priors() {
+    std::vector<int32_t> id, node, type, kernel;
+    std::vector<double> m, plane, info, delta;
+    int n = 0;
+    if (g) {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        if (g->graph) {
+            n = -lio_graph_priors(g->graph, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+            if (n > 0) {
+                id.resize(n); node.resize(n); type.resize(n); kernel.resize(n); delta.resize(n);
+                m.resize(4 * (size_t)n); plane.resize(4 * (size_t)n); info.resize(9 * (size_t)n);
+                require(lio_graph_priors(g->graph, id.data(), node.data(), type.data(), m.data(), plane.data(), info.data(), kernel.data(), delta.data(), (uint32_t)n) == n,
+                        "_graph_priors: lio_graph_priors failed");
+            }
+        }
+    }
+    py::list out;
+    for (int k = 0; k < n; k++) {
+        py::dict d;
+        d["id"] = id[k]; d["node"] = node[k]; d["type"] = type[k]; d["kernel"] = kernel[k]; d["delta"] = delta[k];
+        d["measurement"] = py::array_t<double>(4, &m[4 * (size_t)k]);
+        d["plane"] = py::array_t<double>(4, &plane[4 * (size_t)k]);
+        d["information"] = py::array_t<double>(std::vector<py::ssize_t>{3, 3}, &info[9 * (size_t)k]);
+        out.append(d);
+    }
+    return out;
+}
 // dump_keyframe (graph_utils.cpp:123-131): KeyFrame(stamp, id, pose, numpy_to_pointcloud(points, 255.0)).save(directory) -- `data` + `cloud.pcd`,
 // the files the localisation mode loads its map from
 void dump_keyframe(const std::string& directory, uint64_t stamp, int id, py::array_t<float>& points_input, py::array_t<float>& pose_input) {
@@ -1557,6 +1725,7 @@ void set_ground_extraction(bool enable, uint32_t seed) {
     g_acc.ground_on = enable;
     g_acc.ground_seed = seed;
 }
+uint32_t ground_seed_now() { return g_acc.ground_seed; }
 void accumulate_cloud(py::array_t<float>& points, py::dict& points_attr, py::array_t<double>& poses, std::string odometry_type, bool extract_ground) {
     if (odometry_type != "TUM")
         throw std::invalid_argument("slam_wrapper: accumulate_cloud: odometry_type '" + odometry_type + "' is not supported (only \"TUM\"; the reference indexes an empty pose list)");
@@ -1975,6 +2144,9 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("set_graph_vertex_fix", &set_graph_vertex_fix, "set graph vertex fix", py::arg("id"), py::arg("fix"));
     m.def("run_graph_optimization", &run_graph_optimization, "run graph optimization");
     m.def("run_robust_graph_optimization", &run_robust_graph_optimization, "run robust graph optimization", py::arg("mode"));
+    m.def("add_graph_gnss", &add_graph_gnss, "one GNSS fix for a key frame of the pose graph; the ids of the edges added", py::arg("id"), py::arg("xyz"), py::arg("precision"),
+          py::arg("dimension"), py::arg("orientation") = py::none());
+    m.def("_graph_priors", &_graph_priors, "test visibility: the pose graph's live priors");
     m.def("dump_keyframe", &dump_keyframe, "dump keyframe", py::arg("directory"), py::arg("stamp"), py::arg("id"), py::arg("points_input"), py::arg("pose_input"));
     m.def("dump_odometry", &dump_odometry, "dump odometry", py::arg("directory"));
     m.def("set_export_map_config", &set_export_map_config, "set export map config", py::arg("z_min"), py::arg("z_max"), py::arg("color"));

@@ -61,6 +61,7 @@ SYMBOLS = [
     "lio_graph_default_params", "lio_graph_create", "lio_graph_destroy", "lio_graph_reset", "lio_graph_add_node", "lio_graph_set_fixed", "lio_graph_set_estimate",
     "lio_graph_num_nodes", "lio_graph_get_fixed", "lio_graph_add_edge", "lio_graph_remove_edge", "lio_graph_optimize", "lio_graph_estimates", "lio_graph_edges",
     "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
+    "lio_graph_add_prior", "lio_graph_set_kernel", "lio_graph_priors", "lio_graph_prior_error", "lio_graph_remove_gnss_outliers",
 ]
 
 
@@ -156,6 +157,8 @@ class GraphReport(C.Structure):  # lio_graph_report
 
 
 GRAPH_KERNEL_NONE, GRAPH_KERNEL_HUBER = 0, 1
+GRAPH_KERNEL_DCS2 = 2
+GRAPH_PRIOR_XYZ, GRAPH_PRIOR_QUAT, GRAPH_PRIOR_PLANE = 0, 1, 2
 
 
 class BevInfo(C.Structure):  # lio_bev_info
@@ -458,6 +461,11 @@ def lib():
     sig("lio_se3_from_mqt", None, f64p, f64p)
     sig("lio_se3_to_mqt", None, f64p, f64p)
     sig("lio_graph_edge_error", cint, f64p, f64p, f64p, f64p)
+    sig("lio_graph_add_prior", cint, vp, cint, cint, f64p, f64p, f64p, cint, dbl)
+    sig("lio_graph_set_kernel", cint, vp, cint, cint, dbl)
+    sig("lio_graph_priors", cint, vp, i32p, i32p, i32p, f64p, f64p, f64p, i32p, f64p, u32)
+    sig("lio_graph_prior_error", cint, f64p, cint, f64p, f64p, f64p)
+    sig("lio_graph_remove_gnss_outliers", cint, vp, dbl, cint, i32p, u32, gr)
     sig("lio_state_boxplus", None, f64p, f64p, f64p)
     sig("lio_state_boxminus", None, f64p, f64p, f64p)
     _lib = L

@@ -803,6 +803,8 @@ class PoseGraph:
     OptimizationAlgorithmLevenberg runs it, the linear solve by block-Jacobi conjugate gradients.  Keyword arguments override lio_graph_params."""
 
     NONE, HUBER = capi.GRAPH_KERNEL_NONE, capi.GRAPH_KERNEL_HUBER
+    DCS2 = capi.GRAPH_KERNEL_DCS2
+    XYZ, QUAT, PLANE = capi.GRAPH_PRIOR_XYZ, capi.GRAPH_PRIOR_QUAT, capi.GRAPH_PRIOR_PLANE
     STOPS = {0: "none", 1: "max_iterations", 2: "trials", 3: "rho_zero", 4: "lambda", 5: "chi2_rel"}
 
     def __init__(self, device=0, **params):
@@ -869,6 +871,55 @@ class PoseGraph:
 
     def remove_edge(self, eid):
         check(lib().lio_graph_remove_edge(self.h, int(eid)), "graph remove_edge")
+
+    @staticmethod
+    def _prior_args(kind, measurement, plane):
+        m = np.zeros(4)
+        v = f64(measurement).ravel()
+        m[:len(v)] = v
+        pl = f64(plane).ravel() if plane is not None else None
+        return m, pl, (ptr(pl, C.c_double) if pl is not None else None)
+
+    @staticmethod
+    def prior_error(pose, kind, measurement, plane=None):
+        X, e = f64(pose).reshape(4, 4), np.zeros(3)
+        m, pl, plp = PoseGraph._prior_args(kind, measurement, plane)
+        check(lib().lio_graph_prior_error(ptr(X, C.c_double), int(kind), ptr(m, C.c_double), plp, ptr(e, C.c_double)), "graph prior_error")
+        return e
+
+    def add_prior(self, node, kind, measurement, information, kernel=0, delta=1.0, plane=None):
+        """a unary edge on one node: XYZ (x, y, z), QUAT (x, y, z, w) or PLANE (n, d in the node's frame, with the world plane); -> its edge id"""
+        m, pl, plp = self._prior_args(kind, measurement, plane)
+        W = f64(information).reshape(3, 3)
+        return check(lib().lio_graph_add_prior(self.h, int(node), int(kind), ptr(m, C.c_double), plp, ptr(W, C.c_double), int(kernel), float(delta)), "graph add_prior")
+
+    def set_kernel(self, eid, kernel, delta=1.0):
+        check(lib().lio_graph_set_kernel(self.h, int(eid), int(kernel), float(delta)), "graph set_kernel")
+
+    def priors(self):
+        """the live priors in rising id: a list of dicts (id, node, type, measurement (4,), plane (4,), information (3, 3), kernel, delta)"""
+        n = abs(lib().lio_graph_priors(self.h, None, None, None, None, None, None, None, None, 0))
+        c = max(n, 1)
+        i, nd, ty, kn = (np.zeros(c, np.int32) for _ in range(4))
+        m, pl, W, dl = np.zeros((c, 4)), np.zeros((c, 4)), np.zeros((c, 3, 3)), np.zeros(c)
+        check(lib().lio_graph_priors(self.h, ptr(i, C.c_int32), ptr(nd, C.c_int32), ptr(ty, C.c_int32), ptr(m, C.c_double), ptr(pl, C.c_double), ptr(W, C.c_double),
+                                     ptr(kn, C.c_int32), ptr(dl, C.c_double), c), "graph priors")
+        return [dict(id=int(i[k]), node=int(nd[k]), type=int(ty[k]), measurement=m[k].copy(), plane=pl[k].copy(), information=W[k].copy(), kernel=int(kn[k]),
+                     delta=float(dl[k])) for k in range(n)]
+
+    def remove_gnss_outliers(self, max_distance_error=1.0, max_iterations=1024):
+        """the GNSS outlier stage -> (ids removed, or None when the graph has fewer than min_edges live edges; the second optimisation's report)"""
+        cap = max(len(self.edges()[0]), 1)
+        ids, rep = np.zeros(cap, np.int32), capi.GraphReport()
+        below = len(self.edges()[0]) < self.params.min_edges
+        n = lib().lio_graph_remove_gnss_outliers(self.h, float(max_distance_error), int(max_iterations), ptr(ids, C.c_int32), cap, C.byref(rep))
+        if n == -1 and below:
+            return None, {}
+        check(n, "graph remove_gnss_outliers")
+        d = {k: getattr(rep, k) for k, _ in capi.GraphReport._fields_}
+        d["lambda"] = d.pop("lambda_")
+        d["stop"] = self.STOPS.get(rep.stop_reason, str(rep.stop_reason))
+        return [int(x) for x in ids[:n]], d
 
     @property
     def num_nodes(self):
