@@ -67,8 +67,11 @@ int lio_device_count(void);
  * on the device; the information matrix of two bank frames under a relative pose);
  * 14 = lio_scan_undistort_imu (test visibility: the FastLIO front half's point filter and IMU backward propagation on caller-supplied poses).
  * 15 = lio_graph_add_prior / set_kernel / priors / prior_error / remove_gnss_outliers, LIO_GRAPH_KERNEL_DCS2 (the pose graph's unary edges: GNSS
- *      position, orientation and floor-plane priors, the DCS2 kernel, the GNSS outlier stage of robust_graph_optimize). */
-#define LIO_ABI_VERSION 15
+ *      position, orientation and floor-plane priors, the DCS2 kernel, the GNSS outlier stage of robust_graph_optimize).
+ * 16 = lio_overlap_* (overlap detection between two maps over a lio_loop bank: candidate search over the graph's connections, the range-gated
+ *      fitness for many pairs, FAST_VGICP for arbitrary (target, source) pairs in one set of rounds, the fine target accumulated on the device,
+ *      one detect() call over a fragment of new key frames). */
+#define LIO_ABI_VERSION 16
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1151,6 +1154,133 @@ int lio_loop_align_fine(lio_loop*, int target_id, int source_id, const double gu
  * exact nearest neighbours; max_range = DBL_MAX, so every point with a neighbour counts; sums and ties by the fitness rules above; the score
  * then goes through lio_loop_information_matrix.  score, nr, info36 may be NULL */
 int lio_loop_pair_information(lio_loop*, int id1, int id2, const double relpose[16], double* score, uint32_t* nr, double info36[36]);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * Overlap detection between two maps on the device (csrc/overlap.hip): OverlapDetector of the reference's map merge
+ * (slam/localization/include/overlap_merge.hpp, "OM" below; its caller is MapLoader::mergeMapSLAM, slam/localization/src/map_loader.cpp:82-169).
+ * The handle works over a lio_loop bank: the key frames of BOTH maps are added with lio_loop_add_keyframe_host and addressed by bank id; poses
+ * are the bank's (lio_loop_set_pose); the coarse matcher's parameters are the bank's.  The bank outlives the handle's use and is not owned by it.
+ *   candidates  find_candidates (OM:113-145): the knn nearest key-frame positions by rising distance; the same id and an id already connected
+ *               to the new one are passed over; d2 < distance_thresh^2 (strict); connection_count >= candidate_link_dist; at most
+ *               max_candidate_num.  THE PROJECT'S RULES (FLANN leaves them open): positions rounded to f32 (pcl::PointXYZ),
+ *               d2 = ((dx*dx) + dy*dy) + dz*dz in f32, equal distances go to the smaller index.
+ *   connection_count  get_connection_count (OM:265-296), statement for statement: LEVELS of a breadth-first walk are counted, not hops; a node
+ *               is marked visited when it is popped, so it can be queued more than once; the walk ends at count >= max_count (max_count > 0)
+ *               and returns the count reached when the queue runs dry -- a new map whose component is shallower than candidate_link_dist
+ *               levels from the new frame therefore yields no candidate.  That is the reference's behaviour and is kept.
+ *   gate        calc_fitness_score (OM:225-263): the target filtered by sqrt(x^2 + y^2) < xy_range && z > min_z in its own order (stream
+ *               compaction, then an exact index over what is left); every source point moved by T.cast<float>() (terms left to right, the rule
+ *               of the loop detector's fitness), filtered by the same rule; for the survivors the exact nearest target point by the f32 d2
+ *               with d2 <= max_range (on the SQUARED distance).  score = sum / nr (DBL_MAX when nr = 0), n_in = survivors of the source,
+ *               inlier ratio = nr / n_in.  THE PROJECT'S RULES: the filter's distance is f32 sqrtf((x*x) + (y*y)), each product and the sum
+ *               rounded, compared with xy_range rounded to f32 (the reference's filter() takes floats); both comparisons strict; a point that is
+ *               not finite never survives; f64 sums per 256 consecutive source points and then over those records in order; ties to the
+ *               smaller index.
+ *   align_pairs FAST_VGICP for n arbitrary (target, source) pairs of bank frames in ONE set of rounds: the Gaussian voxels of every distinct
+ *               target are built once by the bank's engine and copied into a pool that lives for the call; the per-point arithmetic, the LM
+ *               step, the table workgroup -> (slot, first point) and the batch rules are lio_loop_align_candidates': a pair's numbers are
+ *               bit-identical to that call on its target alone, whatever its place and neighbours.
+ *   accumulate  OM:186-194: the best frame's points, then each neighbour's in the order given (the caller passes rising id: std::set order) moved
+ *               by best.pose^-1 * neighbour.pose in f64 (inverse R^T, -(R^T t); every sum of three products left to right) with the Matrix4d rule
+ *               of lio_cloud_append_* (f64 per point, terms left to right, cast to f32); then the regularised k-NN covariances of the merged
+ *               cloud (the path of lio_gicp_set_target) on an engine sized max_accum_points.  LIO_E_CAPACITY beyond that size.
+ *   detect      one detect() call (OM:63-110, 147-211) over a fragment of new frames with poses and connections frozen: candidates per new
+ *               frame; the gate for every (new, candidate) pair with guess = (new^-1 * candidate).cast<float>() -- no renormalisation and no
+ *               guess(2,3) = 0, unlike the loop detector's guess -- at gate_max_range, pairs with ratio < fitness_inlier_thresh dropped; ONE
+ *               align_pairs over all surviving pairs of the fragment; getFitnessScore(fitness_score_max_range) of the converged pairs (PCL's
+ *               ungated score, the loop detector's kernel); per new frame a candidate replaces the best unless score > best_score (an equal
+ *               score takes the LATER one; no 2 x threshold gate); then per new frame with a best: accumulate, FAST_GICP (target = the
+ *               accumulated cloud, source = the new frame, guess = Isometry3f(relative_pose).inverse() in f32 as R^T, -(R^T t), max
+ *               correspondence distance fine_max_corr_dist, translation epsilon fine_translation_epsilon = 0.001 (OM:60)); not converged: no
+ *               overlap; score = gate(accumulated, new, relative_pose, fitness_score_max_range).score; score > fitness_score_thresh: no overlap.
+ * DEVIATIONS.  (1) OM:189 looks a neighbour of the best frame up with std::map::operator[]: a neighbour that is not a frame of the reference map
+ * (a new-map frame linked by an earlier fragment's overlap edge) silently becomes index 0 and frame 0 enters the target.  Such a neighbour is
+ * SKIPPED here.  (2), (3) inherited from lio_loop_*: the coarse matcher is the non-CUDA branch (FAST_VGICP) and setMaxProcessTime does not
+ * apply; an alignment whose H is zero ends NOT converged (ldlt_solve6).  (4) the reference's accumulated target has no size limit; in detect a
+ * best frame whose neighbourhood exceeds max_accum_points keeps the neighbours that fit, in std::set order, and the report counts the rest (the
+ * stage door lio_overlap_accumulate returns LIO_E_CAPACITY instead).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_overlap lio_overlap;
+typedef struct lio_overlap_params {
+    double distance_thresh;            /* 30 (OM:46) */
+    int32_t candidate_link_dist;       /* 10 */
+    int32_t max_candidate_num;         /* 3 */
+    int32_t knn;                       /* 10 (OM:120) */
+    float min_z;                       /* 0.5f (OM:227) */
+    double fitness_score_max_range;    /* 25, compared with a squared distance */
+    double fitness_score_thresh;       /* 1.5 */
+    double fitness_inlier_thresh;      /* 0.2 */
+    double gate_max_range;             /* 1.0 (OM:160) */
+    double xy_range;                   /* 100 (OM:226) */
+    double fine_max_corr_dist;         /* 0.5 (OM:59) */
+    double fine_translation_epsilon;   /* 0.001 (OM:60); not the loop detector's 0.01 */
+    uint32_t max_accum_points;         /* 8 x the bank's max_points */
+    uint32_t pad;
+} lio_overlap_params;
+typedef struct lio_overlap_edge {
+    int32_t key1, key2;          /* bank ids: the best frame of the reference map; the new frame */
+    float relative_pose[16];     /* getFinalTransformation of the fine matcher, row-major: key2's frame -> key1's frame */
+    double score;                /* the gated fitness of the fine result */
+    double information[36];      /* lio_loop_information_matrix(score) */
+} lio_overlap_edge;
+#define LIO_OVERLAP_FOUND 0
+#define LIO_OVERLAP_NO_CANDIDATE 1
+#define LIO_OVERLAP_GATE 2                /* every candidate's inlier ratio < fitness_inlier_thresh */
+#define LIO_OVERLAP_COARSE 3              /* no candidate that passed the gate converged */
+#define LIO_OVERLAP_FINE_NOT_CONVERGED 4
+#define LIO_OVERLAP_FINE_SCORE 5          /* fine score > fitness_score_thresh */
+#define LIO_OVERLAP_ACCUM (-1)            /* lio_overlap_gate_batch's target_id for the cloud of the last lio_overlap_accumulate */
+typedef struct lio_overlap_report {
+    int32_t new_id;              /* bank id of the new frame */
+    int32_t n_candidates;
+    int32_t best;                /* index into the candidate list; -1: none */
+    int32_t fine_converged, fine_iterations;
+    int32_t reason;              /* LIO_OVERLAP_* */
+    uint32_t n_accum;            /* points of the fine target; 0: not built */
+    int32_t n_neighbours_skipped;/* neighbours of the best frame that are not frames of the reference map (deviation 1) */
+    double best_score;           /* coarse; DBL_MAX: none */
+    double fine_score;           /* DBL_MAX: not run or nr = 0 */
+    int32_t n_neighbours_dropped;/* neighbours of the best frame left out because the target would exceed max_accum_points (deviation 4) */
+    int32_t pad;
+} lio_overlap_report;
+typedef struct lio_overlap_times {
+    double candidates_us;        /* host time of the candidate search (wall clock) */
+    double gate_us, targets_us, coarse_us, fitness_us, accumulate_us, fine_us; /* HIP events; targets = voxel builds + pool copies */
+    int32_t coarse_rounds, n_pairs, n_targets, pad;
+} lio_overlap_times;
+/* the defaults; bank may be NULL (max_accum_points = 8 x 65536) */
+void lio_overlap_default_params(lio_loop* bank, lio_overlap_params*);
+/* host only.  get_connection_count over the undirected edges (from[k], to[k]) */
+int lio_overlap_connection_count(const int32_t* from, const int32_t* to, uint32_t n_edges, int32_t source, int32_t target, int32_t max_count);
+/* host only.  find_candidates over n key frames (positions n x 3 f64, key-frame ids) for a new frame: indices into the n frames in the order
+ * they were accepted; the count, or -(count) when cap is too small.  params NULL = the defaults */
+int lio_overlap_find_candidates(const double* pos_xyz, const int32_t* ids, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, uint32_t n_edges,
+                                int32_t new_id, const double new_xyz[3], const lio_overlap_params* params, int32_t* out_idx, uint32_t cap);
+/* NULL without a device or with bad parameters.  params NULL = the defaults */
+lio_overlap* lio_overlap_create(lio_loop* bank, const lio_overlap_params* params);
+void lio_overlap_destroy(lio_overlap*);
+/* stage door: the gate of n bank frames source_ids[] moved by T16 (n x 16 f64, cast to f32) against bank frame target_id (or LIO_OVERLAP_ACCUM).
+ * Per pair: score, nr, n_in (any may be NULL) */
+int lio_overlap_gate_batch(lio_overlap*, int target_id, const int32_t* source_ids, uint32_t n, const double* T16, double max_range, double* score, uint32_t* nr,
+                           uint32_t* n_in);
+/* stage door: FAST_VGICP of n (target, source) pairs of bank frames from guesses (n x 16 f64, used as given) in one set of rounds */
+int lio_overlap_align_pairs(lio_overlap*, const int32_t* target_ids, const int32_t* source_ids, uint32_t n, const double* guesses, double* out_T,
+                            int32_t* iterations, int32_t* converged);
+/* stage door: the fine target of best_id and its neighbours (bank ids, in the order given); the number of points, LIO_E_CAPACITY beyond
+ * max_accum_points */
+int lio_overlap_accumulate(lio_overlap*, int best_id, const int32_t* neighbour_ids, uint32_t n);
+/* the accumulated cloud and its covariances (xx, xy, xz, yy, yz, zz) in the cloud's order; the count, or -(count) when cap is too small */
+int lio_overlap_download_accum(lio_overlap*, float* xyzi, double* cov6, uint32_t cap);
+/* one detect() call.  ref_ids / new_ids: bank ids of the reference map's and the fragment's frames; ref_kf / new_kf: their key-frame ids as
+ * the edges name them (NULL: the bank ids).  The overlaps into out (bank ids); the count, or -(count) when cap is too small */
+int lio_overlap_detect(lio_overlap*, const int32_t* ref_ids, const int32_t* ref_kf, uint32_t n_ref, const int32_t* new_ids, const int32_t* new_kf, uint32_t n_new,
+                       const int32_t* edge_from, const int32_t* edge_to, uint32_t n_edges, lio_overlap_edge* out, uint32_t cap);
+/* of new frame k (0 .. n_new) of the last detect; per candidate (arrays of cap entries, any may be NULL): bank id, gate inlier ratio, converged
+ * (0 also where the gate refused), iterations, coarse score (DBL_MAX where not taken).  The number of candidates, or -(number) */
+int lio_overlap_last_report(lio_overlap*, uint32_t k, lio_overlap_report* report, int32_t* candidate_ids, double* gate_ratio, int32_t* converged, int32_t* iterations,
+                            double* scores, uint32_t cap);
+/* stage times of the last detect (summed over its frames), or of the last stage-door call for its own stage */
+int lio_overlap_last_times(lio_overlap*, lio_overlap_times*);
 
 /* -------------------------------------------------------------------------------------------------------------
  * The pose graph on the device (csrc/graph.hip): what hdl_graph_slam's GraphSLAM does with g2o for SE3 pose nodes and EdgeSE3 edges

@@ -1,5 +1,6 @@
 // loop.hip -- loop detection over the key frames on gfx950 (wave64): hdl_graph_slam::LoopDetector
 // (slam/backend/hdl_graph_slam/include/hdl_graph_slam/loop_detector.hpp, "LD") up to the loop edge; include/lio_hip.h states the rules.
+// The records, the handle and the steps overlap.hip reuses on the same bank are in loop_internal.h.
 //
 //   bank      a key frame is uploaded once, in the caller's order, into one allocation that lives as long as the frame; its covariances come
 //             from the engine's source grid (gicp_cloud_covariances: hash grid + gicp_cov_kernel, the path of lio_gicp_set_source) and are kept
@@ -22,36 +23,11 @@
 
 #include "gicp_dev.h"
 #include "knn_index_dev.h"
+#include "loop_internal.h"
 #include "lsq.h"
 
 namespace lio {
 namespace loop {
-
-constexpr int kFitThreads = 256;
-constexpr int kLookEvery = 6;  // rounds between two looks of the host at the slot states
-
-struct LoopSlot {
-    const float4* src;   // the candidate's cloud and covariances (bank)
-    const double* scov;
-    int32_t* corr;       // [n] voxel slot of the point at the last linearisation, -1: none
-    double* maha;        // [n x 6]
-    double* partial;     // [nb x kGicpAcc]
-    uint32_t n, nb;
-    double x0[16], xi[16], delta[16], H[36], b[6], d[6];
-    double y0, lambda, nu;
-    int32_t phase;       // 0: linearise at x0; 1: the cost of the trial xi on the pairs of x0; 2: done
-    int32_t it, trial, conv, evals, it_done;
-    uint32_t n_corr, pad;
-};
-struct LoopLmParams {
-    int32_t max_iterations, lm_max_iterations;
-    double rotation_epsilon_deg, transformation_epsilon, lm_init_lambda_factor;
-};
-struct FitSlot {
-    const float4* src;
-    uint32_t n, pad;
-    float R[9], t[3];  // final_transformation_ (f32)
-};
 
 // FastVGICP::linearize (LIN: update_correspondences at x0 first, fast_vgicp_impl.hpp:72-180) / compute_error (:182-204) of the slot the table
 // gives this workgroup; per point the arithmetic of vgicp_corr_kernel + vgicp_cost_kernel (gicp.hip), DIRECT1
@@ -240,54 +216,11 @@ __global__ void __launch_bounds__(256) loop_stamp(const float4* __restrict__ p, 
     out[i] = make_float4(q.x, q.y, q.z, __uint_as_float(i));
 }
 
-struct Frame {
-    float4* pts = nullptr;  // one allocation: n float4 then 6 n doubles
-    double* cov = nullptr;
-    uint32_t n = 0;
-    double pose[16];
-    double accum = 0;
-};
-
-struct AlignOut {
-    double T[16];
-    int32_t iterations, converged;
-    double score;
-    uint32_t nr;
-};
-
 }  // namespace loop
 }  // namespace lio
 
 using namespace lio;
 using namespace lio::loop;
-
-struct lio_loop {
-    int device = 0;
-    lio_loop_params par;
-    lio_gicp* eng = nullptr;
-    hipStream_t st = nullptr;
-    std::vector<Frame> frames;
-    size_t n_keyframes = 0;  // frames [0, n_keyframes) are `keyframes`, the rest the new_keyframes queue
-    double last_edge_accum = 0.0;
-    std::vector<lio_loop_edge> edges;
-    // the target the engine holds
-    int target_id = -1;
-    knn_index::DeviceIndex index;
-    float4* idx_pts = nullptr;
-    // batch scratch (grown geometrically, kept)
-    LoopSlot *d_slots = nullptr, *h_slots = nullptr;
-    FitSlot *d_fit = nullptr, *h_fit = nullptr;
-    uint2 *d_tab = nullptr, *h_tab = nullptr;
-    uint64_t tab_cap = 0, pts_cap = 0;
-    int32_t* b_corr = nullptr;
-    double *b_maha = nullptr, *b_partial = nullptr, *d_fitp = nullptr, *h_fitp = nullptr;
-    // report of the last matching
-    lio_loop_report rep;
-    std::vector<int32_t> rep_ids, rep_conv, rep_it;
-    std::vector<double> rep_score;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double t_insert = 0, t_target = 0, t_coarse = 0, t_fitness = 0, t_fine = 0;
-};
 
 namespace {
 
@@ -612,6 +545,17 @@ void free_frames(lio_loop* h) {
 bool id_ok(lio_loop* h, int id) { return h && id >= 0 && (size_t)id < h->frames.size(); }
 
 }  // namespace
+
+namespace lio {
+namespace loop {
+int loop_reserve(lio_loop* h, uint64_t pts, uint64_t tab) { return reserve(h, pts, tab); }
+int loop_prepare_target(lio_loop* h, int id) { return prepare_target(h, id); }
+int loop_fitness_batch(lio_loop* h, const int32_t* src_ids, const double* T16, uint32_t n, double* score, uint32_t* nr, double max_range) {
+    return fitness_batch(h, src_ids, T16, n, score, nr, max_range);
+}
+void loop_launch_lm_step(hipStream_t st, uint32_t B, LoopSlot* d_slots, const LoopLmParams& P) { hipLaunchKernelGGL(loop_lm_step, B, 1024, 0, st, d_slots, P); }
+}  // namespace loop
+}  // namespace lio
 
 extern "C" {
 

@@ -27,6 +27,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <charconv>
 #include <chrono>
@@ -36,9 +37,12 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <initializer_list>
 #include <iomanip>
+#include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -136,7 +140,21 @@ struct Loc {
     std::vector<Imu> imu_data;
     std::vector<uint32_t> stamps;
     std::vector<float> staged;
+    // merge_map: the merged pose graph as a host record (key-frame ids; read from the loaded map's graph.g2o by the first merge, extended by every
+    // merge that succeeds -- the device graph is built from it for the length of a call), the bank of both maps' key frames and the overlap
+    // detector over it; key-frame id -> bank frame
+    struct MergeEdge { int a, b, kernel; double M[16], info[36]; };
+    std::vector<MergeEdge> medges;
+    std::set<int> mfixed;
+    bool have_mgraph = false;
+    lio_loop* mbank = nullptr;
+    lio_overlap* moverlap = nullptr;
+    std::map<int, int> bank_of_kf;
+    uint32_t bank_max_points = 0, ndt_biggest = 0;
+    struct MergeReport { std::vector<std::array<int, 2>> overlaps; std::vector<double> scores; std::vector<int> reasons, new_ids; int fragments = 0, skipped_tags = 0; } merge_report;
     ~Loc() {
+        if (moverlap) lio_overlap_destroy(moverlap);
+        if (mbank) lio_loop_destroy(mbank);
         if (pe) lio_pose_estimator_destroy(pe);
         if (lm) lio_localmap_destroy(lm);
         if (ndt) lio_ndt_destroy(ndt);
@@ -340,6 +358,7 @@ bool loc_setup(Slam* s) {
     for (const KeyFrameDisk& kf : L.frames) { total += kf.xyzi.size() / 4; biggest = std::max<uint32_t>(biggest, (uint32_t)(kf.xyzi.size() / 4)); }
     L.lm = lio_localmap_create(0, total + 16, 200000, std::max<uint32_t>(biggest, 1024));
     L.ndt = lio_ndt_create(0, 1.0f, 7, 200000ull + biggest + 1024, 400000, 262144);
+    L.ndt_biggest = biggest;
     L.scan = lio_scan_create(0, 1u << 18, 1u << 18);
     if (!L.lm || !L.ndt || !L.scan) return false;
     lio_ndt_default_params(&L.par);
@@ -347,6 +366,22 @@ bool loc_setup(Slam* s) {
     for (const KeyFrameDisk& kf : L.frames) {
         const float pos[3] = {(float)kf.odom(0, 3), (float)kf.odom(1, 3), (float)kf.odom(2, 3)};
         if (lio_localmap_add_keyframe(L.lm, kf.xyzi.data(), (uint32_t)(kf.xyzi.size() / 4), pos) < 0) return false;
+    }
+    return true;
+}
+
+// the resident map made again from the key-frame list (a re-initialisation, and merge_map once the list has grown and its poses moved)
+bool loc_refill_local_map(Loc& L) {
+    lio_localmap_destroy(L.lm);
+    L.lm = nullptr;
+    uint64_t total = 0;
+    uint32_t biggest = 0;
+    for (const KeyFrameDisk& kf : L.frames) { total += kf.xyzi.size() / 4; biggest = std::max<uint32_t>(biggest, (uint32_t)(kf.xyzi.size() / 4)); }
+    L.lm = lio_localmap_create(0, total + 16, 200000, std::max<uint32_t>(biggest, 1024));
+    if (!L.lm) return false;
+    for (const KeyFrameDisk& kf : L.frames) {
+        const float kp[3] = {(float)kf.odom(0, 3), (float)kf.odom(1, 3), (float)kf.odom(2, 3)};
+        lio_localmap_add_keyframe(L.lm, kf.xyzi.data(), (uint32_t)(kf.xyzi.size() / 4), kp);
     }
     return true;
 }
@@ -415,17 +450,7 @@ bool loc_localize(Slam* s, uint32_t n, uint64_t stamp, Mat4& pose_out) {
         L.initialized = true;
         L.age = 0;
         L.failures = 0;
-        lio_localmap_destroy(L.lm);  // a fresh local-map thread state: the first pose always builds a map
-        L.lm = nullptr;
-        uint64_t total = 0;
-        uint32_t biggest = 0;
-        for (const KeyFrameDisk& kf : L.frames) { total += kf.xyzi.size() / 4; biggest = std::max<uint32_t>(biggest, (uint32_t)(kf.xyzi.size() / 4)); }
-        L.lm = lio_localmap_create(0, total + 16, 200000, std::max<uint32_t>(biggest, 1024));
-        if (!L.lm) return false;
-        for (const KeyFrameDisk& kf : L.frames) {
-            const float kp[3] = {(float)kf.odom(0, 3), (float)kf.odom(1, 3), (float)kf.odom(2, 3)};
-            lio_localmap_add_keyframe(L.lm, kf.xyzi.data(), (uint32_t)(kf.xyzi.size() / 4), kp);
-        }
+        if (!loc_refill_local_map(L)) return false;  // a fresh local-map thread state: the first pose always builds a map
         loc_update_local_map(L, T);  // mPoseQueue.enqueue(mLastOdom)
     }
     if (n == 0) {  // "cloud is empty!!": the nodelet returns LocType::OTHER, which Localization::feedPointData counts like any failed frame
@@ -1230,7 +1255,366 @@ void set_map_origin(double lat, double lon, double alt, double heading, double p
         g->origin_set = true;
     }
 }
-py::dict merge_map(const std::string& directory) { (void)directory; return py::dict(); }
+// ---- merge_map (slam_wrapper.cpp:174-178 -> SLAM::mergeMap -> MapLoader::mergeMapSLAM, map_loader.cpp:82-169) ----------------------------------
+// g2o's text format, as far as a map's graph/graph.g2o needs it: VERTEX_SE3:QUAT id x y z qx qy qz qw; EDGE_SE3:QUAT from to x y z qx qy qz qw and
+// the 21 values of the information matrix's upper triangle, row by row; FIX id ...  Every other tag is passed over and counted.
+struct G2oFile {
+    struct Vertex { int id; double v[7]; };
+    struct Edge { int from, to; double m[7], info[36]; };
+    std::vector<Vertex> vertices;
+    std::vector<Edge> edges;
+    std::vector<int> fixed;
+    int skipped = 0;
+};
+bool pose_ok(const double v[7]) {  // x y z qx qy qz qw: finite, and a quaternion that can be normalised
+    for (int k = 0; k < 7; k++)
+        if (!std::isfinite(v[k])) return false;
+    return std::sqrt(v[3] * v[3] + v[4] * v[4] + v[5] * v[5] + v[6] * v[6]) > 1e-9;
+}
+bool read_g2o(const std::string& path, G2oFile& out, std::string& err) {
+    std::ifstream f(path);
+    if (!f) { err = "cannot open " + path; return false; }
+    std::string line;
+    int ln = 0;
+    while (std::getline(f, line)) {
+        ln++;
+        std::istringstream ls(line);
+        std::string tag;
+        if (!(ls >> tag) || tag[0] == '#') continue;
+        if (tag == "VERTEX_SE3:QUAT") {
+            G2oFile::Vertex v;
+            bool ok = (bool)(ls >> v.id);
+            for (int k = 0; k < 7 && ok; k++) ok = (bool)(ls >> v.v[k]);
+            if (!ok) { err = path + ":" + std::to_string(ln) + ": truncated VERTEX_SE3:QUAT"; return false; }
+            if (!pose_ok(v.v)) { err = path + ":" + std::to_string(ln) + ": a VERTEX_SE3:QUAT that is not finite or has a null quaternion"; return false; }
+            out.vertices.push_back(v);
+        } else if (tag == "EDGE_SE3:QUAT") {
+            G2oFile::Edge e;
+            bool ok = (bool)(ls >> e.from >> e.to);
+            for (int k = 0; k < 7 && ok; k++) ok = (bool)(ls >> e.m[k]);
+            for (int r = 0; r < 6 && ok; r++)
+                for (int c = r; c < 6 && ok; c++) { ok = (bool)(ls >> e.info[r * 6 + c]); e.info[c * 6 + r] = e.info[r * 6 + c]; }
+            if (!ok) { err = path + ":" + std::to_string(ln) + ": truncated EDGE_SE3:QUAT"; return false; }
+            for (int k = 0; k < 36 && ok; k++) ok = std::isfinite(e.info[k]);
+            if (!ok || !pose_ok(e.m)) { err = path + ":" + std::to_string(ln) + ": an EDGE_SE3:QUAT that is not finite or has a null quaternion"; return false; }
+            out.edges.push_back(e);
+        } else if (tag == "FIX") {
+            int id, n = 0;
+            while (ls >> id) { out.fixed.push_back(id); n++; }
+            if (!n) { err = path + ":" + std::to_string(ln) + ": truncated FIX"; return false; }
+        } else {
+            out.skipped++;
+        }
+    }
+    return true;
+}
+Mat4 mat_from_tq(const double v[7]) {  // x y z qx qy qz qw -> the pose, the quaternion normalised
+    const double n = std::sqrt(v[3] * v[3] + v[4] * v[4] + v[5] * v[5] + v[6] * v[6]);
+    const double x = v[3] / n, y = v[4] / n, z = v[5] / n, w = v[6] / n;
+    Mat4 T = Mat4::identity();
+    T(0, 0) = 1 - 2 * (y * y + z * z); T(0, 1) = 2 * (x * y - z * w); T(0, 2) = 2 * (x * z + y * w);
+    T(1, 0) = 2 * (x * y + z * w); T(1, 1) = 1 - 2 * (x * x + z * z); T(1, 2) = 2 * (y * z - x * w);
+    T(2, 0) = 2 * (x * z - y * w); T(2, 1) = 2 * (y * z + x * w); T(2, 2) = 1 - 2 * (x * x + y * y);
+    T(0, 3) = v[0]; T(1, 3) = v[1]; T(2, 3) = v[2];
+    return T;
+}
+// test visibility: _read_g2o(path) -> {vertices: {id: [x y z qx qy qz qw]}, edges: [(from, to, [7], 6 x 6)], fixed: [ids], skipped: tags passed over}
+py::dict _read_g2o(std::string path) {
+    G2oFile gf;
+    std::string err;
+    if (!read_g2o(path, gf, err)) throw std::runtime_error("slam_wrapper: _read_g2o: " + err);
+    py::dict d, vs;
+    for (const auto& v : gf.vertices) vs[py::int_(v.id)] = py::array_t<double>(7, v.v);
+    py::list es;
+    for (const auto& e : gf.edges) {
+        py::array_t<double> info({6, 6});
+        std::memcpy(info.mutable_data(), e.info, sizeof(e.info));
+        es.append(py::make_tuple(e.from, e.to, py::array_t<double>(7, e.m), info));
+    }
+    d["vertices"] = vs;
+    d["edges"] = es;
+    d["fixed"] = py::cast(gf.fixed);
+    d["skipped"] = gf.skipped;
+    return d;
+}
+
+namespace {
+struct MapInfo { double origin[6] = {0, 0, 0, 0, 0, 0}; int coordinate = 0; bool origin_set = false; };
+bool read_map_info(const std::string& map_path, MapInfo& mi) {  // MapLoader::loadMapOrigin (map_loader.cpp:180-221)
+    std::ifstream fs(map_path + "/graph/map_info.txt");
+    if (!fs) return false;
+    for (int i = 0; i < 6; i++) fs >> mi.origin[i];
+    double c = 0;
+    fs >> c;
+    mi.coordinate = (int)c;
+    mi.origin_set = false;
+    for (int i = 0; i < 6; i++) mi.origin_set = mi.origin_set || !(std::fabs(mi.origin[i]) < 1e-4);
+    return true;
+}
+void to_map_frame(KeyFrameDisk& kf) {  // KeyFrame::transformPoints at the frame's pose (load_keyframes' loop)
+    kf.xyzi = kf.local;
+    const size_t n = kf.xyzi.size() / 4;
+    for (size_t i = 0; i < n; i++) {
+        const double x = kf.local[4 * i], y = kf.local[4 * i + 1], z = kf.local[4 * i + 2];
+        for (int r = 0; r < 3; r++) kf.xyzi[4 * i + r] = (float)(kf.odom(r, 0) * x + kf.odom(r, 1) * y + kf.odom(r, 2) * z + kf.odom(r, 3));
+    }
+}
+py::dict keyframes_to_pydict(const std::vector<KeyFrameDisk>& frames, size_t first) {  // keyframe_to_pydict (py_utils.cpp:272-293)
+    py::dict d, points, images, poses, stamps;
+    for (size_t k = first; k < frames.size(); k++) {
+        const KeyFrameDisk& kf = frames[k];
+        const std::string id = std::to_string(kf.id);
+        const py::ssize_t n = (py::ssize_t)(kf.local.size() / 4);
+        py::array_t<float> a({n, (py::ssize_t)4});
+        if (n) std::memcpy(a.mutable_data(), kf.local.data(), kf.local.size() * sizeof(float));
+        points[id.c_str()] = a;
+        poses[id.c_str()] = mat4_to_numpy_f32(kf.odom);
+        stamps[id.c_str()] = kf.stamp;
+        images[id.c_str()] = py::dict();
+    }
+    d["points"] = points;
+    d["images"] = images;
+    d["poses"] = poses;
+    d["stamps"] = stamps;
+    return d;
+}
+// graph_load_impl (hdl_graph_slam_nodelet.cpp:1112-1148) of one map's file into the record: vertices without a key frame are dropped with their
+// edges; `id_of`: file id -> key-frame id of the frames that exist
+void record_take_file(std::vector<Loc::MergeEdge>& edges, std::set<int>& fixed, const G2oFile& gf, const std::map<int, int>& id_of) {
+    for (int id : gf.fixed) {
+        auto it = id_of.find(id);
+        if (it != id_of.end()) fixed.insert(it->second);
+    }
+    for (const auto& e : gf.edges) {
+        auto a = id_of.find(e.from), b = id_of.find(e.to);
+        if (a == id_of.end() || b == id_of.end()) continue;
+        Loc::MergeEdge me;
+        me.a = a->second; me.b = b->second;
+        me.kernel = LIO_GRAPH_KERNEL_NONE;  // (the text format carries no robust kernel: none)
+        const Mat4 M = mat_from_tq(e.m);
+        std::memcpy(me.M, M.m, sizeof(me.M));
+        std::memcpy(me.info, e.info, sizeof(me.info));
+        edges.push_back(me);
+    }
+}
+void graph_add(lio_graph* gr, const std::map<int, int>& node_of_kf, const Loc::MergeEdge& e) {
+    require(lio_graph_add_edge(gr, node_of_kf.at(e.a), node_of_kf.at(e.b), e.M, e.info, e.kernel, 1.0) >= 0, "merge_map: lio_graph_add_edge failed");
+}
+int bank_frame(Loc& L, const KeyFrameDisk& kf) {  // a frame of fewer than k points cannot be matched: it stays out of the bank (and of the detection)
+    if (kf.local.size() / 4 < (size_t)20) return -1;
+    const int id = lio_loop_add_keyframe_host(L.mbank, kf.local.data(), (uint32_t)(kf.local.size() / 4), kf.odom.m, 0.0);
+    require(id >= 0, "merge_map: lio_loop_add_keyframe_host failed");
+    L.bank_of_kf[kf.id] = id;
+    return id;
+}
+void drop_bank(Loc& L) {
+    if (L.moverlap) lio_overlap_destroy(L.moverlap);
+    if (L.mbank) lio_loop_destroy(L.mbank);
+    L.moverlap = nullptr;
+    L.mbank = nullptr;
+    L.bank_of_kf.clear();
+}
+// graph_optimize + graph_sync_pose(FROM_GRAPH) for every frame in `lists`, and the bank's poses
+void optimize_and_sync(Loc& L, lio_graph* gr, const std::map<int, int>& node_of_kf, std::initializer_list<std::vector<KeyFrameDisk>*> lists) {
+    const int it = lio_graph_optimize(gr, 1024, nullptr);
+    require(it >= -1, "merge_map: lio_graph_optimize failed");
+    const int n = lio_graph_num_nodes(gr);
+    std::vector<double> est(16 * (size_t)n);
+    require(lio_graph_estimates(gr, est.data(), (uint32_t)n) == n, "merge_map: lio_graph_estimates failed");
+    for (auto* frames : lists)
+        for (KeyFrameDisk& kf : *frames) {
+            auto node = node_of_kf.find(kf.id);
+            if (node == node_of_kf.end()) continue;
+            std::memcpy(kf.odom.m, &est[16 * (size_t)node->second], sizeof(kf.odom.m));
+            auto b = L.bank_of_kf.find(kf.id);
+            if (b != L.bank_of_kf.end()) require(lio_loop_set_pose(L.mbank, b->second, kf.odom.m) == LIO_OK, "merge_map: lio_loop_set_pose failed");
+        }
+}
+struct MergeInput { std::vector<KeyFrameDisk> fresh; G2oFile ref_g2o, new_g2o; };
+// the merge itself, under the lock of process() and without the GIL.  It works on its own copies -- the record of the graph, a device graph of
+// its own, the report -- and changes the key-frame list's poses and the bank as it goes; the caller undoes those when it throws
+void merge_locked(Slam* s, MergeInput& in, std::vector<Loc::MergeEdge>& edges, std::set<int>& fixed, Loc::MergeReport& report) {
+    Loc& L = *s->loc;
+    std::vector<KeyFrameDisk>& fresh = in.fresh;
+    uint32_t biggest = 1024;
+    for (const KeyFrameDisk& kf : L.frames) biggest = std::max<uint32_t>(biggest, (uint32_t)(kf.local.size() / 4));
+    for (const KeyFrameDisk& kf : fresh) biggest = std::max<uint32_t>(biggest, (uint32_t)(kf.local.size() / 4));
+    if (L.mbank && biggest > L.bank_max_points) drop_bank(L);  // a larger frame than the bank was made for: the bank is made again
+    if (!L.have_mgraph) {
+        std::map<int, int> same;
+        for (const KeyFrameDisk& kf : L.frames) same[kf.id] = kf.id;
+        record_take_file(edges, fixed, in.ref_g2o, same);
+        report.skipped_tags = in.ref_g2o.skipped;
+    }
+    // graph_merge (hdl_graph_slam_nodelet.cpp:1222-1336): new vertex ids max + 1 ... in key-frame order, the new edges behind the graph's
+    int max_id = 0;
+    for (const KeyFrameDisk& kf : L.frames) max_id = std::max(max_id, kf.id);
+    std::map<int, int> renamed;
+    for (KeyFrameDisk& kf : fresh) { renamed[kf.id] = ++max_id; kf.id = max_id; }
+    record_take_file(edges, fixed, in.new_g2o, renamed);
+    report.skipped_tags += in.new_g2o.skipped;
+    // the device graph of this call: node estimates are the key frames' odom
+    struct Graph { lio_graph* h = nullptr; ~Graph() { if (h) lio_graph_destroy(h); } } gr;
+    gr.h = lio_graph_create(0, nullptr);
+    require(gr.h != nullptr, "merge_map: lio_graph_create failed");
+    std::map<int, int> node_of_kf;
+    for (const std::vector<KeyFrameDisk>* frames : std::initializer_list<const std::vector<KeyFrameDisk>*>{&L.frames, &fresh})
+        for (const KeyFrameDisk& kf : *frames) {
+            const int node = lio_graph_add_node(gr.h, kf.odom.m);
+            require(node >= 0, "merge_map: lio_graph_add_node failed");
+            node_of_kf[kf.id] = node;
+        }
+    for (int id : fixed) require(lio_graph_set_fixed(gr.h, node_of_kf.at(id), 1) == LIO_OK, "merge_map: lio_graph_set_fixed failed");
+    for (const Loc::MergeEdge& e : edges) graph_add(gr.h, node_of_kf, e);
+    if (!L.mbank) {
+        lio_loop_params lp;
+        lio_loop_default_params(&lp);
+        lp.max_points = biggest;
+        L.bank_max_points = biggest;
+        L.mbank = lio_loop_create(0, &lp);
+        require(L.mbank != nullptr, "merge_map: lio_loop_create failed");
+        L.moverlap = lio_overlap_create(L.mbank, nullptr);
+        require(L.moverlap != nullptr, "merge_map: lio_overlap_create failed");
+        for (const KeyFrameDisk& kf : L.frames) bank_frame(L, kf);
+    }
+    for (const KeyFrameDisk& kf : fresh) bank_frame(L, kf);
+    std::vector<int32_t> ref_bank, ref_kf;
+    for (const KeyFrameDisk& kf : L.frames) {
+        auto b = L.bank_of_kf.find(kf.id);
+        if (b != L.bank_of_kf.end()) { ref_bank.push_back(b->second); ref_kf.push_back(kf.id); }
+    }
+    std::map<int, int> kf_of_bank;
+    for (const auto& kv : L.bank_of_kf) kf_of_bank[kv.second] = kv.first;
+    // fragments of 10 (map_loader.cpp:119-137)
+    const int fragment = 10, fragment_num = (int)(fresh.size() / fragment) + 1;
+    report.fragments = fragment_num;
+    for (int i = 0; i < fragment_num; i++) {
+        const size_t b0 = (size_t)i * fragment, b1 = std::min<size_t>((size_t)(i + 1) * fragment, fresh.size());
+        std::vector<int32_t> new_bank, new_kf, ea, eb;
+        for (size_t k = b0; k < b1; k++) {
+            auto b = L.bank_of_kf.find(fresh[k].id);
+            if (b != L.bank_of_kf.end()) { new_bank.push_back(b->second); new_kf.push_back(fresh[k].id); }
+        }
+        for (const Loc::MergeEdge& e : edges) { ea.push_back(e.a); eb.push_back(e.b); }  // graph_get_edges, in key-frame ids
+        std::vector<lio_overlap_edge> found(std::max<size_t>(new_bank.size(), 1));
+        const int nf = lio_overlap_detect(L.moverlap, ref_bank.data(), ref_kf.data(), (uint32_t)ref_bank.size(), new_bank.data(), new_kf.data(), (uint32_t)new_bank.size(),
+                                          ea.data(), eb.data(), (uint32_t)ea.size(), found.data(), (uint32_t)found.size());
+        require(nf >= 0, "merge_map: lio_overlap_detect failed");
+        for (size_t k = 0; k < new_bank.size(); k++) {
+            lio_overlap_report rep;
+            lio_overlap_last_report(L.moverlap, (uint32_t)k, &rep, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+            report.new_ids.push_back(new_kf[k]);
+            report.reasons.push_back(rep.reason);
+        }
+        for (int k = 0; k < nf; k++) {  // graph_add_edge (hdl_graph_slam_nodelet.cpp:893-912): key1 -> key2, information(score), Huber 1.0
+            Loc::MergeEdge me;
+            me.a = kf_of_bank[found[k].key1]; me.b = kf_of_bank[found[k].key2];
+            me.kernel = LIO_GRAPH_KERNEL_HUBER;
+            for (int a = 0; a < 16; a++) me.M[a] = (double)found[k].relative_pose[a];
+            std::memcpy(me.info, found[k].information, sizeof(me.info));
+            graph_add(gr.h, node_of_kf, me);
+            edges.push_back(me);
+            report.overlaps.push_back({me.a, me.b});
+            report.scores.push_back(found[k].score);
+        }
+        optimize_and_sync(L, gr.h, node_of_kf, {&L.frames, &fresh});
+    }
+    optimize_and_sync(L, gr.h, node_of_kf, {&L.frames, &fresh});  // OptimizeMap (map_loader.cpp:162)
+    // the localiser's matcher must hold the merged map's biggest frame (the resident map itself is made again at the commit)
+    uint32_t big_map = 0;
+    for (const std::vector<KeyFrameDisk>* frames : std::initializer_list<const std::vector<KeyFrameDisk>*>{&L.frames, &fresh})
+        for (const KeyFrameDisk& kf : *frames) big_map = std::max<uint32_t>(big_map, (uint32_t)(kf.local.size() / 4));
+    if (L.ndt && big_map > L.ndt_biggest) {  // the matcher's target was sized for the loaded map's biggest frame
+        lio_ndt* ndt = lio_ndt_create(0, 1.0f, 7, 200000ull + big_map + 1024, 400000, 262144);
+        require(ndt != nullptr, "merge_map: lio_ndt_create failed");
+        lio_ndt_destroy(L.ndt);
+        L.ndt = ndt;
+        L.ndt_biggest = big_map;
+        L.have_map = false;
+    }
+}
+py::dict merge_refused(const char* why) {
+    std::fprintf(stderr, "slam_wrapper: merge_map: fail to merge map: %s\n", why);
+    return py::dict();
+}
+}  // namespace
+
+py::dict merge_map(const std::string& directory) {
+    if (!g || !g->loc) return merge_refused("not in localisation mode");
+    Slam* s = g.get();
+    Loc& L = *s->loc;
+    // process() localises under this lock with the GIL released; the merge holds it from its first look at the key-frame list to its last write
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (L.frames.empty()) return merge_refused("no map is loaded");
+    // everything that can refuse the merge comes before any state is touched
+    MapInfo ref_info, new_info;
+    if (!read_map_info(s->map_path, ref_info) || !read_map_info(directory, new_info)) return merge_refused("graph/map_info.txt is missing");
+    MergeInput in;
+    if (!load_keyframes(directory, in.fresh)) return merge_refused("the new map has no key frames");
+    std::string err;
+    if (!L.have_mgraph && !read_g2o(s->map_path + "/graph/graph.g2o", in.ref_g2o, err)) return merge_refused(err.c_str());
+    if (!read_g2o(directory + "/graph/graph.g2o", in.new_g2o, err)) return merge_refused(err.c_str());
+    if (ref_info.coordinate != new_info.coordinate) return merge_refused("coordinate system is not consistent");
+    if (!ref_info.origin_set || !new_info.origin_set) return merge_refused("a map without an origin needs global_alignment, which is not built");
+    for (int i = 0; i < 3; i++)
+        if (std::fabs(ref_info.origin[i] - new_info.origin[i]) > 1e-6) return merge_refused("the origins differ: graph_update_origin is not built");
+    auto vertex_ids = [](const G2oFile& gf) { std::set<int> v; for (const auto& x : gf.vertices) v.insert(x.id); return v; };
+    const std::set<int> new_vertices = vertex_ids(in.new_g2o);
+    for (const KeyFrameDisk& kf : in.fresh)
+        if (!new_vertices.count(kf.id)) return merge_refused("a key frame of the new map has no vertex in graph.g2o");
+    if (!L.have_mgraph) {
+        const std::set<int> ref_vertices = vertex_ids(in.ref_g2o);
+        for (const KeyFrameDisk& kf : L.frames)
+            if (!ref_vertices.count(kf.id)) return merge_refused("a key frame of the loaded map has no vertex in graph.g2o");
+    }
+    if (lio_device_count() < 1) return merge_refused("no HIP device");
+    // the work: on copies of the graph's record and of the report; what it changes in place (the poses of the list, the bank) is undone if it fails
+    std::vector<Loc::MergeEdge> edges = L.medges;
+    std::set<int> fixed = L.mfixed;
+    Loc::MergeReport report;
+    std::vector<Mat4> saved;
+    for (const KeyFrameDisk& kf : L.frames) saved.push_back(kf.odom);
+    std::string failure;
+    size_t first_new = L.frames.size();
+    {
+        py::gil_scoped_release release;
+        try {
+            merge_locked(s, in, edges, fixed, report);
+            // commit: the record, the key frames (map_loader.cpp:140), their map-frame clouds, the resident map
+            L.medges.swap(edges);
+            L.mfixed.swap(fixed);
+            L.have_mgraph = true;
+            L.merge_report = report;
+            for (KeyFrameDisk& kf : in.fresh) L.frames.push_back(std::move(kf));
+            for (KeyFrameDisk& kf : L.frames) to_map_frame(kf);
+            if (L.lm) {
+                if (!loc_refill_local_map(L)) { L.initialized = false; L.have_map = false; }  // (no room for the merged map: the next initialisation tries again)
+                else if (L.initialized) loc_update_local_map(L, L.last_odom);
+            }
+        } catch (const std::exception& e) {
+            failure = e.what();
+            for (size_t k = 0; k < saved.size(); k++) L.frames[k].odom = saved[k];
+            drop_bank(L);  // (it holds the new map's frames and moved poses: made again by the next merge)
+        }
+    }
+    if (!failure.empty()) throw std::runtime_error(failure);
+    std::fprintf(stderr, "slam_wrapper: merge_map: merge success, total %zu key frames, %zu overlaps\n", L.frames.size(), L.merge_report.overlaps.size());
+    return keyframes_to_pydict(L.frames, first_new);
+}
+// test visibility: what the last merge_map did -- overlaps [(key1, key2, score)] in key-frame ids, the reason per matched new frame, fragments
+py::dict _last_merge() {
+    py::dict d;
+    if (!g || !g->loc) return d;
+    const auto& r = g->loc->merge_report;
+    py::list ov, reasons;
+    for (size_t k = 0; k < r.overlaps.size(); k++) ov.append(py::make_tuple(r.overlaps[k][0], r.overlaps[k][1], r.scores[k]));
+    for (size_t k = 0; k < r.new_ids.size(); k++) reasons.append(py::make_tuple(r.new_ids[k], r.reasons[k]));
+    d["overlaps"] = ov;
+    d["reasons"] = reasons;
+    d["fragments"] = r.fragments;
+    d["skipped_tags"] = r.skipped_tags;
+    return d;
+}
 // get_graph_map (slam_wrapper.cpp:180-184 -> keyframe_to_pydict, py_utils.cpp:272-293): the key frames of the loaded map in localisation mode
 // (points N x 4 f32 as stored, pose 4 x 4 f32, stamp); empty in mapping mode (the graph back end is out of scope)
 py::dict get_graph_map() {
@@ -2130,6 +2514,8 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("set_map_origin", &set_map_origin, "set map origin", py::arg("lat"), py::arg("lon"), py::arg("alt"), py::arg("heading"), py::arg("pitch"), py::arg("roll"));
     m.def("get_color_map", &get_color_map, "get color map");
     m.def("merge_map", &merge_map, "merge map", py::arg("directory"));
+    m.def("_read_g2o", &_read_g2o, py::arg("path"));
+    m.def("_last_merge", &_last_merge);
     m.def("get_graph_map", &get_graph_map, "get graph map");
     m.def("get_graph_edges", &get_graph_edges, "get graph edges");
     m.def("pointcloud_align", &pointcloud_align, "pointcloud align", py::arg("source_point"), py::arg("target_point"), py::arg("guess"));

@@ -58,6 +58,9 @@ SYMBOLS = [
     "lio_loop_default_params", "lio_loop_find_candidates", "lio_loop_information_matrix", "lio_loop_create", "lio_loop_destroy", "lio_loop_reset",
     "lio_loop_add_keyframe_host", "lio_loop_set_pose", "lio_loop_num_keyframes", "lio_loop_download_keyframe", "lio_loop_detect", "lio_loop_edges",
     "lio_loop_last_report", "lio_loop_last_times", "lio_loop_align_candidates", "lio_loop_align_fine", "lio_loop_pair_information",
+    "lio_overlap_default_params", "lio_overlap_connection_count", "lio_overlap_find_candidates", "lio_overlap_create", "lio_overlap_destroy",
+    "lio_overlap_gate_batch", "lio_overlap_align_pairs", "lio_overlap_accumulate", "lio_overlap_download_accum", "lio_overlap_detect",
+    "lio_overlap_last_report", "lio_overlap_last_times",
     "lio_graph_default_params", "lio_graph_create", "lio_graph_destroy", "lio_graph_reset", "lio_graph_add_node", "lio_graph_set_fixed", "lio_graph_set_estimate",
     "lio_graph_num_nodes", "lio_graph_get_fixed", "lio_graph_add_edge", "lio_graph_remove_edge", "lio_graph_optimize", "lio_graph_estimates", "lio_graph_edges",
     "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
@@ -144,6 +147,32 @@ class LoopEdge(C.Structure):  # lio_loop_edge
 class LoopReport(C.Structure):  # lio_loop_report
     _fields_ = [("new_id", C.c_int32), ("n_candidates", C.c_int32), ("best", C.c_int32), ("fine_converged", C.c_int32), ("fine_iterations", C.c_int32),
                 ("reason", C.c_int32), ("coarse_rounds", C.c_int32), ("pad", C.c_int32), ("best_score", C.c_double), ("fine_score", C.c_double)]
+
+
+class OverlapParams(C.Structure):  # lio_overlap_params
+    _fields_ = [("distance_thresh", C.c_double), ("candidate_link_dist", C.c_int32), ("max_candidate_num", C.c_int32), ("knn", C.c_int32), ("min_z", C.c_float),
+                ("fitness_score_max_range", C.c_double), ("fitness_score_thresh", C.c_double), ("fitness_inlier_thresh", C.c_double), ("gate_max_range", C.c_double),
+                ("xy_range", C.c_double), ("fine_max_corr_dist", C.c_double), ("fine_translation_epsilon", C.c_double), ("max_accum_points", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class OverlapEdge(C.Structure):  # lio_overlap_edge
+    _fields_ = [("key1", C.c_int32), ("key2", C.c_int32), ("relative_pose", C.c_float * 16), ("score", C.c_double), ("information", C.c_double * 36)]
+
+
+class OverlapReport(C.Structure):  # lio_overlap_report
+    _fields_ = [("new_id", C.c_int32), ("n_candidates", C.c_int32), ("best", C.c_int32), ("fine_converged", C.c_int32), ("fine_iterations", C.c_int32),
+                ("reason", C.c_int32), ("n_accum", C.c_uint32), ("n_neighbours_skipped", C.c_int32), ("best_score", C.c_double), ("fine_score", C.c_double),
+                ("n_neighbours_dropped", C.c_int32), ("pad", C.c_int32)]
+
+
+class OverlapTimes(C.Structure):  # lio_overlap_times
+    _fields_ = [("candidates_us", C.c_double), ("gate_us", C.c_double), ("targets_us", C.c_double), ("coarse_us", C.c_double), ("fitness_us", C.c_double),
+                ("accumulate_us", C.c_double), ("fine_us", C.c_double), ("coarse_rounds", C.c_int32), ("n_pairs", C.c_int32), ("n_targets", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+OVERLAP_ACCUM = -1  # LIO_OVERLAP_ACCUM
 
 
 class GraphParams(C.Structure):  # lio_graph_params
@@ -440,6 +469,19 @@ def lib():
     sig("lio_loop_align_candidates", cint, vp, cint, i32p, u32, f64p, f64p, i32p, i32p, f64p, C.POINTER(u32))
     sig("lio_loop_align_fine", cint, vp, cint, cint, f64p, f64p, i32p, i32p, f64p, C.POINTER(u32))
     sig("lio_loop_pair_information", cint, vp, cint, cint, f64p, f64p, C.POINTER(u32), f64p)
+    op, oe = C.POINTER(OverlapParams), C.POINTER(OverlapEdge)
+    sig("lio_overlap_default_params", None, vp, op)
+    sig("lio_overlap_connection_count", cint, i32p, i32p, u32, C.c_int32, C.c_int32, C.c_int32)
+    sig("lio_overlap_find_candidates", cint, f64p, i32p, u32, i32p, i32p, u32, C.c_int32, f64p, op, i32p, u32)
+    sig("lio_overlap_create", vp, vp, op)
+    sig("lio_overlap_destroy", None, vp)
+    sig("lio_overlap_gate_batch", cint, vp, cint, i32p, u32, f64p, dbl, f64p, C.POINTER(u32), C.POINTER(u32))
+    sig("lio_overlap_align_pairs", cint, vp, i32p, i32p, u32, f64p, f64p, i32p, i32p)
+    sig("lio_overlap_accumulate", cint, vp, cint, i32p, u32)
+    sig("lio_overlap_download_accum", cint, vp, f32p, f64p, u32)
+    sig("lio_overlap_detect", cint, vp, i32p, i32p, u32, i32p, i32p, u32, i32p, i32p, u32, oe, u32)
+    sig("lio_overlap_last_report", cint, vp, u32, C.POINTER(OverlapReport), i32p, f64p, i32p, i32p, f64p, u32)
+    sig("lio_overlap_last_times", cint, vp, C.POINTER(OverlapTimes))
     gp, gr = C.POINTER(GraphParams), C.POINTER(GraphReport)
     sig("lio_graph_default_params", None, gp)
     sig("lio_graph_create", vp, cint, gp)

@@ -798,6 +798,129 @@ class LoopDetector:
         return sc.value, nr.value, info
 
 
+class OverlapDetector:
+    """OverlapDetector of the reference's map merge on the device (lio_overlap_*) over a LoopDetector's bank: the key frames of both maps are
+    added to `bank` and addressed by bank id.  find_candidates and connection_count run on the host; gate, align_pairs and accumulate are the
+    stage doors; detect is one detect() call over a fragment of new frames.  Keyword arguments override lio_overlap_params.  The bank must
+    outlive the detector."""
+
+    REASONS = {0: "found", 1: "no_candidate", 2: "gate", 3: "coarse", 4: "fine_not_converged", 5: "fine_score"}
+    ACCUM = capi.OVERLAP_ACCUM
+
+    def __init__(self, bank, **params):
+        self.bank = bank
+        self.params = self.default_params(bank)
+        for k, v in params.items():
+            if not hasattr(self.params, k):
+                raise TypeError(f"lio_overlap_params has no field {k!r}")
+            setattr(self.params, k, v)
+        self.h = lib().lio_overlap_create(bank.h, C.byref(self.params))
+        if not self.h:
+            raise capi.LioError("lio_overlap_create failed: " + lib().lio_last_error().decode())
+
+    @staticmethod
+    def default_params(bank=None):
+        p = capi.OverlapParams()
+        lib().lio_overlap_default_params(bank.h if bank is not None else None, C.byref(p))
+        return p
+
+    @staticmethod
+    def _edges(edges):
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        return np.ascontiguousarray(e[:, 0]), np.ascontiguousarray(e[:, 1])
+
+    @staticmethod
+    def connection_count(edges, source, target, max_count):
+        """get_connection_count (overlap_merge.hpp:265-296) over the undirected edges (m, 2): breadth-first LEVELS from source until target"""
+        a, b = OverlapDetector._edges(edges)
+        return check(lib().lio_overlap_connection_count(ptr(a, C.c_int32), ptr(b, C.c_int32), len(a), int(source), int(target), int(max_count)), "overlap connection_count")
+
+    @staticmethod
+    def find_candidates(pos_xyz, ids, edges, new_id, new_xyz, params=None):
+        """find_candidates (overlap_merge.hpp:113-145) on the host: indices into the key frames, in the order they were accepted"""
+        pos, kid, q = f64(pos_xyz).reshape(-1, 3), np.ascontiguousarray(ids, np.int32).ravel(), f64(new_xyz).ravel()
+        assert len(pos) == len(kid) and len(q) == 3
+        a, b = OverlapDetector._edges(edges)
+        out = np.zeros(max(len(kid), 1), np.int32)
+        n = check(lib().lio_overlap_find_candidates(ptr(pos, C.c_double), ptr(kid, C.c_int32), len(kid), ptr(a, C.c_int32), ptr(b, C.c_int32), len(a), int(new_id),
+                                                    ptr(q, C.c_double), C.byref(params) if params is not None else None, ptr(out, C.c_int32), len(out)),
+                  "overlap find_candidates")
+        return out[:n].copy()
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None and getattr(self.bank, "h", None):
+            lib().lio_overlap_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def gate(self, target_id, source_ids, Ts, max_range=1.0):
+        """calc_fitness_score (overlap_merge.hpp:225-263) of bank frames source_ids moved by Ts against bank frame target_id (ACCUM: the
+        accumulated cloud): per pair (score, nr, n_in); the inlier ratio is nr / n_in"""
+        ids, T = np.ascontiguousarray(source_ids, np.int32).ravel(), f64(Ts).reshape(-1, 4, 4)
+        n = len(ids)
+        assert len(T) == n
+        sc, nr, nin = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        check(lib().lio_overlap_gate_batch(self.h, int(target_id), ptr(ids, C.c_int32), n, ptr(T, C.c_double), float(max_range), ptr(sc, C.c_double),
+                                           ptr(nr, C.c_uint32), ptr(nin, C.c_uint32)), "overlap gate")
+        return [(float(sc[i]), int(nr[i]), int(nin[i])) for i in range(n)]
+
+    def align_pairs(self, target_ids, source_ids, guesses):
+        """FAST_VGICP of (target, source) pairs of bank frames in one set of rounds: per pair (T (4, 4) f64, converged, iterations)"""
+        t, s = np.ascontiguousarray(target_ids, np.int32).ravel(), np.ascontiguousarray(source_ids, np.int32).ravel()
+        g = f64(guesses).reshape(-1, 4, 4)
+        n = len(t)
+        assert len(s) == n and len(g) == n
+        T, it, conv = np.zeros((max(n, 1), 4, 4)), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        check(lib().lio_overlap_align_pairs(self.h, ptr(t, C.c_int32), ptr(s, C.c_int32), n, ptr(g, C.c_double), ptr(T, C.c_double), ptr(it, C.c_int32),
+                                            ptr(conv, C.c_int32)), "overlap align_pairs")
+        return [(T[i].copy(), bool(conv[i]), int(it[i])) for i in range(n)]
+
+    def accumulate(self, best_id, neighbour_ids):
+        """the fine target: best's cloud, then every neighbour's moved by best.pose^-1 * neighbour.pose -> (points (n, 4), covariances (n, 3, 3))"""
+        nb = np.ascontiguousarray(neighbour_ids, np.int32).ravel()
+        n = check(lib().lio_overlap_accumulate(self.h, int(best_id), ptr(nb, C.c_int32), len(nb)), "overlap accumulate")
+        pts, cov = np.zeros((n, 4), np.float32), np.zeros((n, 6))
+        check(lib().lio_overlap_download_accum(self.h, ptr(pts, C.c_float), ptr(cov, C.c_double), n), "overlap download_accum")
+        full = np.stack([cov[:, 0], cov[:, 1], cov[:, 2], cov[:, 1], cov[:, 3], cov[:, 4], cov[:, 2], cov[:, 4], cov[:, 5]], 1).reshape(n, 3, 3)
+        return pts, full
+
+    def detect(self, ref_ids, new_ids, edges, ref_kf=None, new_kf=None, cap=64):
+        """one detect() call: bank ids of the reference map's frames and of the fragment, the graph's edges (m, 2) in key-frame ids (ref_kf /
+        new_kf: the frames' key-frame ids, default the bank ids) -> the overlaps, each a dict key1 (best), key2 (new), relative_pose, score,
+        information"""
+        r, w = np.ascontiguousarray(ref_ids, np.int32).ravel(), np.ascontiguousarray(new_ids, np.int32).ravel()
+        rk = np.ascontiguousarray(ref_kf, np.int32).ravel() if ref_kf is not None else None
+        wk = np.ascontiguousarray(new_kf, np.int32).ravel() if new_kf is not None else None
+        assert (rk is None or len(rk) == len(r)) and (wk is None or len(wk) == len(w))
+        a, b = self._edges(edges)
+        cap = max(cap, len(w), 1)
+        buf = (capi.OverlapEdge * cap)()
+        n = check(lib().lio_overlap_detect(self.h, ptr(r, C.c_int32), ptr(rk, C.c_int32) if rk is not None else None, len(r), ptr(w, C.c_int32),
+                                           ptr(wk, C.c_int32) if wk is not None else None, len(w), ptr(a, C.c_int32), ptr(b, C.c_int32), len(a), buf, cap), "overlap detect")
+        self._n_new = len(w)
+        return [LoopDetector._edge(buf[i]) for i in range(n)]
+
+    def last_report(self, k=None):
+        """the report of new frame k of the last detect (None: a list over all its frames)"""
+        if k is None:
+            return [self.last_report(i) for i in range(getattr(self, "_n_new", 0))]
+        rep = capi.OverlapReport()
+        K = abs(lib().lio_overlap_last_report(self.h, int(k), C.byref(rep), None, None, None, None, None, 0))  # -(count): the arrays were too small
+        m = max(K, 1)
+        ids, ratio, conv, it, sc = np.zeros(m, np.int32), np.zeros(m), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m)
+        check(lib().lio_overlap_last_report(self.h, int(k), C.byref(rep), ptr(ids, C.c_int32), ptr(ratio, C.c_double), ptr(conv, C.c_int32), ptr(it, C.c_int32),
+                                            ptr(sc, C.c_double), m), "overlap last_report")
+        return dict(new_id=rep.new_id, candidates=ids[:K].copy(), gate_ratio=ratio[:K].copy(), converged=conv[:K].astype(bool), iterations=it[:K].copy(),
+                    scores=sc[:K].copy(), best=rep.best, best_score=rep.best_score, fine_converged=bool(rep.fine_converged), fine_iterations=rep.fine_iterations,
+                    fine_score=rep.fine_score, n_accum=rep.n_accum, n_neighbours_skipped=rep.n_neighbours_skipped, n_neighbours_dropped=rep.n_neighbours_dropped, reason=self.REASONS.get(rep.reason, str(rep.reason)))
+
+    def last_times(self):
+        t = capi.OverlapTimes()
+        check(lib().lio_overlap_last_times(self.h, C.byref(t)), "overlap last_times")
+        return {k: getattr(t, k) for k, _ in capi.OverlapTimes._fields_ if k != "pad"}
+
+
 class PoseGraph:
     """The pose graph on the device (lio_graph_*): SE3 nodes, EdgeSE3 edges with an optional Huber kernel, Levenberg-Marquardt as g2o's
     OptimizationAlgorithmLevenberg runs it, the linear solve by block-Jacobi conjugate gradients.  Keyword arguments override lio_graph_params."""
