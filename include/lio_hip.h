@@ -70,8 +70,11 @@ int lio_device_count(void);
  *      position, orientation and floor-plane priors, the DCS2 kernel, the GNSS outlier stage of robust_graph_optimize).
  * 16 = lio_overlap_* (overlap detection between two maps over a lio_loop bank: candidate search over the graph's connections, the range-gated
  *      fitness for many pairs, FAST_VGICP for arbitrary (target, source) pairs in one set of rounds, the fine target accumulated on the device,
- *      one detect() call over a fragment of new key frames). */
-#define LIO_ABI_VERSION 16
+ *      one detect() call over a fragment of new key frames).
+ * 17 = lio_gicp_neighbours / lio_gicp_mahalanobis (test visibility: the neighbour list behind every covariance, the Mahalanobis matrices of the
+ *      current pairs).  lio_gicp_set_target / _set_source now refuse points that are not finite, lio_gicp_linearize / _align a pose that is not
+ *      finite or a max_corr_dist that is negative or NaN (LIO_E_INVALID, nothing launched, the object as it was). */
+#define LIO_ABI_VERSION 17
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -651,7 +654,19 @@ int lio_ndt_align_batch(lio_ndt*, lio_align_job* jobs, int n_jobs, const lio_ndt
  *   align .......... pcl::Registration::align(guess) -> LsqRegistration's LM loop; params NULL = the reference's FAST_GICP settings
  *   download / correspondences  test visibility: the clouds in internal (grid) order with their regularised covariances (xx, xy, xz, yy, yz, zz);
  *                    the target index of every source point (-1 = none), in that order
- * Transforms are row-major 4 x 4 doubles. */
+ *   neighbours / mahalanobis  test visibility, see below
+ * Transforms are row-major 4 x 4 doubles.
+ * "Exact" means: the neighbour list of point i is the k smallest keys (d2, index), d2 = (ex*ex + ey*ey) + ez*ez in f32 and the index in internal
+ * order, so ties of distance and duplicate points are decided; a pair is the smallest such key over the target, taken iff d2 < (float)(max_corr_dist^2)
+ * strictly.  Both searches walk rings of grid cells (rings 0 .. 65 for the neighbours, 0 .. 16 for the pairs) and, when that has not settled
+ * the answer, go over the whole cloud instead: the result is the same at any distance and any grid_resolution, only the time differs.
+ * Input contract: coordinates are finite (set_target / set_source: LIO_E_INVALID otherwise, the object unchanged; the intensity is not read);
+ * the pose is finite and max_corr_dist is >= 0, +inf = no limit (linearize / align: LIO_E_INVALID otherwise, nothing launched).  A source point
+ * whose TRANSFORMED position overflows f32 gets no pair.  A finite coordinate may be of any size: where |x / grid_resolution| is past 2^21 the
+ * cells alias (the key keeps 21 bits per axis: more candidates, the same result), past 2^24 the distance to the cell's face is taken as
+ * unknown, and past the int range (or where the quotient overflows f32) the cell index saturates and the search of that point goes over the
+ * whole cloud; in all of these the lists and pairs stay the exact ones, only the time differs.  Clouds that enter on the device (the loop detector's and the overlap detector's key
+ * frames, which go through the same covariance kernel) are not checked: they are required to hold finite points. */
 typedef struct lio_gicp lio_gicp;
 lio_gicp* lio_gicp_create(int device, float grid_resolution, uint32_t max_points, int k_correspondences);
 void lio_gicp_destroy(lio_gicp*);
@@ -668,6 +683,14 @@ int lio_gicp_set_voxel_mode(lio_gicp*, double voxel_resolution, int search_metho
 int lio_gicp_voxel_at(lio_gicp*, const float p[3], double mean[3], double cov6[6]);
 int lio_gicp_download(lio_gicp*, int which, float* xyzi, double* cov6, uint32_t cap);
 int lio_gicp_correspondences(lio_gicp*, int32_t* corr, uint32_t cap);
+/* diagnostics (ABI 17).  neighbours: the sorted neighbour list of every point of cloud `which` (0 target, 1 source) as the covariance kernel holds
+ * it, idx[i * 32 + j] = internal index of the j-th nearest of point i (point i itself included), ascending (d2, index); places >= k hold further
+ * candidates no nearer than the k-th, or -1.  Runs the search again on the cloud's grid; the cloud and its covariances stay as they are.  Returns the
+ * number of points; LIO_E_STATE for a cloud without a grid (none set, or a source that was adopted on the device as it stands), LIO_E_CAPACITY for
+ * cap_points < n.  mahalanobis: (xx, xy, xz, yy, yz, zz) of (C_B + R C_A R^T)^-1 for every source point as the last linearize with update_corr
+ * left it; a row whose correspondence is -1 is undefined.  LIO_E_STATE in voxel mode (its matrices are per (point, voxel) and not exposed). */
+int lio_gicp_neighbours(lio_gicp*, int which, int32_t* idx, uint32_t cap_points);
+int lio_gicp_mahalanobis(lio_gicp*, double* maha6, uint32_t cap);
 int lio_gicp_linearize(lio_gicp*, const double T[16], double max_corr_dist, int update_corr, int with_derivatives, double H[36], double b[6], double* err,
                        uint32_t* n_corr);
 int lio_gicp_align(lio_gicp*, const double guess[16], const lio_ndt_params* params, double max_corr_dist, double out[16], int* iterations, int* converged);

@@ -18,6 +18,8 @@
 // U diag(1, 1, 1e-3) V^T = I - (1 - 1e-3) v0 v0^T for a symmetric positive semi-definite covariance.
 #include <sched.h>
 
+#include <cfloat>
+#include <cmath>
 #include <vector>
 
 #include "gicp_dev.h"
@@ -27,22 +29,62 @@
 
 namespace lio {
 
+// When a ring search may stop.  After ring r everything unseen lies outside the (2r + 1)^3 cells around the query's, at least r cells plus
+// the distance g (in cells) from the query to the nearest face of its own cell away -- less what the f32 arithmetic can be wrong by: the keys of
+// the query and of the unseen point (floor(x / res - 0.5): two roundings of a number of size |x / res| + r), and the subtraction and the three
+// products of the squared distance itself, together under 2.5e-7 (|x / res| + r + 2) cells.  g comes shrunk by 1e-6 (1 + |x / res|) and is NOT
+// clamped at zero (the rounding can put a point a hair outside its cell); the part that grows with r is the relative 4e-6.  A search stops
+// when its k-th (its best) squared distance is STRICTLY below ring_floor2: an unseen point at the same f32 distance and a lower index would
+// have won the tie.
+__device__ inline float cell_gap_cells(float x, float res, int k) {
+    const float f = x / res - 0.5f - (float)k;
+    return fminf(f, 1.0f - f) - 1e-6f * (1.0f + fabsf(x / res));
+}
+// a cell index plus a ring offset; wraps where |x / res| is past the int range (the index is saturated there and the pool sweep decides)
+__device__ inline int cell_add(int k, int d) { return (int)((uint32_t)k + (uint32_t)d); }
+__device__ inline float ring_floor2(int r, float g, float res) {
+    const float reach = ((float)r + g) * res;
+    return reach > 0.f ? (reach * reach) * (1.0f - 4e-6f) : 0.f;
+}
 
 // k nearest neighbours of every point of the cloud within the cloud itself (the point is its own nearest), their covariance, PLANE
 // regularisation.  cov6 = (xx, xy, xz, yy, yz, zz) of the regularised matrix, pool order.
 // The sorted list of the k <= 32 best lives in two registers per lane (position = lane, 16 + lane); an insertion is one shift by a lane.
+// The ring search runs rings 0 .. kGicpCovRings.  A point whose k-th neighbour is not within reach by then (a few points far from the rest
+// of the cloud at a fine grid) starts over and sweeps the whole pool, n / 16 steps with the same keys: the list is the exact one at any distance.
+// NBR (lio_gicp_neighbours, test visibility) also stores the list: position `lane` from e0, 16 + lane from e1, -1 = an empty place.
+constexpr int kGicpCovRings = 65;
+
+// one batch of up to sixteen candidates (a lane's key c, all ones = none) into the group's sorted list; kth = the key at position k - 1 afterwards
+__device__ __forceinline__ void gicp_list_offer(unsigned long long c, int lane, int k, unsigned long long& e0, unsigned long long& e1, unsigned long long& kth) {
+    uint32_t take = grp_ballot(c < kth);
+    while (take) {
+        const int bb = __ffs((int)take) - 1;
+        take &= take - 1;
+        const unsigned long long cc = __shfl(c, bb, kGrp);
+        unsigned long long l0 = __shfl_up(e0, 1, kGrp), l1 = __shfl_up(e1, 1, kGrp);
+        const unsigned long long carry = __shfl(e0, kGrp - 1, kGrp);
+        if (lane == 0) { l0 = 0; l1 = carry; }
+        e0 = e0 <= cc ? e0 : (l0 <= cc ? cc : l0);
+        e1 = e1 <= cc ? e1 : (l1 <= cc ? cc : l1);
+    }
+    kth = k <= kGrp ? __shfl(e0, k - 1, kGrp) : __shfl(e1, k - 1 - kGrp, kGrp);
+}
+
+template <bool NBR>
 __global__ void __launch_bounds__(kGrpThreads) gicp_cov_kernel(const Slot* __restrict__ table, uint32_t mask, const float4* __restrict__ pool, uint32_t n,
-                                                               float res, int k, double* __restrict__ cov6) {
+                                                               float res, int k, double* __restrict__ cov6, int32_t* __restrict__ nbr) {
     const int lane = threadIdx.x & (kGrp - 1);
     const uint32_t i = (blockIdx.x * kGrpThreads + threadIdx.x) / kGrp;
     if (i >= n) return;  // whole groups leave together
     const float4 p = pool[i];
     int kx, ky, kz;
     pos2grid_ndt(p.x, p.y, p.z, res, kx, ky, kz);
-    const float gap = cell_gap3(p.x, p.y, p.z, res, kx, ky, kz);
+    const float gap = fminf(fminf(cell_gap_cells(p.x, res, kx), cell_gap_cells(p.y, res, ky)), cell_gap_cells(p.z, res, kz));
     const unsigned long long kNone = ~0ull;
     unsigned long long e0 = kNone, e1 = kNone, kth = kNone;
-    for (int r = 0;; r++) {
+    bool within = false;  // the k-th neighbour is within the radius the rings have covered (the same in all lanes of the group)
+    for (int r = 0; r <= kGicpCovRings && !within; r++) {
         const int n_cells = shell_cells(r);
         for (int t0 = 0; t0 < n_cells; t0 += kGrp) {
             const int t = t0 + lane;
@@ -51,7 +93,7 @@ __global__ void __launch_bounds__(kGrpThreads) gicp_cov_kernel(const Slot* __res
             if (t < n_cells) {
                 int dx, dy, dz;
                 shell_cell(r, t, dx, dy, dz);
-                found = grid_find(table, mask, kx + dx, ky + dy, kz + dz, ptr, cnt);
+                found = grid_find(table, mask, cell_add(kx, dx), cell_add(ky, dy), cell_add(kz, dz), ptr, cnt);
             }
             uint32_t hits = grp_ballot(found);
             while (hits) {
@@ -67,23 +109,29 @@ __global__ void __launch_bounds__(kGrpThreads) gicp_cov_kernel(const Slot* __res
                         const float d2 = (ex * ex + ey * ey) + ez * ez;
                         if (d2 == d2) c = cand_key(d2, cptr + j);
                     }
-                    uint32_t take = grp_ballot(c < kth);
-                    while (take) {
-                        const int bb = __ffs((int)take) - 1;
-                        take &= take - 1;
-                        const unsigned long long cc = __shfl(c, bb, kGrp);
-                        unsigned long long l0 = __shfl_up(e0, 1, kGrp), l1 = __shfl_up(e1, 1, kGrp);
-                        const unsigned long long carry = __shfl(e0, kGrp - 1, kGrp);
-                        if (lane == 0) { l0 = 0; l1 = carry; }
-                        e0 = e0 <= cc ? e0 : (l0 <= cc ? cc : l0);
-                        e1 = e1 <= cc ? e1 : (l1 <= cc ? cc : l1);
-                    }
-                    kth = k <= kGrp ? __shfl(e0, k - 1, kGrp) : __shfl(e1, k - 1 - kGrp, kGrp);
+                    gicp_list_offer(c, lane, k, e0, e1, kth);
                 }
             }
         }
-        const float reach = (float)r * res + gap;
-        if ((kth != kNone && __uint_as_float((uint32_t)(kth >> 32)) <= reach * reach) || r > 64) break;
+        within = kth != kNone && __uint_as_float((uint32_t)(kth >> 32)) < ring_floor2(r, gap, res);
+    }
+    if (!within) {  // past the last ring: every point of the pool, from an empty list (the rings' finds would come a second time)
+        e0 = e1 = kth = kNone;
+        for (uint32_t j0 = 0; j0 < n; j0 += kGrp) {
+            const uint32_t j = j0 + lane;
+            unsigned long long c = kNone;
+            if (j < n) {
+                const float4 q = pool[j];
+                const float ex = q.x - p.x, ey = q.y - p.y, ez = q.z - p.z;
+                const float d2 = (ex * ex + ey * ey) + ez * ez;
+                if (d2 == d2) c = cand_key(d2, j);
+            }
+            gicp_list_offer(c, lane, k, e0, e1, kth);
+        }
+    }
+    if (NBR) {
+        nbr[(size_t)i * (2 * kGrp) + lane] = e0 != kNone ? (int32_t)(uint32_t)e0 : -1;
+        nbr[(size_t)i * (2 * kGrp) + kGrp + lane] = e1 != kNone ? (int32_t)(uint32_t)e1 : -1;
     }
     // neighbors.colwise() -= neighbors.rowwise().mean(); cov = neighbors * neighbors^T / k   (f64, as the reference casts); the lanes hold
     // one or two neighbours each, sums by a fixed butterfly over the group
@@ -124,10 +172,14 @@ __global__ void __launch_bounds__(kGrpThreads) gicp_cov_kernel(const Slot* __res
     o[5] = 1.0 - g * n0[2] * n0[2];
 }
 
-// update_correspondences: nearest target point of trans_f * a within the correspondence distance, and the Mahalanobis matrix of the pair
+// update_correspondences: nearest target point of trans_f * a within the correspondence distance, and the Mahalanobis matrix of the pair.
+// The ring search runs rings 0 .. kGicpCorrRings, whatever the data; a group that has not settled by then takes the minimum over the whole
+// target pool, n_tgt / 16 steps with the same keys.  Both loops have fixed trip counts.
+constexpr int kGicpCorrRings = 16;
 __global__ void __launch_bounds__(kGrpThreads) gicp_corr_kernel(const Slot* __restrict__ table, uint32_t mask, const float4* __restrict__ tpool, float res,
                                                                 const double* __restrict__ tcov, const float4* __restrict__ spool, const double* __restrict__ scov,
-                                                                uint32_t n_src, GicpXform X, float max_d2, int32_t* __restrict__ corr, double* __restrict__ maha) {
+                                                                uint32_t n_src, uint32_t n_tgt, GicpXform X, float max_d2, int32_t* __restrict__ corr,
+                                                                double* __restrict__ maha) {
     const int lane = threadIdx.x & (kGrp - 1);
     const uint32_t i = (blockIdx.x * kGrpThreads + threadIdx.x) / kGrp;
     if (i >= n_src) return;
@@ -136,11 +188,17 @@ __global__ void __launch_bounds__(kGrpThreads) gicp_corr_kernel(const Slot* __re
     const float tx = (X.Rf[0] * a.x + X.Rf[1] * a.y) + (X.Rf[2] * a.z + X.tf[0]);
     const float ty = (X.Rf[3] * a.x + X.Rf[4] * a.y) + (X.Rf[5] * a.z + X.tf[1]);
     const float tz = (X.Rf[6] * a.x + X.Rf[7] * a.y) + (X.Rf[8] * a.z + X.tf[2]);
+    // a transformed point that is not finite is at no distance from anything: no pair, and no search (the whole group leaves: one point, one i)
+    if (!(fabsf(tx) <= FLT_MAX && fabsf(ty) <= FLT_MAX && fabsf(tz) <= FLT_MAX)) {
+        if (lane == 0) corr[i] = -1;
+        return;
+    }
     int kx, ky, kz;
     pos2grid_ndt(tx, ty, tz, res, kx, ky, kz);
-    const float gap = cell_gap3(tx, ty, tz, res, kx, ky, kz);
+    const float gap = fminf(fminf(cell_gap_cells(tx, res, kx), cell_gap_cells(ty, res, ky)), cell_gap_cells(tz, res, kz));
     unsigned long long bk = ~0ull;  // (squared distance, index) of the nearest so far, the same in all lanes of the group after every ring
-    for (int r = 0;; r++) {
+    bool settled = false;           // the nearest is within the radius covered, or that radius is past the correspondence distance
+    for (int r = 0; r <= kGicpCorrRings && !settled; r++) {
         const int n_cells = shell_cells(r);
         for (int t0 = 0; t0 < n_cells; t0 += kGrp) {
             const int t = t0 + lane;
@@ -149,7 +207,7 @@ __global__ void __launch_bounds__(kGrpThreads) gicp_corr_kernel(const Slot* __re
             if (t < n_cells) {
                 int dx, dy, dz;
                 shell_cell(r, t, dx, dy, dz);
-                found = grid_find(table, mask, kx + dx, ky + dy, kz + dz, ptr, cnt);
+                found = grid_find(table, mask, cell_add(kx, dx), cell_add(ky, dy), cell_add(kz, dz), ptr, cnt);
             }
             if (found)
                 for (uint32_t j = 0; j < cnt; j++) {
@@ -167,8 +225,24 @@ __global__ void __launch_bounds__(kGrpThreads) gicp_corr_kernel(const Slot* __re
             const unsigned long long o = __shfl_xor(bk, off, kGrp);
             if (o < bk) bk = o;
         }
-        const float reach = (float)r * res + gap;
-        if ((bk != ~0ull && __uint_as_float((uint32_t)(bk >> 32)) <= reach * reach) || reach * reach > max_d2) break;
+        const float floor2 = ring_floor2(r, gap, res);
+        settled = (bk != ~0ull && __uint_as_float((uint32_t)(bk >> 32)) < floor2) || floor2 > max_d2;
+    }
+    if (!settled) {  // past the last ring (a source point far from the target under a wide or no correspondence distance): the whole target
+        for (uint32_t j = lane; j < n_tgt; j += kGrp) {
+            const float4 q = tpool[j];
+            const float ex = q.x - tx, ey = q.y - ty, ez = q.z - tz;
+            const float d2 = (ex * ex + ey * ey) + ez * ez;
+            if (d2 == d2) {
+                const unsigned long long c = cand_key(d2, j);
+                if (c < bk) bk = c;
+            }
+        }
+#pragma unroll
+        for (int off = kGrp / 2; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_xor(bk, off, kGrp);
+            if (o < bk) bk = o;
+        }
     }
     if (lane != 0) return;
     const float best = bk != ~0ull ? __uint_as_float((uint32_t)(bk >> 32)) : INFINITY;
@@ -457,6 +531,12 @@ int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
     if (!g || (!xyzi && n)) return LIO_E_INVALID;
     if (n > g->max_points) { set_error("lio_gicp: cloud of %u points exceeds max_points %u", n, g->max_points); return LIO_E_CAPACITY; }
     if ((int)n < g->k) { set_error("lio_gicp: a cloud needs at least k = %d points", g->k); return LIO_E_INVALID; }
+    // the searches are specified on finite points (a NaN is at no distance from anything); refused before anything is touched
+    for (uint32_t i = 0; i < n; i++)
+        if (!std::isfinite(xyzi[4 * (size_t)i]) || !std::isfinite(xyzi[4 * (size_t)i + 1]) || !std::isfinite(xyzi[4 * (size_t)i + 2])) {
+            set_error("lio_gicp: point %u has a coordinate that is not finite", i);
+            return LIO_E_INVALID;
+        }
     hipSetDevice(g->device);
     // an EMPTY grid per cloud: the first batch into an empty map is laid out exactly (cell by cell, contiguous from the start of the pool).
     // The grid object is made once and emptied in place afterwards (map_clear: memsets; a fresh lio_map_create per call was 5-65 ms of
@@ -475,8 +555,10 @@ int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
     if (rc != LIO_OK) return rc;
     g->n[which] = n;
     g->rows[which] = false;
+    g->gridded[which] = true;
     if (which == 0) g->vmap_valid = false;
-    hipLaunchKernelGGL(gicp_cov_kernel, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which]);
+    hipLaunchKernelGGL(gicp_cov_kernel<false>, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which],
+                       (int32_t*)nullptr);
     LIO_HIP_TRY(hipGetLastError());
     LIO_HIP_TRY(hipStreamSynchronize(st));
     return LIO_OK;
@@ -551,8 +633,10 @@ int gicp_cloud_covariances(lio_gicp* g, int which, const float4* d_pts, uint32_t
     if (rc != LIO_OK) return rc;
     g->n[which] = n;
     g->rows[which] = true;
+    g->gridded[which] = true;
     if (which == 0) g->vmap_valid = false;
-    hipLaunchKernelGGL(gicp_cov_kernel, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which]);
+    hipLaunchKernelGGL(gicp_cov_kernel<false>, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which],
+                       (int32_t*)nullptr);
     hipLaunchKernelGGL(gicp_scatter_cov_kernel, (n + 255) / 256, 256, 0, st, m->pool, n, g->cov[which], d_cov6_rows);
     LIO_HIP_TRY(hipGetLastError());
     LIO_HIP_TRY(hipStreamSynchronize(st));
@@ -575,6 +659,7 @@ int gicp_adopt_cloud(lio_gicp* g, int which, const float4* d_pts, const double* 
         LIO_HIP_TRY(hipMemcpyAsync(g->cov[1], d_cov6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
         g->n[1] = n;
         g->rows[1] = false;
+        g->gridded[1] = false;
         LIO_HIP_TRY(hipStreamSynchronize(st));
         return LIO_OK;
     }
@@ -584,6 +669,7 @@ int gicp_adopt_cloud(lio_gicp* g, int which, const float4* d_pts, const double* 
     if (rc != LIO_OK) return rc;
     g->n[0] = n;
     g->rows[0] = true;
+    g->gridded[0] = true;
     g->vmap_valid = false;
     hipLaunchKernelGGL(gicp_gather_cov_kernel, (n + 255) / 256, 256, 0, st, m->pool, n, d_cov6, g->cov[0]);
     LIO_HIP_TRY(hipGetLastError());
@@ -594,6 +680,14 @@ int gicp_adopt_cloud(lio_gicp* g, int which, const float4* d_pts, const double* 
 }  // namespace lio
 
 namespace {
+
+// the pose entries the kernels read (rows 0 .. 2) are finite, and the correspondence distance is a distance (+inf = no limit)
+bool gicp_pose_ok(const double T[16], double max_corr_dist, const char* who) {
+    for (int a = 0; a < 12; a++)
+        if (!std::isfinite(T[a])) { set_error("%s: the pose is not finite", who); return false; }
+    if (!(max_corr_dist >= 0.0)) { set_error("%s: max_corr_dist is negative or NaN", who); return false; }
+    return true;
+}
 
 int gicp_eval(lio_gicp* g, const double T[16], double max_corr_dist, bool update, bool deriv, double* H, double* b, double* err, uint32_t* n_corr) {
     if (!g->grid[0] || !g->grid[1]) { set_error("lio_gicp: set target and source first"); return LIO_E_STATE; }
@@ -620,7 +714,7 @@ int gicp_eval(lio_gicp* g, const double T[16], double max_corr_dist, bool update
     } else {
     if (update) {
         const double d2 = max_corr_dist * max_corr_dist;
-        hipLaunchKernelGGL(gicp_corr_kernel, (uint32_t)(((uint64_t)ns * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, mt->table, mt->table_mask, mt->pool, g->res, g->cov[0], g->grid[1]->pool, g->cov[1], ns, X,
+        hipLaunchKernelGGL(gicp_corr_kernel, (uint32_t)(((uint64_t)ns * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, mt->table, mt->table_mask, mt->pool, g->res, g->cov[0], g->grid[1]->pool, g->cov[1], ns, g->n[0], X,
                            d2 > 3.0e38 ? 3.0e38f : (float)d2, g->corr, g->maha);
     }
     if (deriv) hipLaunchKernelGGL(gicp_cost_kernel<true>, blocks, kGicpThreads, 0, st, mt->pool, g->grid[1]->pool, ns, g->corr, g->maha, X, g->partial);
@@ -769,15 +863,52 @@ int lio_gicp_correspondences(lio_gicp* g, int32_t* corr, uint32_t cap) {
     return (int)g->n[1];
 }
 
+int lio_gicp_neighbours(lio_gicp* g, int which, int32_t* idx, uint32_t cap_points) {
+    if (!g || !idx || which < 0 || which > 1) return LIO_E_INVALID;
+    if (!g->grid[which] || !g->gridded[which]) { set_error("lio_gicp_neighbours: cloud %d has no search grid", which); return LIO_E_STATE; }
+    const uint32_t n = g->n[which];
+    if (n > cap_points) return LIO_E_CAPACITY;
+    hipSetDevice(g->device);
+    lio_map* m = g->grid[which];
+    hipStream_t st = m->stream;
+    double* d_cov = nullptr;  // the covariances of this run go beside the cloud's own, which stay as they are
+    int32_t* d_idx = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d_cov), (size_t)n * 6 * sizeof(double)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d_idx), (size_t)n * 2 * kGrp * sizeof(int32_t)) != hipSuccess) {
+        if (d_cov) hipFree(d_cov);
+        set_error("lio_gicp_neighbours: allocation failed");
+        return LIO_E_DEVICE;
+    }
+    hipLaunchKernelGGL(gicp_cov_kernel<true>, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, d_cov, d_idx);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(idx, d_idx, (size_t)n * 2 * kGrp * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    hipFree(d_cov);
+    hipFree(d_idx);
+    if (e != hipSuccess) { set_error("lio_gicp_neighbours: %s", hipGetErrorString(e)); return LIO_E_DEVICE; }
+    return (int)n;
+}
+
+int lio_gicp_mahalanobis(lio_gicp* g, double* maha6, uint32_t cap) {
+    if (!g || !maha6 || !g->grid[1]) return LIO_E_INVALID;
+    if (g->voxel_res > 0.0) { set_error("lio_gicp_mahalanobis: the voxel mode keeps its matrices per (point, voxel); switch it off first"); return LIO_E_STATE; }
+    if (g->n[1] > cap) return LIO_E_CAPACITY;
+    hipSetDevice(g->device);
+    LIO_HIP_TRY(hipMemcpy(maha6, g->maha, (size_t)g->n[1] * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    return (int)g->n[1];
+}
+
 int lio_gicp_linearize(lio_gicp* g, const double T[16], double max_corr_dist, int update_corr, int with_derivatives, double H[36], double b[6], double* err,
                        uint32_t* n_corr) {
     if (!g || !T) return LIO_E_INVALID;
+    if (!gicp_pose_ok(T, max_corr_dist, "lio_gicp_linearize")) return LIO_E_INVALID;
     hipSetDevice(g->device);
     return gicp_eval(g, T, max_corr_dist, update_corr != 0, with_derivatives != 0, H, b, err, n_corr);
 }
 
 int lio_gicp_align(lio_gicp* g, const double guess[16], const lio_ndt_params* prm, double max_corr_dist, double out[16], int* iterations, int* converged) {
     if (!g || !guess || !out) return LIO_E_INVALID;
+    if (!gicp_pose_ok(guess, max_corr_dist, "lio_gicp_align")) return LIO_E_INVALID;
     hipSetDevice(g->device);
     lio_ndt_params p;
     if (prm) p = *prm;

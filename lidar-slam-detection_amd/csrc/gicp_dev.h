@@ -82,6 +82,7 @@ struct lio_gicp {
     uint32_t max_points = 0;
     lio_map* grid[2] = {nullptr, nullptr};  // 0 target, 1 source: hash grids holding the clouds
     uint32_t n[2] = {0, 0};
+    bool gridded[2] = {false, false};  // the cloud lies in its grid (not: a source adopted as it stands, which nothing searches)
     bool rows[2] = {false, false};  // the grid's copy carries, where the intensity was, the row its point has in the caller's cloud
     double* cov[2] = {nullptr, nullptr};
     int32_t* corr = nullptr;

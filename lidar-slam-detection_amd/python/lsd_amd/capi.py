@@ -54,7 +54,7 @@ SYMBOLS = [
     "lio_state_predict", "lio_eskf_update_cb", "lio_eskf_update_ws_cb", "lio_eskf_update_sums_cb",
     "lio_ndt_create", "lio_ndt_destroy", "lio_ndt_set_target", "lio_ndt_set_target_device", "lio_ndt_num_voxels", "lio_ndt_fitness_score", "lio_ndt_overlap_score", "lio_ndt_voxel_at",
     "lio_ndt_linearize", "lio_ndt_default_params", "lio_ndt_align", "lio_ndt_align_batch", "lio_ndt_enable_kernel_timing", "lio_ndt_kernel_times",
-    "lio_gicp_create", "lio_gicp_destroy", "lio_gicp_set_target", "lio_gicp_set_source", "lio_gicp_set_voxel_mode", "lio_gicp_voxel_at", "lio_gicp_download", "lio_gicp_correspondences", "lio_gicp_linearize", "lio_gicp_align",
+    "lio_gicp_create", "lio_gicp_destroy", "lio_gicp_set_target", "lio_gicp_set_source", "lio_gicp_set_voxel_mode", "lio_gicp_voxel_at", "lio_gicp_download", "lio_gicp_correspondences", "lio_gicp_neighbours", "lio_gicp_mahalanobis", "lio_gicp_linearize", "lio_gicp_align",
     "lio_loop_default_params", "lio_loop_find_candidates", "lio_loop_information_matrix", "lio_loop_create", "lio_loop_destroy", "lio_loop_reset",
     "lio_loop_add_keyframe_host", "lio_loop_set_pose", "lio_loop_num_keyframes", "lio_loop_download_keyframe", "lio_loop_detect", "lio_loop_edges",
     "lio_loop_last_report", "lio_loop_last_times", "lio_loop_align_candidates", "lio_loop_align_fine", "lio_loop_pair_information",
@@ -449,6 +449,8 @@ def lib():
     sig("lio_gicp_voxel_at", cint, vp, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double))
     sig("lio_gicp_download", cint, vp, cint, f32p, f64p, u32)
     sig("lio_gicp_correspondences", cint, vp, i32p, u32)
+    sig("lio_gicp_neighbours", cint, vp, cint, i32p, u32)
+    sig("lio_gicp_mahalanobis", cint, vp, f64p, u32)
     sig("lio_gicp_linearize", cint, vp, f64p, dbl, cint, cint, f64p, f64p, f64p, C.POINTER(u32))
     sig("lio_gicp_align", cint, vp, f64p, C.POINTER(NdtParams), dbl, f64p, C.POINTER(cint), C.POINTER(cint))
     lp, le, lr = C.POINTER(LoopParams), C.POINTER(LoopEdge), C.POINTER(LoopReport)

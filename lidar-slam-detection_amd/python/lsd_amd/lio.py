@@ -643,6 +643,20 @@ class Gicp:
         n = check(lib().lio_gicp_correspondences(self.h, ptr(out, C.c_int32), self.max_points), "gicp correspondences")
         return out[:n].copy()
 
+    def neighbours(self, which):
+        """(n, 32) int32: the sorted neighbour list of every point of cloud `which` in internal order (the point itself first or among its
+        duplicates), -1 = an empty place; places >= k hold candidates no nearer than the k-th"""
+        out = np.full((self.max_points, 32), -1, np.int32)
+        n = check(lib().lio_gicp_neighbours(self.h, int(which), ptr(out, C.c_int32), self.max_points), "gicp neighbours")
+        return out[:n].copy()
+
+    def mahalanobis(self):
+        """(n_source, 3, 3): (C_B + R C_A R^T)^-1 of the current pairs; rows without a pair are undefined"""
+        m = np.zeros((self.max_points, 6))
+        n = check(lib().lio_gicp_mahalanobis(self.h, ptr(m, C.c_double), self.max_points), "gicp mahalanobis")
+        c = m[:n]
+        return np.stack([c[:, 0], c[:, 1], c[:, 2], c[:, 1], c[:, 3], c[:, 4], c[:, 2], c[:, 4], c[:, 5]], 1).reshape(n, 3, 3)
+
     def linearize(self, T, max_corr_dist=2.0, update_corr=True, with_derivatives=True):
         T = f64(T).reshape(4, 4)
         H, b, err, nc = np.zeros((6, 6)), np.zeros(6), C.c_double(0), C.c_uint32(0)
