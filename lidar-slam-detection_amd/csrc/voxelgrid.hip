@@ -12,13 +12,14 @@
 // Pipeline (all sizes stay on the device; nothing is read back between stages):
 //   bbox      wave shuffle + LDS reduce, one set of ordered-uint atomics per workgroup
 //   keys      voxel index per point (every lane re-derives the grid from the bbox: no setup launch)
-//   4 x {hist, scatter}  stable 8-bit LSD radix sort of (key, point index); the scatter workgroups scan the
-//             [digit][tile] histogram themselves (no scan launch); passes above the significant key bits
-//             exit at once and the consumers pick the ping-pong buffer from the pass count
-//   count_heads / heads  voxel occupancy flags -> wave ballot + prefix-sum compaction (fixed order), fused
-//             with the gather of the points into sorted order
-//   centroid  one lane per voxel, sequential f32 sums; runs of >= 32 points are queued and summed one wave per
-//             run (coalesced loads, v_readlane broadcast) in the same sequential order
+//   4 x {hist, scatter}  stable 8-bit LSD radix sort of (key, point index); the first pass takes a key's position as its index (no index array is
+//             written beside the keys); the scatter workgroups scan the [digit][tile] histogram themselves (no scan launch); passes above the
+//             significant key bits exit at once and the consumers pick the ping-pong buffer from the pass count
+//   count_heads / heads  voxel occupancy flags -> wave ballot + prefix-sum compaction (fixed order), fused with the gather of the tile's points
+//             into LDS, half a tile (1024 points) at a time, and the centroid (sequential f32 sums) of every voxel whose run lies inside the
+//             staged half; the points of a run that crosses an edge of a half go to `sorted`, the run to a queue
+//   centroid_long  the queued runs, one wave per run (coalesced loads, LDS rows, four sum chains side by side) in the same sequential order;
+//             runs of >= 2048 points one component per wave (monster_component_sum)
 #include "device_prims.h"
 
 namespace lio {
@@ -177,7 +178,7 @@ __device__ inline VgGrid vg_derive(const uint32_t bmin[3], const uint32_t bmax[3
 // no histogram launch of its own (the later passes histogram the re-ordered keys)
 template <bool FOLD>
 __device__ __forceinline__ void vg_keys_body(const float4* __restrict__ in, uint32_t n, float inv, ScanDev* sd,
-                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ hist,
+                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ hist,
                                                            uint32_t nblocks, const uint32_t* __restrict__ parts, uint32_t bx = 0xFFFFFFFFu) {
     if (bx == 0xFFFFFFFFu) bx = blockIdx.x;  // (the tile this call works on: the launch's own block unless the caller maps blocks to tiles itself)
     // the cloud's points first (they do not depend on the box), then the fold of the tiles' box records: every workgroup forms the same box
@@ -250,8 +251,7 @@ __device__ __forceinline__ void vg_keys_body(const float4* __restrict__ in, uint
             const int i2 = (int)(floorf(p[r].z * inv) - (float)g.minb[2]);
             key = (uint32_t)(i0 + i1 * g.mul1 + i2 * g.mul2);
         }
-        keys[i] = key;
-        vals[i] = i;
+        keys[i] = key;  // (no index array beside it: the first radix pass takes a key's position as its index)
         atomicAdd(&h[key & 255u], 1u);
     }
     __syncthreads();
@@ -337,7 +337,12 @@ __device__ __forceinline__ void radix_scatter_body(uint32_t* __restrict__ ka, ui
         ok[r] = i < n;
         const uint32_t ic = ok[r] ? i : 0u;  // (unconditional loads at clamped indices, in flight together)
         k[r] = kin[ic];
-        v[r] = vin[ic];
+        v[r] = i;
+    }
+    // the first pass sorts the identity: a key's index is its own position, nothing wrote an index array for it to read (uniform over the launch)
+    if (pass != 0) {
+#pragma unroll
+        for (int r = 0; r < kItems; r++) v[r] = vin[ok[r] ? base + r * 64 + lane : 0u];
     }
     pin_loaded(nbits_w);
 #pragma unroll
@@ -458,14 +463,36 @@ __device__ __forceinline__ void vg_count_heads_body(const uint32_t* __restrict__
     if (threadIdx.x == 0) blockcnt[bx] = c;
 }
 
-// compaction of the voxel heads (ballot + prefix sum, fixed order) and the gather of the points into sorted order.
+// Runs of >= kLongRun points (the rings close to the sensor: a few hundred voxels holding half of the points) are not walked by one lane; the
+// few runs of thousands of points (a wall a metre from the sensor, the ground ring under it) are summed one COMPONENT per wave by integer
+// arithmetic inside the running sum's binade (monster_sum below).
+constexpr uint32_t kLongRun = 32;
+// vg_heads stages its tile in LDS in parts of kStageItems x kThreads points: two halves of 1024 points (16 KB) each, so a run across the middle
+// of a tile counts as crossing like one across a tile edge.  (Measured and not kept, tools/experiments/README.md round 7: the whole tile at once --
+// 32 KB, 4 waves per SIMD -- for the same chain time.)
+constexpr int kStageItems = 4;
+constexpr int kStages = kItems / kStageItems;
+constexpr uint32_t kStagePts = kStageItems * kThreads;
+static_assert(kStageItems % 4 == 0 && kItems % kStageItems == 0, "the gathers go out four at a time");
+constexpr uint32_t kMonsterRun = 2048;
+constexpr uint32_t kMonsterBlocks = 16;       // workgroups of the long-run launch that serve the monster queue (one scan)
+constexpr uint32_t kMonsterBlocksBatch = 16;  // ... per slot of the batched chain
+
+// compaction of the voxel heads (ballot + prefix sum, fixed order), the gather of the tile's points through the sort's permutation, and the
+// centroid of every voxel whose run lies inside one half of the tile: the gathered points are staged in LDS half a tile at a time (kStagePts =
+// 1024 points, 16 KB, beside a run table of the tile's head positions) and summed from there in ascending sorted position -- PCL's sequential
+// f32 sums, `sum / (float)count` -- by one lane per run, runs of >= kLongRun points by four lanes (one coordinate each).  Only the points of a
+// run that crosses an edge of a staged half (a tile edge or the middle of the tile) travel through `sorted`: the half that holds such a run's
+// head queues it for vg_centroid_long_* (the monster queue at >= kMonsterRun points, the long-run queue otherwise, whatever its length).  Every
+// tile is independent.
 // (Measured in round 4 and not kept: every load of the tile requested up front, the ballot rounds on registers -- 11.4 -> 13.8 us for one scan,
 // 42 -> 79 us for a batched round: the eight gathers through the sort's permutation then leave together and queue behind each other.)
 __device__ __forceinline__ void vg_heads_body(const float4* __restrict__ in, const uint32_t* __restrict__ ka,
                                                             const uint32_t* __restrict__ kb, const uint32_t* __restrict__ va,
                                                             const uint32_t* __restrict__ vb, uint32_t n, ScanDev* sd,
                                                             const uint32_t* __restrict__ blockcnt, uint32_t* __restrict__ hpos,
-                                                            float4* __restrict__ sorted, float4* __restrict__ out, uint32_t max_ds, uint32_t* __restrict__ host_nds,
+                                                            float4* __restrict__ sorted, float4* __restrict__ out, uint32_t* __restrict__ longlist,
+                                                            uint32_t max_ds, uint32_t* __restrict__ host_nds,
                                                             uint32_t launched_passes, uint32_t last_block, uint32_t bx = 0xFFFFFFFFu) {
     if (bx == 0xFFFFFFFFu) bx = blockIdx.x;  // (the tile this call works on: the launch's own block unless the caller maps blocks to tiles itself)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -483,10 +510,15 @@ __device__ __forceinline__ void vg_heads_body(const float4* __restrict__ in, con
         if (bx == 0 && tid == 0) { sd->n_ds = n; host_nds[0] = n; host_nds[1] = 0u; }
         return;
     }
-    const bool odd = active_passes(sd) & 1;
+    const uint32_t act = active_passes(sd);
+    const bool odd = act & 1;
     const uint32_t* keys = odd ? kb : ka;
     const uint32_t* vals = odd ? vb : va;
+    // the index buffer holds this scan's permutation only if every radix pass its box needs was launched (the first pass writes the first
+    // indices); a scan without a finite point has no pass at all.  Otherwise nothing below dereferences an index: the host runs the chain again.
+    const bool sorted_ok = act != 0u && act <= launched_passes;
     __shared__ uint32_t red[kWaves];
+    __shared__ uint32_t n_lq;
     // exclusive prefix of the tiles before this one (fixed order -> deterministic output slots)
     uint32_t pre = 0;
     for (uint32_t b = tid; b < bx; b += kThreads) pre += blockcnt[b];
@@ -497,8 +529,10 @@ __device__ __forceinline__ void vg_heads_body(const float4* __restrict__ in, con
     uint32_t run = 0;
     for (int w = 0; w < kWaves; w++) run += red[w];
     __syncthreads();
+    const uint32_t run0 = run;  // the output slot of this tile's first head
 
     const uint32_t total = sd->total_cells;
+    const uint32_t n_valid = sd->n_valid;
     const uint32_t base = bx * kTile;
     const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     // Round 4, second form.  Until then: per item { key, previous key, index, the gather through the index, two workgroup barriers } -- four dependent
@@ -515,7 +549,23 @@ __device__ __forceinline__ void vg_heads_body(const float4* __restrict__ in, con
         kp[r] = keys[ic ? ic - 1u : 0u];
         vv[r] = vals[ic];
     }
+    // the tile is staged in kStages parts of kStagePts points.  The keys on both sides of every part's edge (the same for every thread) tell which
+    // runs go on across it
+    uint32_t efirst[kStages + 1], eprev[kStages + 1];
+    bool ecross[kStages + 1];
+#pragma unroll
+    for (int e = 0; e <= kStages; e++) {
+        const uint32_t g = base + (uint32_t)e * kStagePts;
+        efirst[e] = keys[g < n ? g : n - 1u];
+        eprev[e] = keys[(g < n ? g : n) ? (g < n ? g : n) - 1u : 0u];  // (the last key of the part before the edge, or of the scan)
+    }
+#pragma unroll
+    for (int e = 0; e <= kStages; e++) {
+        const uint32_t g = base + (uint32_t)e * kStagePts;
+        ecross[e] = g != 0u && g < n && efirst[e] < total && eprev[e] == efirst[e];
+    }
     __shared__ uint32_t wcnt[kItems][kWaves];
+    __shared__ uint16_t tab[kTile];  // the tile's run table: position in the tile of its h-th head (a run ends where the next starts)
     unsigned long long hm[kItems];
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
@@ -525,6 +575,8 @@ __device__ __forceinline__ void vg_heads_body(const float4* __restrict__ in, con
         if (lane == 0) wcnt[r][wave] = (uint32_t)__popcll(hm[r]);
     }
     __syncthreads();
+    uint32_t hcum[kStages + 1];  // heads of the tile before each part
+    hcum[0] = 0;
 #pragma unroll
     for (int r = 0; r < kItems; r++) {
         uint32_t woff = 0, rtot = 0;
@@ -537,20 +589,86 @@ __device__ __forceinline__ void vg_heads_body(const float4* __restrict__ in, con
         if ((hm[r] >> lane) & 1ull) {
             const uint32_t slot = run + woff + (uint32_t)__popcll(hm[r] & lt);
             if (slot < max_ds) hpos[slot] = base + r * kThreads + tid;
+            tab[slot - run0] = (uint16_t)(r * kThreads + tid);
         }
         run += rtot;
+        if ((r + 1) % kStageItems == 0) hcum[(r + 1) / kStageItems] = run - run0;
     }
+    __shared__ float4 pts[kStagePts];              // the part's points in sorted order
+    __shared__ uint16_t lq[kStagePts / kLongRun];  // heads of the runs of >= kLongRun points inside the part
+    if (sorted_ok) {
 #pragma unroll
-    for (int r0 = 0; r0 < kItems; r0 += 4) {
-        float4 pt[4];
+        for (int st = 0; st < kStages; st++) {
+            const bool left_cross = ecross[st], right_cross = ecross[st + 1];
+            const uint32_t kfirst = efirst[st], klast = eprev[st + 1];
+            if (st) __syncthreads();  // (the part before has been summed: its points may go)
 #pragma unroll
-        for (int k = 0; k < 4; k++) pt[k] = in[vv[r0 + k]];  // (a thread beyond the scan's end gathers the last point again and drops it)
+            for (int r0 = st * kStageItems; r0 < (st + 1) * kStageItems; r0 += 4) {
+                float4 pt[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) pin_loaded(pt[k]);
+                for (int k = 0; k < 4; k++) pt[k] = in[vv[r0 + k]];  // (a thread beyond the scan's end gathers the last point again and drops it)
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t i = base + (r0 + k) * kThreads + tid;
-            if (i < n) sorted[i] = pt[k];
+                for (int k = 0; k < 4; k++) pin_loaded(pt[k]);
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t i = base + (r0 + k) * kThreads + tid;
+                    if (i < n) {
+                        pts[(r0 + k - st * kStageItems) * kThreads + tid] = pt[k];
+                        // a point of a run that goes on in a neighbouring part or tile: vg_centroid_long_* sums that run from `sorted`
+                        if ((left_cross && kc[r0 + k] == kfirst) || (right_cross && kc[r0 + k] == klast)) sorted[i] = pt[k];
+                    }
+                }
+            }
+            if (tid == 0) n_lq = 0;
+            __syncthreads();
+            // invalid (non-finite) points sort behind every voxel: the part's last run ends where they begin
+            const uint32_t p0 = (uint32_t)st * kStagePts;  // the part's first position in the tile
+            const uint32_t vend = n_valid < base + p0 + kStagePts ? n_valid - base : p0 + kStagePts;  // (a head in the part implies n_valid > base + p0)
+            const uint32_t h0 = hcum[st], h1 = hcum[st + 1];
+            for (uint32_t h = h0 + tid; h < h1; h += kThreads) {
+                const uint32_t a = tab[h] - p0, b = (h + 1u < h1 ? (uint32_t)tab[h + 1u] : vend) - p0;
+                const uint32_t slot = run0 + h;
+                if (h + 1u == h1 && right_cross) {  // the run goes on behind the part: queued, by its length
+                    if (slot < max_ds) {
+                        const uint32_t far = base + p0 + a + kMonsterRun - 1u;
+                        if (far < n && keys[far] == klast) longlist[max_ds - 1u - atomicAdd(&sd->n_monster, 1u)] = slot;
+                        else longlist[atomicAdd(&sd->n_long, 1u)] = slot;
+                    }
+                } else if (b - a >= kLongRun) {
+                    lq[atomicAdd(&n_lq, 1u)] = (uint16_t)h;
+                } else if (slot < max_ds) {
+                    float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
+                    for (uint32_t j = a; j < b; j += 4) {
+                        float4 p[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) p[k] = pts[(j + k < b) ? (j + k) : (b - 1)];
+#pragma unroll
+                        for (int k = 0; k < 4; k++)
+                            if (j + k < b) { sx = sx + p[k].x; sy = sy + p[k].y; sz = sz + p[k].z; sw = sw + p[k].w; }
+                    }
+                    const float c = (float)(b - a);
+                    out[slot] = make_float4(sx / c, sy / c, sz / c, sw / c);
+                }
+            }
+            __syncthreads();
+            // the long runs inside the part: four lanes per run, lane c owning coordinate c (sixteen runs per wave side by side)
+            const uint32_t nq = n_lq;
+            const float* flat = reinterpret_cast<const float*>(pts) + (tid & 3);
+            for (uint32_t q = (uint32_t)tid >> 2; q < nq; q += kThreads / 4) {
+                const uint32_t h = lq[q];
+                const uint32_t a = tab[h] - p0, b = (h + 1u < h1 ? (uint32_t)tab[h + 1u] : vend) - p0;
+                const uint32_t slot = run0 + h;
+                float t = 0.f;
+                for (uint32_t j = a; j < b; j += 8) {
+                    float x[8];
+#pragma unroll
+                    for (int k = 0; k < 8; k++) x[k] = flat[4u * ((j + k < b) ? (j + k) : (b - 1))];
+#pragma unroll
+                    for (int k = 0; k < 8; k++)
+                        if (j + k < b) t = t + x[k];
+                }
+                if (slot < max_ds) reinterpret_cast<float*>(&out[slot])[tid & 3] = t / (float)(b - a);
+            }
         }
     }
     if (bx == last_block && tid == 0) {
@@ -564,83 +682,6 @@ __device__ __forceinline__ void vg_heads_body(const float4* __restrict__ in, con
         host_nds[1] = err;
         host_nds[2] = active_passes(sd);
     }
-}
-
-// one lane per occupied voxel: centroid of its run in ascending input order (f32 running sums, as PCL does).
-// Runs shorter than 32 points are walked by the owning lane, four loads in flight.  Longer runs (the rings
-// close to the sensor: a few hundred voxels holding half of the points) are queued for the wave-per-voxel
-// kernel below, so that their latency is spread over the chip instead of serialising one wave.
-constexpr uint32_t kLongRun = 32;
-constexpr uint32_t kCentroidGridCap = 96;  // workgroups per scan of vg_centroid_*: 96 x 256 = 24 576 voxels per sweep of the grid
-// ... and the few runs of thousands of points (a wall a metre from the sensor, the ground ring under it) go to a second queue, filled from the
-// top of the same array, whose runs are summed one COMPONENT per wave by integer arithmetic inside the running sum's binade (monster_sum below)
-constexpr uint32_t kMonsterRun = 2048;
-constexpr uint32_t kMonsterBlocks = 16;       // workgroups of the long-run launch that serve the monster queue (one scan)
-constexpr uint32_t kMonsterBlocksBatch = 16;  // ... per slot of the batched chain (its own launch there)
-
-__device__ __forceinline__ void vg_centroid_body(const float4* __restrict__ sorted, const uint32_t* __restrict__ hpos,
-                                                               ScanDev* __restrict__ sd, float4* __restrict__ out,
-                                                               uint32_t* __restrict__ longlist, uint32_t max_ds, uint32_t vb) {
-    // vb: the block of kThreads voxels this call works on -- the kernels stride over the scan's blocks (a grid sized for max_ds = 100 000 voxels left
-    // 345 of 391 workgroups per slot to start, wait for the scan's size and exit)
-    if (sd->passthrough) return;
-    const uint32_t nv = sd->n_ds;
-    const uint32_t v = vb * kThreads + threadIdx.x;
-    if (v >= nv) return;
-    // (both run bounds and the scan's valid count requested together: the conditional form was two memory round trips one after the other)
-    uint32_t a = hpos[v];
-    uint32_t b_next = hpos[v + 1 < nv ? v + 1 : v];
-    const uint32_t n_valid = sd->n_valid;
-    pin_loaded(a);
-    pin_loaded(b_next);
-    const uint32_t b = (v + 1 < nv) ? b_next : n_valid;  // invalid (non-finite) points sort behind every voxel
-    const bool is_monster = b - a >= kMonsterRun;
-    const unsigned long long mm = __ballot(is_monster);
-    if (mm) {
-        const int lane = threadIdx.x & 63;
-        const int leader = __ffsll((long long)mm) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&sd->n_monster, (uint32_t)__popcll(mm));
-        base = __shfl(base, leader);
-        if (is_monster) {
-            longlist[max_ds - 1u - (base + __popcll(mm & ((1ull << lane) - 1ull)))] = v;
-            return;
-        }
-    }
-    // queue the long runs: one atomic per wave (ballot + popcount), not one per voxel
-    const bool is_long = b - a >= kLongRun;
-    const unsigned long long lm = __ballot(is_long);
-    if (lm) {
-        const int lane = threadIdx.x & 63;
-        const int leader = __ffsll((long long)lm) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&sd->n_long, (uint32_t)__popcll(lm));
-        base = __shfl(base, leader);
-        if (is_long) {
-            longlist[base + __popcll(lm & ((1ull << lane) - 1ull))] = v;
-            return;
-        }
-    }
-    float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
-    // the first eight points of the run in one request (most runs end there: one memory round trip instead of two), then four at a time
-    {
-        float4 p[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) p[k] = sorted[(a + k < b) ? (a + k) : (b - 1)];
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            if (a + k < b) { sx = sx + p[k].x; sy = sy + p[k].y; sz = sz + p[k].z; sw = sw + p[k].w; }
-    }
-    for (uint32_t j = a + 8; j < b; j += 4) {
-        float4 p[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) p[k] = sorted[(j + k < b) ? (j + k) : (b - 1)];
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (j + k < b) { sx = sx + p[k].x; sy = sy + p[k].y; sz = sz + p[k].z; sw = sw + p[k].w; }
-    }
-    const float c = (float)(b - a);
-    out[v] = make_float4(sx / c, sy / c, sz / c, sw / c);
 }
 
 // one wave per long run.  The sum itself is PCL's sequential f32 sum -- a dependent chain by definition -- run as four chains side by side (lanes
@@ -785,6 +826,7 @@ __device__ __forceinline__ void vg_centroid_long_body(const float4* __restrict__
                                                                     const uint32_t* __restrict__ longlist, uint32_t max_ds, uint32_t n_long_blocks) {
     if (sd->passthrough) return;
     const uint32_t nv = sd->n_ds, nl = sd->n_long;
+    if (nv == 0) return;  // (no voxel, or a chain that ended in an error: whatever vg_heads queued before its last tile knew is not summed)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __shared__ __attribute__((aligned(16))) float park[kWaves][kMonsterStep > 256 ? kMonsterStep : 256];
     if (WHICH == 2 || (WHICH == 0 && blockIdx.x >= n_long_blocks)) {
@@ -902,16 +944,16 @@ __global__ void __launch_bounds__(kThreads) vg_bbox_batch(const SlotDesc* __rest
     vg_bbox_atomic_body(d.raw, d.n_raw, d.sd);
 }
 __global__ void __launch_bounds__(kThreads) vg_keys_kernel(const float4* __restrict__ in, uint32_t n, float inv, ScanDev* sd,
-                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ hist,
+                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ hist,
                                                            uint32_t nblocks, const uint32_t* __restrict__ parts) {
-    vg_keys_body<true>(in, n, inv, sd, keys, vals, hist, nblocks, parts);
+    vg_keys_body<true>(in, n, inv, sd, keys, hist, nblocks, parts);
 }
 __global__ void __launch_bounds__(kThreads) vg_keys_batch(const SlotDesc* __restrict__ slots, float inv) {
     uint32_t slot, bx;
     vg_slot_tile(gridDim.y, slot, bx);
     const SlotDesc& d = slots[slot];
     if (!d.active || bx >= d.nblocks) return;
-    vg_keys_body<false>(d.raw, d.n_raw, inv, d.sd, d.keys_a, d.vals_a, d.hist, d.nblocks, nullptr, bx);
+    vg_keys_body<false>(d.raw, d.n_raw, inv, d.sd, d.keys_a, d.hist, d.nblocks, nullptr, bx);
 }
 __global__ void __launch_bounds__(kThreads) radix_hist_kernel(const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, uint32_t n,
                                                               int pass, uint32_t* __restrict__ hist, uint32_t nblocks, const ScanDev* sd) {
@@ -973,29 +1015,17 @@ __global__ void __launch_bounds__(kThreads) vg_heads_kernel(const float4* __rest
                                                             const uint32_t* __restrict__ kb, const uint32_t* __restrict__ va,
                                                             const uint32_t* __restrict__ vb, uint32_t n, ScanDev* sd,
                                                             const uint32_t* __restrict__ blockcnt, uint32_t* __restrict__ hpos,
-                                                            float4* __restrict__ sorted, float4* __restrict__ out, uint32_t max_ds, uint32_t* __restrict__ host_nds,
-                                                            uint32_t launched_passes) {
-    vg_heads_body(in, ka, kb, va, vb, n, sd, blockcnt, hpos, sorted, out, max_ds, host_nds, launched_passes, gridDim.x - 1);
+                                                            float4* __restrict__ sorted, float4* __restrict__ out, uint32_t* __restrict__ longlist,
+                                                            uint32_t max_ds, uint32_t* __restrict__ host_nds, uint32_t launched_passes) {
+    vg_heads_body(in, ka, kb, va, vb, n, sd, blockcnt, hpos, sorted, out, longlist, max_ds, host_nds, launched_passes, gridDim.x - 1);
 }
 __global__ void __launch_bounds__(kThreads) vg_heads_batch(const SlotDesc* __restrict__ slots, uint32_t launched_passes) {
     uint32_t slot, bx;
     vg_slot_tile(gridDim.y, slot, bx);
     const SlotDesc& d = slots[slot];
     if (!d.active || bx >= d.nblocks) return;
-    vg_heads_body(d.raw, d.keys_a, d.keys_b, d.vals_a, d.vals_b, d.n_raw, d.sd, d.blockcnt, d.hpos, d.sorted, d.ds_body, d.max_ds, d.host_nds,
+    vg_heads_body(d.raw, d.keys_a, d.keys_b, d.vals_a, d.vals_b, d.n_raw, d.sd, d.blockcnt, d.hpos, d.sorted, d.ds_body, d.longlist, d.max_ds, d.host_nds,
                   launched_passes, d.nblocks - 1, bx);
-}
-__global__ void __launch_bounds__(kThreads) vg_centroid_kernel(const float4* __restrict__ sorted, const uint32_t* __restrict__ hpos,
-                                                               ScanDev* __restrict__ sd, float4* __restrict__ out,
-                                                               uint32_t* __restrict__ longlist, uint32_t max_ds) {
-    const uint32_t nv = sd->passthrough ? 0u : sd->n_ds;
-    for (uint32_t vb = blockIdx.x; vb * kThreads < nv; vb += gridDim.x) vg_centroid_body(sorted, hpos, sd, out, longlist, max_ds, vb);
-}
-__global__ void __launch_bounds__(kThreads) vg_centroid_batch(const SlotDesc* __restrict__ slots) {
-    const SlotDesc& d = slots[blockIdx.y];
-    if (!d.active) return;
-    const uint32_t nv = d.sd->passthrough ? 0u : d.sd->n_ds;
-    for (uint32_t vb = blockIdx.x; vb * kThreads < nv; vb += gridDim.x) vg_centroid_body(d.sorted, d.hpos, d.sd, d.ds_body, d.longlist, d.max_ds, vb);
 }
 __global__ void __launch_bounds__(kThreads) vg_centroid_long_kernel(const float4* __restrict__ sorted, const uint32_t* __restrict__ hpos,
                                                                     const ScanDev* __restrict__ sd, float4* __restrict__ out,
@@ -1040,7 +1070,7 @@ int vg_downsample(lio_scan* s, float leaf, int passes) {
     }
     uint32_t* parts = reinterpret_cast<uint32_t*>(s->sorted);
     hipLaunchKernelGGL(vg_bbox_kernel, nblocks, kThreads, 0, st, s->raw, n, parts);
-    hipLaunchKernelGGL(vg_keys_kernel, nblocks, kThreads, 0, st, s->raw, n, inv, s->dev, s->keys_a, s->vals_a, s->hist, nblocks, parts);
+    hipLaunchKernelGGL(vg_keys_kernel, nblocks, kThreads, 0, st, s->raw, n, inv, s->dev, s->keys_a, s->hist, nblocks, parts);
     for (int pass = 0; pass < passes; pass++) {  // kernels of a pass the bounding box does not need return at once
         if (pass > 0) hipLaunchKernelGGL(radix_hist_kernel, nblocks, kThreads, 0, st, s->keys_a, s->keys_b, n, pass, s->hist, nblocks, s->dev);
         hipLaunchKernelGGL(radix_scatter_kernel, nblocks, kThreads, 0, st, s->keys_a, s->vals_a, s->keys_b, s->vals_b, n, pass, s->hist, nblocks,
@@ -1048,11 +1078,8 @@ int vg_downsample(lio_scan* s, float leaf, int passes) {
     }
     hipLaunchKernelGGL(vg_count_heads_kernel, nblocks, kThreads, 0, st, s->keys_a, s->keys_b, n, s->dev, s->blockcnt);
     hipLaunchKernelGGL(vg_heads_kernel, nblocks, kThreads, 0, st, s->raw, s->keys_a, s->keys_b, s->vals_a, s->vals_b, n, s->dev, s->blockcnt,
-                       s->hpos, s->sorted, s->ds_body, s->max_ds, s->host_nds_dev, (uint32_t)passes);
-    const uint32_t vbound = n < s->max_ds ? n : s->max_ds;
-    const uint32_t cblocks1 = (vbound + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(vg_centroid_kernel, cblocks1 < 2u * kCentroidGridCap ? cblocks1 : 2u * kCentroidGridCap, kThreads, 0, st, s->sorted, s->hpos, s->dev, s->ds_body,
-                       s->longlist, s->max_ds);  // (strides over the scan's blocks)
+                       s->hpos, s->sorted, s->ds_body, s->longlist, s->max_ds, s->host_nds_dev, (uint32_t)passes);
+    // (the runs inside a staged half tile were summed by vg_heads_kernel; what is left are the queued runs that cross an edge of one)
     hipLaunchKernelGGL(vg_centroid_long_kernel, 256 + kMonsterBlocks, kThreads, 0, st, s->sorted, s->hpos, s->dev, s->ds_body, s->longlist, s->max_ds, 256u);
     LIO_HIP_TRY(hipGetLastError());
     return LIO_OK;
@@ -1073,9 +1100,6 @@ int vg_downsample_batch(hipStream_t st, const SlotDesc* d_slots, int n_slots, ui
     }
     hipLaunchKernelGGL(vg_count_heads_batch, dim3(nblocks, B), kThreads, 0, st, d_slots);
     hipLaunchKernelGGL(vg_heads_batch, dim3(nblocks, B), kThreads, 0, st, d_slots, (uint32_t)passes);
-    const uint32_t vbound = max_raw < max_ds ? max_raw : max_ds;
-    const uint32_t cblocks = (vbound + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(vg_centroid_batch, dim3(cblocks < kCentroidGridCap ? cblocks : kCentroidGridCap, B), kThreads, 0, st, d_slots);  // (strides over the scan's blocks)
     static const bool split = []() { const char* e = getenv("LIO_VG_MONSTER_SPLIT"); return e && e[0] == '1'; }();
     if (split) {
         hipLaunchKernelGGL(vg_centroid_long_batch, dim3(64, B), kThreads, 0, st, d_slots);
