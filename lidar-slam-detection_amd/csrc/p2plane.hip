@@ -151,15 +151,19 @@ __device__ inline bool esti_plane_dev(const float4 pt[5], float threshold, float
         }
     }
     // triangularView<Upper>().solveInPlace(): Eigen's column-major vector solve is column oriented
-    // (x_i = b_i / a_ii, then b_r -= x_i * a_ri for the rows above)
+    // (x_i = b_i / a_ii, then b_r -= x_i * a_ri for the rows above); an entry that is exactly zero is left alone, as Eigen's
+    // `if (rhs[i] != 0)` leaves it: no division, so the zero keeps its sign (+0 / a negative pivot would be -0), and no update above
     float xs[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 2; i >= 0; i--) {
         if (i < nonzero) {
-            xs[i] = b[i] / A[i][i];
+            xs[i] = b[i];
+            if (b[i] != 0.f) {
+                xs[i] = b[i] / A[i][i];
 #pragma unroll
-            for (int r = 0; r < 3; r++)
-                if (r < i) b[r] = b[r] - xs[i] * A[r][i];
+                for (int r = 0; r < 3; r++)
+                    if (r < i) b[r] = b[r] - xs[i] * A[r][i];
+            }
         }
     }
     float nv[3] = {0.f, 0.f, 0.f};

@@ -437,11 +437,15 @@ bool esti_plane(float pabcd[4], const P4* pt, float threshold) {
         }
     }
     // triangularView<Upper>().solveInPlace: Eigen's column-major vector solve is column oriented --
-    // x_i = b_i / a_ii, then b_r -= x_i * a_ri for the rows above (not the row-oriented dot-product form)
+    // x_i = b_i / a_ii, then b_r -= x_i * a_ri for the rows above (not the row-oriented dot-product form); an entry that is exactly zero is
+    // left alone (TriangularSolverVector.h:117, `if (rhs[i] != 0)`): no division, so the zero keeps its sign, and no update of the rows above
     float xs[C] = {0.f, 0.f, 0.f};
     for (int i = nonzero - 1; i >= 0; i--) {
-        xs[i] = b[i] / A[i][i];
-        for (int r = 0; r < i; r++) b[r] = b[r] - xs[i] * A[r][i];
+        xs[i] = b[i];
+        if (b[i] != 0.f) {
+            xs[i] = b[i] / A[i][i];
+            for (int r = 0; r < i; r++) b[r] = b[r] - xs[i] * A[r][i];
+        }
     }
     float nv[C] = {0.f, 0.f, 0.f};
     for (int i = 0; i < nonzero; i++) nv[perm[i]] = xs[i];
