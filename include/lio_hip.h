@@ -73,8 +73,10 @@ int lio_device_count(void);
  *      one detect() call over a fragment of new key frames).
  * 17 = lio_gicp_neighbours / lio_gicp_mahalanobis (test visibility: the neighbour list behind every covariance, the Mahalanobis matrices of the
  *      current pairs).  lio_gicp_set_target / _set_source now refuse points that are not finite, lio_gicp_linearize / _align a pose that is not
- *      finite or a max_corr_dist that is negative or NaN (LIO_E_INVALID, nothing launched, the object as it was). */
-#define LIO_ABI_VERSION 17
+ *      finite or a max_corr_dist that is negative or NaN (LIO_E_INVALID, nothing launched, the object as it was).
+ * 18 = lio_sc_* (the Scan Context bank of the relocalisation: descriptors of many clouds in one set of launches, the ring-key search, the
+ *      column-shift distance, globalSearch) and lio_gicp_fitness_score (getFitnessScore of the handle's own pair). */
+#define LIO_ABI_VERSION 18
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -694,6 +696,11 @@ int lio_gicp_mahalanobis(lio_gicp*, double* maha6, uint32_t cap);
 int lio_gicp_linearize(lio_gicp*, const double T[16], double max_corr_dist, int update_corr, int with_derivatives, double H[36], double b[6], double* err,
                        uint32_t* n_corr);
 int lio_gicp_align(lio_gicp*, const double guess[16], const lio_ndt_params* params, double max_corr_dist, double out[16], int* iterations, int* converged);
+/* pcl::Registration::getFitnessScore(max_range) of the handle's pair under T (the loop section's "fitness" rule: the source moved by T cast to
+ * f32, the exact nearest target point by the f32 d2, the bound applied to the SQUARED distance, f64 sum / count; DBL_MAX when nr = 0).  The
+ * sum runs over the source in the order lio_gicp_set_source was given it, by the loop detector's kernel: for a pair that is also in a lio_loop
+ * bank, score and nr are lio_loop_align_candidates'.  nr may be NULL */
+int lio_gicp_fitness_score(lio_gicp*, const double T[16], double max_range, double* score, uint32_t* nr);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The localisation loop around the matcher: hdl_localization::PoseEstimator (slam/localization/hdl_localization/src/
@@ -1304,6 +1311,75 @@ int lio_overlap_last_report(lio_overlap*, uint32_t k, lio_overlap_report* report
                             double* scores, uint32_t cap);
 /* stage times of the last detect (summed over its frames), or of the last stage-door call for its own stage */
 int lio_overlap_last_times(lio_overlap*, lio_overlap_times*);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * The Scan Context bank (csrc/scancontext.hip): SCManager of the relocalisation (slam/common/Scancontext/Scancontext.cpp, "SC") with the
+ * descriptors of the map's key frames resident in HBM, KeyFrame::computeDescriptor (slam/localization/src/keyframe.cpp:163-168) for many
+ * frames in one set of launches, and GlobalLocalization::globalSearch (slam/localization/src/global_localization.cpp:387-413).  A descriptor
+ * is 20 rings x 60 sectors of f64, row-major (ring, sector).  THE RULES, restated in numpy by tests/sc_cases.py:
+ *   points      a point with a coordinate that is not finite is dropped and counted (lio_sc_last_dropped); the intensity is not read
+ *   shift       x' = f32(f64(x) + dx), y' = f32(f64(y) + dy), z' = f32(f64(z) + 0.5) (SC:172-174, LIDAR_HEIGHT)
+ *   ring        range = sqrtf(x'*x' + y'*y') in f32; the point is dropped when f64(range) > 80; ring = clamp(ceil(f64(range) / 80 * 20), 1, 20)
+ *   sector      theta follows xy2theta's four branches (SC:21-36) with the quotient y'/x' (or its mirrored forms) in f32 as the reference
+ *               forms it; the arctangent of that quotient is taken in F64, scaled by 180 / pi in f64, combined with the branch's 180 or 360 in
+ *               f64 and rounded ONCE to f32; sector = clamp(ceil(f64(theta) / 360 * 60), 1, 60), and a theta that is not a number (the origin's
+ *               0 / 0) goes to sector 1.  DEVIATION: the reference calls atanf, whose last bit differs between libraries; this rule moves a
+ *               point only when it lies within an f32 ulp of a sector edge, and makes the device, numpy and glibc agree
+ *   bins        a bin starts at -1000 and takes z' when bin < z'; bins still at -1000 become 0 (SC:164-196).  The result is a maximum: it
+ *               depends neither on the order of the points nor on how the device cuts a cloud into slices
+ *   keys        ring key r = f32((sum over the 60 columns, in column order, in f64) / 60); sector key c = (sum over the 20 rows, in row order) /
+ *               20 in f64; column norm c = sqrt(sum of squares in row order).  (Eigen adds in another order: a few ulp.)
+ *   ring-key distance   f32, nanoflann's L2_Adaptor::evalMetric (Scancontext/nanoflann.hpp:383-408): five groups of four,
+ *               result += ((d0*d0 + d1*d1) + d2*d2) + d3*d3 with d = query - frame.  The min(10, active frames) smallest are the candidates, in
+ *               rising distance; equal distances go to the smaller id
+ *   distance    distanceBtnScanContext (SC:124-156).  fastAlignUsingVkey: for shift s = 0..59 the norm sqrt(sum over j, in column order, of
+ *               (key1[j] - key2[(j - s) mod 60])^2); the smallest by strict < from 10000000, the first shift wins.  The search radius is
+ *               round(0.5 * 0.1 * 60) = 3: the shift and its three neighbours on either side mod 60, tried in RISING order of the shift, strict <
+ *               from 10000000.  distDirectSC under shift s compares column j of the first with column (j - s) mod 60 of the second: a pair with a
+ *               zero norm on either side is skipped, otherwise cos = (dot in row order) / (norm1 * norm2); the result is 1 - (sum of cos in
+ *               column order) / count; a count of 0 gives NaN, which wins no <: two descriptors without a common column give {10000000, 0}
+ *   yaw         f32(f64(f32(shift * 6.0)) * pi / 180) (SC:322, lio_sc_shift_to_yaw)
+ *   search      detectClosestMatch (SC:262-326) scores the candidates in rising ring-key distance and keeps the first of equal scores; its id
+ *               is -1 when the score is not below dist_thres; an empty search set gives {-1, yaw 0, score 1}.  globalSearch describes the cloud
+ *               under the nine shifts {0,0} {-4,0} {4,0} {0,-4} {0,4} {-4,-4} {-4,4} {4,-4} {4,4}, in that order, and keeps the best by strict <
+ * NULL from lio_sc_create without a device: there is no CPU path.  No floating-point atomics; no workgroup waits for another. */
+#define LIO_SC_RINGS 20
+#define LIO_SC_SECTORS 60
+#define LIO_SC_CANDIDATES 10
+#define LIO_SC_MAX_SHIFTS 9
+typedef struct lio_sc lio_sc;
+/* a bank of at most max_frames descriptors; a call stages at most max_points_per_call points (the largest frame, the largest query cloud) */
+lio_sc* lio_sc_create(int device, uint32_t max_frames, uint32_t max_points_per_call);
+void lio_sc_destroy(lio_sc*);
+int lio_sc_reset(lio_sc*);      /* an empty bank, every later frame active */
+int lio_sc_num_frames(lio_sc*);
+/* the map load: frame k is points [offsets[k], offsets[k + 1]) of xyzi (n x 4 f32), described under the shift (0, 0); as many whole frames as
+ * fit max_points_per_call go into one set of launches.  The id of the first frame (ids rise by one); LIO_E_CAPACITY beyond max_frames or for
+ * a frame larger than max_points_per_call, with the bank as it was */
+int lio_sc_add_frames_host(lio_sc*, const float* xyzi, const uint64_t* offsets, uint32_t n_frames);
+/* a frame's descriptor (1200 f64), ring key (20 f32) and sector key (60 f64); any may be NULL */
+int lio_sc_download_frame(lio_sc*, int id, double* desc, float* ringkey, double* sectorkey);
+/* stage door: makeScancontext(cloud, dx, dy) of one cloud under n_shifts (1..9) shifts (dx, dy pairs) in one set of launches; per shift the
+ * descriptor, ring key and sector key (any may be NULL) */
+int lio_sc_describe_host(lio_sc*, const float* xyzi, uint32_t n, const double* shifts_xy, uint32_t n_shifts, double* desc, float* ringkey, double* sectorkey);
+/* the frames a search looks at (mSearchIdxMap of setInitPoseRange, the range filter applied by the caller): n distinct ids; n = 0 is the empty
+ * set; n < 0 is every frame of the bank, later ones included (the state after create and reset) */
+int lio_sc_set_active(lio_sc*, const int32_t* ids, int32_t n);
+/* stage door: distanceBtnScanContext(desc_a[k], desc_b[k]) for n_pairs pairs of descriptors (1200 f64 each) */
+int lio_sc_distance(lio_sc*, const double* desc_a, const double* desc_b, uint32_t n_pairs, double* dist, int32_t* shift);
+/* per query (descriptor and ring key) the candidates among the active frames in rising ring-key distance, with the distance and shift of each:
+ * detectCandidateMatch (SC:328-361) without its threshold.  10 entries per query; places past n_cand[q] = min(10, active) hold id -1, NaN, -1.
+ * Any output may be NULL */
+int lio_sc_search(lio_sc*, const double* desc, const float* ringkey, uint32_t n_queries, int32_t* cand_ids, double* cand_dist, int32_t* cand_shift, int32_t* n_cand);
+/* globalSearch of a cloud: the matched frame's id (-1: the best score is not below dist_thres; 0.30 with point clouds alone), the yaw, the
+ * score and the column shift behind the yaw (any may be NULL) */
+int lio_sc_global_search_host(lio_sc*, const float* xyzi, uint32_t n, double dist_thres, int32_t* match_id, float* yaw, double* score, int32_t* shift);
+/* host only: the yaw of a column shift */
+float lio_sc_shift_to_yaw(int32_t shift);
+/* points the last add_frames / describe / global_search call dropped because a coordinate was not finite */
+int lio_sc_last_dropped(lio_sc*, uint64_t* n_nonfinite);
+/* device time (HIP events) of the last call's stages in us: upload + describe, ring-key search, distances (any may be NULL) */
+int lio_sc_last_times(lio_sc*, double* describe_us, double* ringkey_us, double* distance_us);
 
 /* -------------------------------------------------------------------------------------------------------------
  * The pose graph on the device (csrc/graph.hip): what hdl_graph_slam's GraphSLAM does with g2o for SE3 pose nodes and EdgeSE3 edges

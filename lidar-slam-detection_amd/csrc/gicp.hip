@@ -551,12 +551,18 @@ int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
     lio_map* m = g->grid[which];
     hipStream_t st = m->stream;
     LIO_HIP_TRY(hipMemcpyAsync(g->stage, xyzi, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, st));
+    if (which == 1) {  // the grid lays the cloud out cell by cell: lio_gicp_fitness_score adds in the caller's order
+        g->src_order = 0;
+        if (!g->src_rows) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->src_rows), (size_t)g->max_points * sizeof(float4)));
+        LIO_HIP_TRY(hipMemcpyAsync(g->src_rows, g->stage, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    }
     int rc = lio_map_insert_device(m, g->stage, n, 0.0);
     if (rc != LIO_OK) return rc;
     g->n[which] = n;
     g->rows[which] = false;
     g->gridded[which] = true;
-    if (which == 0) g->vmap_valid = false;
+    if (which == 0) { g->vmap_valid = false; g->fit_valid = false; }
+    else g->src_order = 1;
     hipLaunchKernelGGL(gicp_cov_kernel<false>, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which],
                        (int32_t*)nullptr);
     LIO_HIP_TRY(hipGetLastError());
@@ -634,7 +640,8 @@ int gicp_cloud_covariances(lio_gicp* g, int which, const float4* d_pts, uint32_t
     g->n[which] = n;
     g->rows[which] = true;
     g->gridded[which] = true;
-    if (which == 0) g->vmap_valid = false;
+    if (which == 0) { g->vmap_valid = false; g->fit_valid = false; }
+    else g->src_order = 0;
     hipLaunchKernelGGL(gicp_cov_kernel<false>, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which],
                        (int32_t*)nullptr);
     hipLaunchKernelGGL(gicp_scatter_cov_kernel, (n + 255) / 256, 256, 0, st, m->pool, n, g->cov[which], d_cov6_rows);
@@ -660,6 +667,7 @@ int gicp_adopt_cloud(lio_gicp* g, int which, const float4* d_pts, const double* 
         g->n[1] = n;
         g->rows[1] = false;
         g->gridded[1] = false;
+        g->src_order = 2;
         LIO_HIP_TRY(hipStreamSynchronize(st));
         return LIO_OK;
     }
@@ -671,6 +679,7 @@ int gicp_adopt_cloud(lio_gicp* g, int which, const float4* d_pts, const double* 
     g->rows[0] = true;
     g->gridded[0] = true;
     g->vmap_valid = false;
+    g->fit_valid = false;
     hipLaunchKernelGGL(gicp_gather_cov_kernel, (n + 255) / 256, 256, 0, st, m->pool, n, d_cov6, g->cov[0]);
     LIO_HIP_TRY(hipGetLastError());
     LIO_HIP_TRY(hipStreamSynchronize(st));
@@ -788,6 +797,8 @@ void lio_gicp_destroy(lio_gicp* g) {
     if (g->maha) hipFree(g->maha);
     if (g->partial) hipFree(g->partial);
     if (g->stage) hipFree(g->stage);
+    if (g->src_rows) hipFree(g->src_rows);
+    gicp_fit_free(g);
     if (g->report) hipHostFree(g->report);
     delete g;
 }

@@ -103,6 +103,12 @@ struct lio_gicp {
     double* vmaha = nullptr;
     double* vpartial = nullptr;
     uint32_t vblocks = 0;
+    // lio_gicp_fitness_score (loop.hip): the source as the caller ordered it -- the fitness sum runs in that order -- and the exact index over
+    // the target with the launch's scratch, both made when first needed
+    float4* src_rows = nullptr;
+    int src_order = 0;       // 0: not kept; 1: src_rows; 2: the source grid's pool is the caller's order (an adopted source)
+    void* fit = nullptr;     // loop.hip's GicpFit
+    bool fit_valid = false;  // the index is over the current target
 };
 
 namespace lio {
@@ -119,4 +125,6 @@ int gicp_cloud_covariances(lio_gicp* g, int which, const float4* d_pts, uint32_t
 int gicp_adopt_cloud(lio_gicp* g, int which, const float4* d_pts, const double* d_cov6, uint32_t n);
 // create_voxelmap of the current target
 int vgicp_build(lio_gicp* g);
+// frees g->fit (loop.hip)
+void gicp_fit_free(lio_gicp* g);
 }  // namespace lio

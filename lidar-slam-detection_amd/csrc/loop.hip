@@ -550,6 +550,28 @@ namespace lio {
 namespace loop {
 int loop_reserve(lio_loop* h, uint64_t pts, uint64_t tab) { return reserve(h, pts, tab); }
 int loop_prepare_target(lio_loop* h, int id) { return prepare_target(h, id); }
+
+// what lio_gicp_fitness_score keeps on a matcher handle: the exact index over its target and the scratch of one fitness launch
+struct GicpFit {
+    knn_index::DeviceIndex index;
+    FitSlot *d_fit = nullptr, *h_fit = nullptr;
+    uint2 *d_tab = nullptr, *h_tab = nullptr;
+    double *d_p = nullptr, *h_p = nullptr;
+};
+}  // namespace loop
+void gicp_fit_free(lio_gicp* g) {
+    loop::GicpFit* f = static_cast<loop::GicpFit*>(g->fit);
+    if (!f) return;
+    knn_index::device_index_free(f->index);
+    hipFree(f->d_fit); hipFree(f->d_tab); hipFree(f->d_p);
+    if (f->h_fit) hipHostFree(f->h_fit);
+    if (f->h_tab) hipHostFree(f->h_tab);
+    if (f->h_p) hipHostFree(f->h_p);
+    delete f;
+    g->fit = nullptr;
+    g->fit_valid = false;
+}
+namespace loop {
 int loop_fitness_batch(lio_loop* h, const int32_t* src_ids, const double* T16, uint32_t n, double* score, uint32_t* nr, double max_range) {
     return fitness_batch(h, src_ids, T16, n, score, nr, max_range);
 }
@@ -601,6 +623,55 @@ int lio_loop_find_candidates(const double* accum, const double* pos_xy, uint32_t
         count++;
     }
     return (count > cap || (count && !out_idx)) ? -(int)count : (int)count;
+}
+
+// getFitnessScore(max_range) of the matcher's own pair: loop_fitness over the source in the caller's order against an exact index over the
+// target, the records added as fitness_batch adds them -- for a pair of bank frames the loop detector's numbers
+int lio_gicp_fitness_score(lio_gicp* g, const double T[16], double max_range, double* score, uint32_t* nr) {
+    if (!g || !T || !score || !(max_range >= 0)) return LIO_E_INVALID;
+    for (int k = 0; k < 12; k++)
+        if (!(T[k] - T[k] == 0.0)) { set_error("lio_gicp_fitness_score: the transform is not finite"); return LIO_E_INVALID; }
+    if (!g->grid[0] || !g->grid[1] || g->n[0] == 0 || g->n[1] == 0) { set_error("lio_gicp_fitness_score: set target and source first"); return LIO_E_STATE; }
+    if (g->src_order == 0) { set_error("lio_gicp_fitness_score: the source's own order was not kept (set it with lio_gicp_set_source)"); return LIO_E_STATE; }
+    hipSetDevice(g->device);
+    hipStream_t st = g->grid[0]->stream;
+    GicpFit* f = static_cast<GicpFit*>(g->fit);
+    const uint32_t max_blocks = (g->max_points + kFitThreads - 1) / kFitThreads;
+    if (!f) {
+        f = new GicpFit();
+        g->fit = f;
+        const bool ok = hipMalloc(reinterpret_cast<void**>(&f->d_fit), sizeof(FitSlot)) == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&f->h_fit), sizeof(FitSlot), hipHostMallocDefault) == hipSuccess &&
+                        hipMalloc(reinterpret_cast<void**>(&f->d_tab), sizeof(uint2) * max_blocks) == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&f->h_tab), sizeof(uint2) * max_blocks, hipHostMallocDefault) == hipSuccess &&
+                        hipMalloc(reinterpret_cast<void**>(&f->d_p), sizeof(double) * 2 * max_blocks) == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(&f->h_p), sizeof(double) * 2 * max_blocks, hipHostMallocDefault) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); gicp_fit_free(g); set_error("lio_gicp_fitness_score: allocation failed"); return LIO_E_DEVICE; }
+    }
+    const uint32_t nt = g->n[0], ns = g->n[1];
+    if (!g->fit_valid) {
+        int rc = knn_index::device_index_reserve(f->index, g->max_points);
+        if (rc != LIO_OK) return rc;
+        hipLaunchKernelGGL(loop_stamp, (nt + 255) / 256, 256, 0, st, g->grid[0]->pool, nt, g->stage);  // the index copies what it is given
+        LIO_HIP_TRY(hipGetLastError());
+        rc = knn_index::device_index_build(st, f->index, g->stage, nullptr, nt);
+        if (rc != LIO_OK) return rc;
+        g->fit_valid = true;
+    }
+    FitSlot& fs = *f->h_fit;
+    fs.src = g->src_order == 1 ? g->src_rows : g->grid[1]->pool;
+    fs.n = ns; fs.pad = 0;
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) fs.R[r * 3 + c] = (float)T[r * 4 + c]; fs.t[r] = (float)T[r * 4 + 3]; }
+    uint32_t b = 0;
+    for (uint32_t p0 = 0; p0 < ns; p0 += kFitThreads) f->h_tab[b++] = make_uint2(0, p0);
+    LIO_HIP_TRY(hipMemcpyAsync(f->d_fit, f->h_fit, sizeof(FitSlot), hipMemcpyHostToDevice, st));
+    LIO_HIP_TRY(hipMemcpyAsync(f->d_tab, f->h_tab, sizeof(uint2) * b, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(loop_fitness, b, kFitThreads, 0, st, f->d_tab, f->d_fit, f->index.leaves, f->index.nodes, nt, f->index.P, f->index.L, max_range, f->d_p);
+    LIO_HIP_TRY(hipGetLastError());
+    LIO_HIP_TRY(hipMemcpyAsync(f->h_p, f->d_p, sizeof(double) * 2 * b, hipMemcpyDeviceToHost, st));
+    LIO_HIP_TRY(hipStreamSynchronize(st));
+    double sum = 0.0, cnt = 0.0;
+    for (uint32_t k = 0; k < b; k++) { sum += f->h_p[2 * k]; cnt += f->h_p[2 * k + 1]; }
+    *score = cnt > 0 ? sum / cnt : DBL_MAX;
+    if (nr) *nr = (uint32_t)cnt;
+    return LIO_OK;
 }
 
 int lio_loop_information_matrix(double fitness_score, double out36[36]) {

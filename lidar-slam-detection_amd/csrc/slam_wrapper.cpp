@@ -152,7 +152,17 @@ struct Loc {
     std::map<int, int> bank_of_kf;
     uint32_t bank_max_points = 0, ndt_biggest = 0;
     struct MergeReport { std::vector<std::array<int, 2>> overlaps; std::vector<double> scores; std::vector<int> reasons, new_ids; int fragments = 0, skipped_tags = 0; } merge_report;
+    // global relocalisation (GlobalLocalization::globalSearch + registrationAlign, global_localization.cpp:387-413, 456-482): off unless
+    // set_global_localization(true) / LSD_AMD_RELOC=1.  The bank holds the descriptors of the key frames' local clouds, frame k = key frame k
+    bool reloc = false;
+    lio_sc* sc = nullptr;
+    lio_gicp* reloc_gicp = nullptr;
+    std::vector<float> reloc_ds;
+    struct Reloc { bool searched = false, accepted = false; int match_id = -1, converged = 0; double score = 0, fitness = 0, dx = 0, da = 0; float yaw = 0; } last_reloc;
+    int reloc_searches = 0;  // searches run since init_slam
     ~Loc() {
+        if (reloc_gicp) lio_gicp_destroy(reloc_gicp);
+        if (sc) lio_sc_destroy(sc);
         if (moverlap) lio_overlap_destroy(moverlap);
         if (mbank) lio_loop_destroy(mbank);
         if (pe) lio_pose_estimator_destroy(pe);
@@ -349,7 +359,102 @@ bool load_keyframes(const std::string& map_path, std::vector<KeyFrameDisk>& out)
     return !out.empty();
 }
 
-// Localization::init (localization.cpp:91-131) without the graph back end and the global locator: the key frames of the map go to HBM once
+// GlobalLocalization::feedInitData -> KeyFrame::computeDescriptor for every key frame (keyframe.cpp:163-168), PoseRange(+-10000): the descriptors
+// of the key frames' local clouds into a bank on the device, 64 frames a call; every frame is searched
+bool loc_fill_sc(Loc& L) {
+    if (L.sc) { lio_sc_destroy(L.sc); L.sc = nullptr; }
+    uint32_t biggest = 0;
+    for (const KeyFrameDisk& kf : L.frames) biggest = std::max<uint32_t>(biggest, (uint32_t)(kf.local.size() / 4));
+    L.sc = lio_sc_create(0, (uint32_t)L.frames.size(), std::max<uint32_t>(biggest, 1u << 20));
+    if (!L.sc) return false;
+    std::vector<float> buf;
+    std::vector<uint64_t> off;
+    for (size_t k0 = 0; k0 < L.frames.size(); k0 += 64) {
+        const size_t k1 = std::min(L.frames.size(), k0 + 64);
+        buf.clear();
+        off.assign(1, 0);
+        for (size_t k = k0; k < k1; k++) {
+            buf.insert(buf.end(), L.frames[k].local.begin(), L.frames[k].local.end());
+            off.push_back(buf.size() / 4);
+        }
+        if (lio_sc_add_frames_host(L.sc, buf.data(), off.data(), (uint32_t)(k1 - k0)) != (int)k0) return false;
+    }
+    return true;
+}
+
+// yaw2matrix (Scancontext.cpp:68-75): cos / sin of the f32 angle
+Mat4 yaw_matrix_f32(float y) {
+    Mat4 m = Mat4::identity();
+    m(0, 0) = (double)std::cos(y); m(0, 1) = (double)-std::sin(y);
+    m(1, 0) = (double)std::sin(y); m(1, 1) = (double)std::cos(y);
+    return m;
+}
+
+// GlobalLocalization::globalSearch + registrationAlign with the cloud in L.staged: true when an initial pose was accepted into L.init_pose.
+// DEVIATION: synchronous, on every uninitialised frame (the reference's search thread drops the frames that arrive while it is busy and
+// registers the next one against the frame it searched with); localSearch (INS-aided) and the image search are not built
+bool loc_relocalize(Loc& L, uint32_t n) {
+    Loc::Reloc& r = L.last_reloc;
+    r = Loc::Reloc();
+    if (!L.sc || n == 0) return false;
+    // GlobalLocalization::downsample: the VoxelGrid of the localizer's resolution
+    if (lio_scan_upload(L.scan, L.staged.data(), n) != LIO_OK) return false;
+    uint32_t n_ds = n;
+    if (L.resolution >= 0.1) {
+        if (lio_scan_voxel_downsample(L.scan, (float)L.resolution, 1, &n_ds) != LIO_OK) return false;
+        L.reloc_ds.resize(4 * (size_t)n_ds);
+        if (n_ds && lio_scan_download_ds(L.scan, L.reloc_ds.data(), n_ds) < 0) return false;
+    } else {
+        L.reloc_ds.assign(L.staged.begin(), L.staged.begin() + 4 * (size_t)n);
+    }
+    r.searched = true;
+    L.reloc_searches++;
+    int32_t id = -1;
+    if (lio_sc_global_search_host(L.sc, L.reloc_ds.data(), n_ds, 0.30, &id, &r.yaw, &r.score, nullptr) != LIO_OK) return false;
+    r.match_id = id;
+    if (id < 0 || (size_t)id >= L.frames.size()) return false;
+    // select_registration_method("FAST_VGICP"): the loop detector's coarse configuration
+    lio_loop_params lp;
+    lio_loop_default_params(&lp);
+    const KeyFrameDisk& kf = L.frames[id];
+    const uint32_t nt = (uint32_t)(kf.local.size() / 4);
+    if ((int)nt < lp.k_correspondences || (int)n_ds < lp.k_correspondences) return false;
+    if (!L.reloc_gicp) {
+        uint32_t biggest = 1u << 18;
+        for (const KeyFrameDisk& f : L.frames) biggest = std::max<uint32_t>(biggest, (uint32_t)(f.local.size() / 4));
+        L.reloc_gicp = lio_gicp_create(0, lp.grid_resolution, biggest, lp.k_correspondences);
+        if (!L.reloc_gicp || lio_gicp_set_voxel_mode(L.reloc_gicp, lp.voxel_resolution, 1) != LIO_OK) return false;
+    }
+    if (lio_gicp_set_target(L.reloc_gicp, kf.local.data(), nt) != LIO_OK || lio_gicp_set_source(L.reloc_gicp, L.reloc_ds.data(), n_ds) != LIO_OK) return false;
+    const Mat4 guess = yaw_matrix_f32(-r.yaw);
+    lio_ndt_params p;
+    lio_ndt_default_params(&p);
+    p.rotation_epsilon_deg = lp.coarse_rotation_epsilon_deg;
+    p.transformation_epsilon = lp.coarse_translation_epsilon;
+    p.max_iterations = lp.max_iterations;
+    p.max_process_time_ms = -1;
+    double T[16];
+    int it = 0, conv = 0;
+    if (lio_gicp_align(L.reloc_gicp, guess.m, &p, 1.0, T, &it, &conv) != LIO_OK) return false;
+    r.converged = conv;
+    if (!conv) return false;
+    if (lio_gicp_fitness_score(L.reloc_gicp, T, lp.fitness_score_max_range, &r.fitness, nullptr) != LIO_OK) return false;
+    // :468-473: delta = getFinalTransformation() (f32), deltadelta = guess^-1 * delta, its translation norm and rotation angle
+    Mat4 delta;
+    for (int i = 0; i < 16; i++) delta.m[i] = (double)(float)T[i];
+    delta(3, 0) = delta(3, 1) = delta(3, 2) = 0.0; delta(3, 3) = 1.0;
+    const Mat4 dd = mul(rigid_inverse(guess), delta);
+    r.dx = std::sqrt(dd(0, 3) * dd(0, 3) + dd(1, 3) * dd(1, 3) + dd(2, 3) * dd(2, 3));
+    const double c = std::max(-1.0, std::min(1.0, (dd(0, 0) + dd(1, 1) + dd(2, 2) - 1.0) * 0.5));
+    r.da = std::acos(c) / M_PI * 180.0;
+    if (!(r.fitness < 1.5 && r.dx < 10.0 && r.da < 30.0)) return false;
+    L.init_pose = mul(kf.odom, delta);
+    L.have_init_pose = true;
+    r.accepted = true;
+    return true;
+}
+
+// Localization::init (localization.cpp:91-131) without the graph back end: the key frames of the map go to HBM once
 bool loc_setup(Slam* s) {
     Loc& L = *s->loc;
     if (L.frames.empty()) return false;  // "Map Loader: error to load map" (setup_slam read the key frames from disk)
@@ -367,6 +472,7 @@ bool loc_setup(Slam* s) {
         const float pos[3] = {(float)kf.odom(0, 3), (float)kf.odom(1, 3), (float)kf.odom(2, 3)};
         if (lio_localmap_add_keyframe(L.lm, kf.xyzi.data(), (uint32_t)(kf.xyzi.size() / 4), pos) < 0) return false;
     }
+    if (L.reloc && !loc_fill_sc(L)) return false;
     return true;
 }
 
@@ -416,7 +522,8 @@ bool loc_timed_pose(Loc& L, uint64_t stamp, Mat4& out) {
 bool loc_localize(Slam* s, uint32_t n, uint64_t stamp, Mat4& pose_out) {
     Loc& L = *s->loc;
     if (!L.initialized) {
-        if (!L.have_init_pose) return false;  // (the global locator -- GNSS / scan-context initial pose -- is out of scope: set_init_pose starts the filter)
+        // no pose from set_init_pose: the global locator (scan context + FAST_VGICP) looks for one when it is switched on
+        if (!L.have_init_pose && !(L.reloc && loc_relocalize(L, n))) return false;
         // Localization::initLocalizer -> initialpose_callback (hdl_localization_nodelet.cpp:304-317): normalised quaternion of the pose, cool time 0.2 s
         float ext[16];
         for (int i = 0; i < 16; i++) ext[i] = (float)s->T_imu.m[i];
@@ -586,6 +693,8 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
     for (auto h : sensor_input) in.push_back(py::cast<std::string>(h));
     if (localization) {
         g->loc.reset(new Loc());
+        const char* reloc_env = std::getenv("LSD_AMD_RELOC");
+        g->loc->reloc = reloc_env && reloc_env[0] == '1';
         g->loc->resolution = resolution;
         g->loc->key_frame_distance = dist_threshold;
         // Localization::setSensors (localization.cpp:154-182): RTK / IMU as they come, the first "n-" name is the lidar, the first other one the camera
@@ -1154,6 +1263,33 @@ void set_loop_detection(bool enable) {
     std::lock_guard<std::mutex> kl(g->kf_mtx);
     g->loop_detection = enable;
     if (enable) g->keyframe_output = true;
+}
+// not in the reference's module (whose global locator always runs): global relocalisation in localisation mode, off by default; LSD_AMD_RELOC=1 at
+// init_slam switches it on for an unchanged slam.py.  Switched on after setup_slam, the descriptor bank is filled here
+void set_global_localization(bool enable) {
+    require((bool)g && (bool)g->loc, "init_slam in localisation mode first");
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> lk(g->mtx);
+    g->loc->reloc = enable;
+    if (enable && !g->loc->sc && g->loc->scan) require(loc_fill_sc(*g->loc), "the scan-context bank could not be filled");
+}
+// test visibility: what the last search of the global locator found and why it was (not) accepted
+py::dict _last_relocalization() {
+    py::dict d;
+    if (!g || !g->loc) return d;
+    std::lock_guard<std::mutex> lk(g->mtx);
+    const auto& r = g->loc->last_reloc;
+    d["searched"] = r.searched;
+    d["match_id"] = r.match_id;
+    d["score"] = r.score;
+    d["yaw"] = r.yaw;
+    d["converged"] = (bool)r.converged;
+    d["fitness"] = r.fitness;
+    d["dx"] = r.dx;
+    d["da"] = r.da;
+    d["accepted"] = r.accepted;
+    d["searches"] = g->loc->reloc_searches;
+    return d;
 }
 // not in the reference's module: the pose graph over the key frames and the loops (off by default; LSD_AMD_GRAPH=1 at init_slam switches it on for
 // an unchanged slam.py).  It consumes the loops and the key frames, so it switches both on too.
@@ -2553,6 +2689,8 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("save_render_cloud", &save_render_cloud, "save render cloud", py::arg("file"));
     m.def("set_keyframe_output", &set_keyframe_output, "key frames from process() through update_odom()", py::arg("enable"));
     m.def("set_loop_detection", &set_loop_detection, "loop detection over the key frames update_odom() hands out", py::arg("enable"));
+    m.def("set_global_localization", &set_global_localization, "scan-context relocalisation in localisation mode", py::arg("enable"));
+    m.def("_last_relocalization", &_last_relocalization);
     m.def("set_pose_graph", &set_pose_graph, "the pose graph over the key frames and the loops", py::arg("enable"));
     m.def("_push_keyframe", &_push_keyframe, "test hook: a key frame for the next update_odom()", py::arg("points"), py::arg("pose"), py::arg("stamp"), py::arg("accum_distance"));
     m.def("set_loop_config", &set_loop_config, "LoopDetector thresholds", py::arg("dict"));

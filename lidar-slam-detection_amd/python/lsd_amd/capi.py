@@ -54,13 +54,15 @@ SYMBOLS = [
     "lio_state_predict", "lio_eskf_update_cb", "lio_eskf_update_ws_cb", "lio_eskf_update_sums_cb",
     "lio_ndt_create", "lio_ndt_destroy", "lio_ndt_set_target", "lio_ndt_set_target_device", "lio_ndt_num_voxels", "lio_ndt_fitness_score", "lio_ndt_overlap_score", "lio_ndt_voxel_at",
     "lio_ndt_linearize", "lio_ndt_default_params", "lio_ndt_align", "lio_ndt_align_batch", "lio_ndt_enable_kernel_timing", "lio_ndt_kernel_times",
-    "lio_gicp_create", "lio_gicp_destroy", "lio_gicp_set_target", "lio_gicp_set_source", "lio_gicp_set_voxel_mode", "lio_gicp_voxel_at", "lio_gicp_download", "lio_gicp_correspondences", "lio_gicp_neighbours", "lio_gicp_mahalanobis", "lio_gicp_linearize", "lio_gicp_align",
+    "lio_gicp_create", "lio_gicp_destroy", "lio_gicp_set_target", "lio_gicp_set_source", "lio_gicp_set_voxel_mode", "lio_gicp_voxel_at", "lio_gicp_download", "lio_gicp_correspondences", "lio_gicp_neighbours", "lio_gicp_mahalanobis", "lio_gicp_linearize", "lio_gicp_align", "lio_gicp_fitness_score",
     "lio_loop_default_params", "lio_loop_find_candidates", "lio_loop_information_matrix", "lio_loop_create", "lio_loop_destroy", "lio_loop_reset",
     "lio_loop_add_keyframe_host", "lio_loop_set_pose", "lio_loop_num_keyframes", "lio_loop_download_keyframe", "lio_loop_detect", "lio_loop_edges",
     "lio_loop_last_report", "lio_loop_last_times", "lio_loop_align_candidates", "lio_loop_align_fine", "lio_loop_pair_information",
     "lio_overlap_default_params", "lio_overlap_connection_count", "lio_overlap_find_candidates", "lio_overlap_create", "lio_overlap_destroy",
     "lio_overlap_gate_batch", "lio_overlap_align_pairs", "lio_overlap_accumulate", "lio_overlap_download_accum", "lio_overlap_detect",
     "lio_overlap_last_report", "lio_overlap_last_times",
+    "lio_sc_create", "lio_sc_destroy", "lio_sc_reset", "lio_sc_num_frames", "lio_sc_add_frames_host", "lio_sc_download_frame", "lio_sc_describe_host", "lio_sc_set_active",
+    "lio_sc_distance", "lio_sc_search", "lio_sc_global_search_host", "lio_sc_shift_to_yaw", "lio_sc_last_dropped", "lio_sc_last_times",
     "lio_graph_default_params", "lio_graph_create", "lio_graph_destroy", "lio_graph_reset", "lio_graph_add_node", "lio_graph_set_fixed", "lio_graph_set_estimate",
     "lio_graph_num_nodes", "lio_graph_get_fixed", "lio_graph_add_edge", "lio_graph_remove_edge", "lio_graph_optimize", "lio_graph_estimates", "lio_graph_edges",
     "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
@@ -453,6 +455,7 @@ def lib():
     sig("lio_gicp_mahalanobis", cint, vp, f64p, u32)
     sig("lio_gicp_linearize", cint, vp, f64p, dbl, cint, cint, f64p, f64p, f64p, C.POINTER(u32))
     sig("lio_gicp_align", cint, vp, f64p, C.POINTER(NdtParams), dbl, f64p, C.POINTER(cint), C.POINTER(cint))
+    sig("lio_gicp_fitness_score", cint, vp, f64p, dbl, f64p, C.POINTER(u32))
     lp, le, lr = C.POINTER(LoopParams), C.POINTER(LoopEdge), C.POINTER(LoopReport)
     sig("lio_loop_default_params", None, lp)
     sig("lio_loop_find_candidates", cint, f64p, f64p, u32, dbl, f64p, dbl, lp, i32p, u32)
@@ -484,6 +487,20 @@ def lib():
     sig("lio_overlap_detect", cint, vp, i32p, i32p, u32, i32p, i32p, u32, i32p, i32p, u32, oe, u32)
     sig("lio_overlap_last_report", cint, vp, u32, C.POINTER(OverlapReport), i32p, f64p, i32p, i32p, f64p, u32)
     sig("lio_overlap_last_times", cint, vp, C.POINTER(OverlapTimes))
+    sig("lio_sc_create", vp, cint, u32, u32)
+    sig("lio_sc_destroy", None, vp)
+    sig("lio_sc_reset", cint, vp)
+    sig("lio_sc_num_frames", cint, vp)
+    sig("lio_sc_add_frames_host", cint, vp, f32p, C.POINTER(u64), u32)
+    sig("lio_sc_download_frame", cint, vp, cint, f64p, f32p, f64p)
+    sig("lio_sc_describe_host", cint, vp, f32p, u32, f64p, u32, f64p, f32p, f64p)
+    sig("lio_sc_set_active", cint, vp, i32p, C.c_int32)
+    sig("lio_sc_distance", cint, vp, f64p, f64p, u32, f64p, i32p)
+    sig("lio_sc_search", cint, vp, f64p, f32p, u32, i32p, f64p, i32p, i32p)
+    sig("lio_sc_global_search_host", cint, vp, f32p, u32, dbl, i32p, f32p, f64p, i32p)
+    sig("lio_sc_shift_to_yaw", flt, C.c_int32)
+    sig("lio_sc_last_dropped", cint, vp, C.POINTER(u64))
+    sig("lio_sc_last_times", cint, vp, f64p, f64p, f64p)
     gp, gr = C.POINTER(GraphParams), C.POINTER(GraphReport)
     sig("lio_graph_default_params", None, gp)
     sig("lio_graph_create", vp, cint, gp)

@@ -676,6 +676,108 @@ class Gicp:
         check(lib().lio_gicp_align(self.h, ptr(g, C.c_double), C.byref(prm), float(max_corr_dist), ptr(out, C.c_double), C.byref(it), C.byref(conv)), "gicp align")
         return out, bool(conv.value), int(it.value)
 
+    def fitness_score(self, T, max_range=25.0):
+        """getFitnessScore(max_range) of the current pair under T -> (score, nr); max_range bounds the SQUARED distance"""
+        T = f64(T).reshape(4, 4)
+        sc, nr = C.c_double(0), C.c_uint32(0)
+        check(lib().lio_gicp_fitness_score(self.h, ptr(T, C.c_double), float(max_range), C.byref(sc), C.byref(nr)), "gicp fitness_score")
+        return sc.value, nr.value
+
+
+class ScanContext:
+    """SCManager of the relocalisation on the device (lio_sc_*): a bank of key-frame descriptors (20 rings x 60 sectors) resident in HBM,
+    described many clouds at a time; the ring-key search, the column-shift distance and GlobalLocalization::globalSearch over it."""
+
+    RINGS, SECTORS, CANDIDATES = 20, 60, 10
+    SEARCH_SHIFTS = ((0, 0), (-4, 0), (4, 0), (0, -4), (0, 4), (-4, -4), (-4, 4), (4, -4), (4, 4))  # global_localization.cpp:388-390
+
+    def __init__(self, max_frames=4096, max_points_per_call=1 << 20, device=0):
+        self.h = lib().lio_sc_create(device, int(max_frames), int(max_points_per_call))
+        if not self.h:
+            raise capi.LioError("lio_sc_create failed: " + lib().lio_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_sc_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        check(lib().lio_sc_reset(self.h), "sc reset")
+
+    def num_frames(self):
+        return check(lib().lio_sc_num_frames(self.h), "sc num_frames")
+
+    def add_frames(self, clouds):
+        """the clouds ((n_k, 4) f32 each) into the bank in one call; the id of the first"""
+        clouds = [f32(c).reshape(-1, 4) for c in clouds]
+        off = np.zeros(len(clouds) + 1, np.uint64)
+        off[1:] = np.cumsum([len(c) for c in clouds])
+        allp = np.ascontiguousarray(np.concatenate(clouds)) if clouds else np.zeros((0, 4), np.float32)
+        return check(lib().lio_sc_add_frames_host(self.h, ptr(allp, C.c_float), ptr(off, C.c_uint64), len(clouds)), "sc add_frames")
+
+    def download_frame(self, kid):
+        """(descriptor (20, 60) f64, ring key (20,) f32, sector key (60,) f64)"""
+        d, r, s = np.zeros((20, 60)), np.zeros(20, np.float32), np.zeros(60)
+        check(lib().lio_sc_download_frame(self.h, int(kid), ptr(d, C.c_double), ptr(r, C.c_float), ptr(s, C.c_double)), "sc download_frame")
+        return d, r, s
+
+    def describe(self, cloud, shifts=((0.0, 0.0),)):
+        """makeScancontext(cloud, dx, dy) per shift -> (descriptors (m, 20, 60), ring keys (m, 20) f32, sector keys (m, 60))"""
+        p, sh = f32(cloud).reshape(-1, 4), f64(shifts).reshape(-1, 2)
+        m = len(sh)
+        d, r, s = np.zeros((m, 20, 60)), np.zeros((m, 20), np.float32), np.zeros((m, 60))
+        check(lib().lio_sc_describe_host(self.h, ptr(p, C.c_float), len(p), ptr(sh, C.c_double), m, ptr(d, C.c_double), ptr(r, C.c_float), ptr(s, C.c_double)), "sc describe")
+        return d, r, s
+
+    def set_active(self, ids):
+        """the frames a search looks at; None: every frame of the bank"""
+        if ids is None:
+            check(lib().lio_sc_set_active(self.h, None, -1), "sc set_active")
+            return
+        a = np.ascontiguousarray(ids, np.int32).ravel()
+        check(lib().lio_sc_set_active(self.h, ptr(a, C.c_int32), len(a)), "sc set_active")
+
+    def distance(self, desc_a, desc_b):
+        """distanceBtnScanContext per pair -> (distances (n,), shifts (n,) int32)"""
+        a, b = f64(desc_a).reshape(-1, 20, 60), f64(desc_b).reshape(-1, 20, 60)
+        assert len(a) == len(b)
+        n = len(a)
+        d, s = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.int32)
+        check(lib().lio_sc_distance(self.h, ptr(a, C.c_double), ptr(b, C.c_double), n, ptr(d, C.c_double), ptr(s, C.c_int32)), "sc distance")
+        return d[:n], s[:n]
+
+    def search(self, desc, ringkey):
+        """per query the candidates in rising ring-key distance -> (ids (n, 10), distances (n, 10), shifts (n, 10), n_cand (n,))"""
+        d, r = f64(desc).reshape(-1, 20, 60), f32(ringkey).reshape(-1, 20)
+        assert len(d) == len(r)
+        n = len(d)
+        ids, dist, sh, nc = np.full((max(n, 1), 10), -1, np.int32), np.zeros((max(n, 1), 10)), np.zeros((max(n, 1), 10), np.int32), np.zeros(max(n, 1), np.int32)
+        check(lib().lio_sc_search(self.h, ptr(d, C.c_double), ptr(r, C.c_float), n, ptr(ids, C.c_int32), ptr(dist, C.c_double), ptr(sh, C.c_int32), ptr(nc, C.c_int32)), "sc search")
+        return ids[:n], dist[:n], sh[:n], nc[:n]
+
+    def global_search(self, cloud, dist_thres=0.30):
+        """globalSearch -> dict(match_id (-1: none), yaw (f32), score, shift)"""
+        p = f32(cloud).reshape(-1, 4)
+        mid, yaw, sc, sh = C.c_int32(0), C.c_float(0), C.c_double(0), C.c_int32(0)
+        check(lib().lio_sc_global_search_host(self.h, ptr(p, C.c_float), len(p), float(dist_thres), C.byref(mid), C.byref(yaw), C.byref(sc), C.byref(sh)), "sc global_search")
+        return dict(match_id=mid.value, yaw=np.float32(yaw.value), score=sc.value, shift=sh.value)
+
+    @staticmethod
+    def shift_to_yaw(shift):
+        return np.float32(lib().lio_sc_shift_to_yaw(int(shift)))
+
+    def last_dropped(self):
+        n = C.c_uint64(0)
+        check(lib().lio_sc_last_dropped(self.h, C.byref(n)), "sc last_dropped")
+        return n.value
+
+    def last_times(self):
+        v = [C.c_double(0) for _ in range(3)]
+        check(lib().lio_sc_last_times(self.h, *[C.byref(x) for x in v]), "sc last_times")
+        return dict(zip(("describe_us", "ringkey_us", "distance_us"), [x.value for x in v]))
+
 
 class LoopDetector:
     """hdl_graph_slam::LoopDetector on the device (lio_loop_*): a bank of key frames with their covariances, find_candidates, all candidates
