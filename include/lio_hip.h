@@ -75,8 +75,12 @@ int lio_device_count(void);
  *      current pairs).  lio_gicp_set_target / _set_source now refuse points that are not finite, lio_gicp_linearize / _align a pose that is not
  *      finite or a max_corr_dist that is negative or NaN (LIO_E_INVALID, nothing launched, the object as it was).
  * 18 = lio_sc_* (the Scan Context bank of the relocalisation: descriptors of many clouds in one set of launches, the ring-key search, the
- *      column-shift distance, globalSearch) and lio_gicp_fitness_score (getFitnessScore of the handle's own pair). */
-#define LIO_ABI_VERSION 18
+ *      column-shift distance, globalSearch) and lio_gicp_fitness_score (getFitnessScore of the handle's own pair).
+ * 19 = lio_gicp_set_target_device / _set_source_device (a cloud in HBM through the host entry's path), lio_scan_ds_device, lio_localmap_nearest /
+ *      _gather / _z_mean / _download_gather / _gather_device / _store_frame / _frame / _estimate_pose, lio_estimate_matcher_params (the operator's
+ *      pose hint, GlobalLocalization::getEstimatePose, on the device).  lio_gicp_set_target / _set_source now leave the cloud in an internal
+ *      order that is a function of the cloud (it was the grid's arrival order: lio_gicp_download differed from call to call, T in its last bits). */
+#define LIO_ABI_VERSION 19
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -210,6 +214,9 @@ int lio_scan_set_ds(lio_scan*, const float* ds_body_xyzi, uint32_t n_ds);
 int lio_scan_num_ds(lio_scan*);                                                   /* syncs the stream */
 int lio_scan_download_ds(lio_scan*, float* out_xyzi, uint32_t cap);              /* feats_down_body */
 int lio_scan_download_world(lio_scan*, float* out_xyzi, uint32_t cap);           /* feats_down_world */
+/* ABI 19: the downsampled cloud where it lies in HBM (n_ds float4 x y z intensity) and its size; waits for the scan's stream.  NULL when there
+ * is none.  The pointer is the scan's own buffer: valid until the scan is written again. */
+const void* lio_scan_ds_device(lio_scan*, uint32_t* n);
 /* per-point results of the last linearize: any pointer may be NULL.
  * selected[n_ds] (point_selected_surf), normvec[n_ds*4] (n, pd2), nn_cnt[n_ds], nn_pts[n_ds*5*4] */
 int lio_scan_download_match(lio_scan*, uint8_t* selected, float* normvec, int32_t* nn_cnt, float* nn_pts);
@@ -674,6 +681,15 @@ lio_gicp* lio_gicp_create(int device, float grid_resolution, uint32_t max_points
 void lio_gicp_destroy(lio_gicp*);
 int lio_gicp_set_target(lio_gicp*, const float* xyzi, uint32_t n);
 int lio_gicp_set_source(lio_gicp*, const float* xyzi, uint32_t n);
+/* ABI 19: the same two calls for a cloud that lies in HBM (n float4 x y z intensity, complete: whatever wrote it has been waited for).  The
+ * contract is the host entry's: more than max_points is LIO_E_CAPACITY, fewer than k points or a coordinate that is not finite is LIO_E_INVALID
+ * (a kernel counts such points and one word comes back), and a refused call leaves the matcher as it was.  The staging copy is device to device;
+ * from there on the path is the host entry's (grid, covariance kernel, the source's copy in caller order).  All four entries leave the cloud
+ * in ONE internal order, a function of the cloud alone: the grid's cells by the lowest caller row among their points, a cell's points by
+ * rising caller row (the grid's own arrival order is put right after the insertion).  So the same points set from either side, on any handle,
+ * any number of times, give the same bits in lio_gicp_download, lio_gicp_align and lio_gicp_fitness_score. */
+int lio_gicp_set_target_device(lio_gicp*, const void* d_xyzi, uint32_t n);
+int lio_gicp_set_source_device(lio_gicp*, const void* d_xyzi, uint32_t n);
 /* The voxelised variant, fast_gicp::FastVGICP (fast_vgicp_impl.hpp:72-204; select_registration_method("FAST_VGICP"), registrations.cpp:56-66:
  * the reference's matcher on machines without CUDA): voxel_resolution > 0 turns the target into Gaussian voxels (mean position, mean of the
  * points' regularised 20-NN covariances: ADDITIVE mode, fast_vgicp_voxel.hpp:95-110,129-167) and lio_gicp_linearize / _align into its
@@ -758,6 +774,54 @@ int lio_localmap_num_keyframes(lio_localmap*);
 int lio_localmap_update(lio_localmap*, lio_ndt* target, const double pose_xyz[3], double update_distance, double radius, double key_frame_distance,
                         float leaf, int* n_keyframes, uint32_t* n_points);
 int lio_localmap_download(lio_localmap*, float* out_xyzi, uint32_t cap);
+
+/* ABI 19 -- the operator's pose hint on the device: GlobalLocalization::getEstimatePose (slam/localization/src/global_localization.cpp:196-262).
+ * The key frames near the hint become the FAST_VGICP matcher's target without leaving HBM, the latest scan (already in HBM) is its source.
+ *   nearest ........ mGraphKDTree->nearestKSearch over the key-frame positions with z = 0 on both sides (buildGraphKDTree), on the host: f32,
+ *                    dx = pos_x - (float)x, dy = pos_y - (float)y, d2 = dx*dx + dy*dy; the min(k, frames) smallest (d2, id) in rising order --
+ *                    equal distances go to the smaller id.  Returns the count; d2 may be NULL.
+ *   gather ......... the named key frames' clouds back to back, in the order given, into a buffer of the local map by ONE launch, which also
+ *                    sums z.  THE CHUNKED Z SUM (the project's rule; the reference adds sequentially, so the last bits differ -- the mean only
+ *                    seeds a guess): the output is cut into chunks of 256 consecutive points; lane j of chunk c holds (double)z of point
+ *                    256 c + j, or 0 past the end; a chunk's sum is the tree x[j] += x[j + s] for s = 128, 64, ..., 1; the chunk sums are
+ *                    added in rising chunk order by one thread; the mean is that sum divided by n (on the host).  No floating-point atomics:
+ *                    two runs give the same bits.  n_ids <= 16; ids may repeat; empty frames are allowed; a total of 0 is LIO_E_INVALID; a total
+ *                    above the buffer (max(max_local_points + max_keyframe_points, 5 * max_keyframe_points)) is LIO_E_CAPACITY; a refused
+ *                    call changes nothing (the previous gather is still there).
+ *   z_mean ......... the same sum over any cloud in HBM (the hint's source), by the same rule.
+ *   download_gather / gather_device  the last gather, to the host / where it lies (NULL before the first).
+ *   store_frame / frame  two clouds kept with the local map as device copies (slot 0, 1; the module keeps the latest scan and the frame a hint
+ *                    was matched with); n = 0 empties a slot.
+ *   estimate_pose .. 1. the LIO_ESTIMATE_K = 5 nearest key frames to (hint[3], hint[7]), up to the first with d2 > 400;  2. gather -> target,
+ *                    source from the device;  3. hint z = z_mean(target) - z_mean(source);  4. the guess is the hint rounded to f32;
+ *                    5. lio_gicp_align with lio_estimate_matcher_params (the loop detector's coarse FAST_VGICP) -- `gicp` must be in voxel mode
+ *                    with the loop parameters' voxel_resolution, DIRECT1;  6. not converged: result 0, out_T = the hint with the new z;
+ *                    7. else lio_gicp_fitness_score(loop fitness_score_max_range): score < 5 -> out_T = the final transformation through f32,
+ *                    score < 0.5 -> result 1;  8. no key frame within 20 m, only empty ones, or n_source = 0: result 0, out_T = the hint
+ *                    untouched, LIO_OK.  A matcher error (a cloud below k points, over its max_points) is returned as it is, with result 0
+ *                    and out_T = the hint.  400, 5.0 and 0.5 are the reference's.  There is no CPU path.
+ * The report's stage times are HIP-event spans on the local map's stream; the matcher's stages run on the matcher's streams and are waited for
+ * before the next event, so a span covers the stage's launches and the host work between them (the LM loop of align). */
+#define LIO_ESTIMATE_K 5
+typedef struct lio_estimate_report {
+    int32_t n_ids, ids[LIO_ESTIMATE_K];
+    uint32_t n_target, n_source;
+    int32_t converged, iterations, result, pose_replaced; /* result: the reference's return value; pose_replaced: score < 5 */
+    double z_mean_target, z_mean_source;
+    double guess[16]; /* what the matcher started from (f32 values) */
+    double score;     /* 0 when the matcher did not converge */
+    double nearest_us /* host */, gather_us, set_target_us, set_source_us, z_source_us, align_us, fitness_us;
+} lio_estimate_report;
+int lio_localmap_nearest(lio_localmap*, const double xy[2], uint32_t k, int32_t* ids, float* d2);
+int lio_localmap_gather(lio_localmap*, const int32_t* ids, uint32_t n_ids, uint32_t* n_points, double* z_mean);
+int lio_localmap_z_mean(lio_localmap*, const void* d_xyzi, uint32_t n, double* z_mean);
+int lio_localmap_download_gather(lio_localmap*, float* out_xyzi, uint32_t cap);
+const void* lio_localmap_gather_device(lio_localmap*, uint32_t* n);
+int lio_localmap_store_frame(lio_localmap*, int slot, const void* d_xyzi, uint32_t n);
+const void* lio_localmap_frame(lio_localmap*, int slot, uint32_t* n);
+void lio_estimate_matcher_params(lio_ndt_params* out);
+int lio_localmap_estimate_pose(lio_localmap*, lio_gicp*, const void* d_source_xyzi, uint32_t n_source, const double hint[16], lio_estimate_report* report,
+                               double out_T[16]);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Dense-map export on the device: one cloud that grows over a drive (the reference's static g_accumulate_cloud,

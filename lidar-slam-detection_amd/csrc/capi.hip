@@ -952,6 +952,15 @@ static int download_f4(lio_scan* s, const float4* src, float* out, uint32_t cap)
 }
 
 int lio_scan_download_ds(lio_scan* s, float* out, uint32_t cap) { return (!s || !out) ? LIO_E_INVALID : download_f4(s, s->ds_body, out, cap); }
+// the downsampled cloud where it lies (waits for the scan's stream; valid until the scan is next written)
+const void* lio_scan_ds_device(lio_scan* s, uint32_t* n) {
+    if (n) *n = 0;
+    if (!s) return nullptr;
+    const int m = lio_scan_num_ds(s);
+    if (m <= 0) return nullptr;
+    if (n) *n = (uint32_t)m;
+    return s->ds_body;
+}
 int lio_scan_download_world(lio_scan* s, float* out, uint32_t cap) { return (!s || !out) ? LIO_E_INVALID : download_f4(s, s->ds_world, out, cap); }
 
 int lio_scan_download_match(lio_scan* s, uint8_t* selected, float* normvec, int32_t* nn_cnt, float* nn_pts) {

@@ -336,29 +336,6 @@ __global__ void __launch_bounds__(256) vgicp_stamp_kernel(const float4* __restri
     out[i] = make_float4(p.x, p.y, p.z, __uint_as_float(i));
 }
 
-// AdditiveGaussianVoxel::append / finalize: one lane per occupied voxel, its points in pool order
-__global__ void __launch_bounds__(256) vgicp_fold_kernel(const Slot* __restrict__ table, uint32_t table_cap, const float4* __restrict__ pool,
-                                                         const double* __restrict__ tcov, VgicpVoxel* __restrict__ vox) {
-    const uint32_t h = blockIdx.x * 256u + threadIdx.x;
-    if (h >= table_cap) return;
-    const Slot s = table[h];
-    if (s.key == kEmptyKey || s.cnt == 0) return;
-    double m[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t j = 0; j < s.cnt; j++) {
-        const float4 p = pool[s.ptr + j];
-        m[0] += (double)p.x; m[1] += (double)p.y; m[2] += (double)p.z;
-        const double* pc = tcov + (size_t)__float_as_uint(p.w) * 6;
-#pragma unroll
-        for (int a = 0; a < 6; a++) c[a] += pc[a];
-    }
-    const double n = (double)s.cnt;
-    VgicpVoxel v;
-    for (int a = 0; a < 3; a++) v.mean[a] = m[a] / n;
-    for (int a = 0; a < 6; a++) v.cov[a] = c[a] / n;
-    v.n = n;
-    vox[h] = v;
-}
-
 // The fold for a target adopted with its rows (grid0[i].w = the row of the point in the caller's cloud): a voxel's points are taken by rising
 // row, not in the voxel map's pool order, which is their arrival order and differs from one build to the next.
 // Step 1, one lane per target point i (= its row in grid0, the order it was inserted into the voxel map in, so slot_of_point[i] is its voxel):
@@ -381,7 +358,7 @@ __global__ void __launch_bounds__(256) vgicp_rank_rows_kernel(const Slot* __rest
     if (rank < s.cnt && (unsigned long long)s.ptr + rank < n) order[s.ptr + rank] = i;  // (a first batch is laid out exactly: ptr + cnt <= n)
 }
 
-// Step 2, AdditiveGaussianVoxel::append / finalize as vgicp_fold_kernel, one lane per occupied voxel, its points in `order`
+// Step 2, AdditiveGaussianVoxel::append / finalize: one lane per occupied voxel, its points in `order`
 __global__ void __launch_bounds__(256) vgicp_fold_rows_kernel(const Slot* __restrict__ table, uint32_t table_cap, const uint32_t* __restrict__ order,
                                                               const float4* __restrict__ grid0, uint32_t n, const double* __restrict__ tcov,
                                                               VgicpVoxel* __restrict__ vox) {
@@ -495,6 +472,114 @@ __global__ void __launch_bounds__(256) gicp_scatter_cov_kernel(const float4* __r
     for (int a = 0; a < 6; a++) out[(size_t)i * 6 + a] = in[(size_t)j * 6 + a];
 }
 
+// ---- a pool whose order is a function of the cloud (gicp_stage_cloud) ------------------------------------------------------------------------
+// The grid lays a first batch out cell by cell, the cells in the order of the slots their keys won and a cell's points in the order they
+// arrived: both differ from one insertion of a cloud to the next.  The cost sums run in pool order and the neighbour searches break ties by
+// pool index, so set_target / set_source put the pool into ONE order afterwards: the cells by the lowest caller row among their points, a
+// cell's points by rising caller row.  The grid was filled from a copy stamped with the rows (vgicp_stamp_kernel).
+// 1: the lowest row of every cell (integer atomicMin: the result does not depend on the order of arrival)
+__global__ void __launch_bounds__(256) gicp_canon_minrow_kernel(const uint32_t* __restrict__ slot_of_point, uint32_t n, uint32_t table_cap, uint32_t* __restrict__ minrow) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t sp = slot_of_point[i];
+    if (sp == kNoIdx) return;
+    const uint32_t h = sp & 0x7FFFFFFFu;
+    if (h < table_cap) atomicMin(&minrow[h], i);
+}
+// 2: the cell's size at the place of its lowest row (every other place of `size` is 0)
+__global__ void __launch_bounds__(256) gicp_canon_sizes_kernel(const Slot* __restrict__ table, uint32_t table_cap, const uint32_t* __restrict__ minrow, uint32_t n,
+                                                               uint32_t* __restrict__ size) {
+    const uint32_t h = blockIdx.x * 256u + threadIdx.x;
+    if (h >= table_cap) return;
+    const Slot s = table[h];
+    if (s.key == kEmptyKey || s.cnt == 0 || minrow[h] >= n) return;
+    size[minrow[h]] = s.cnt;
+}
+// 3: exclusive prefix sum of `size` in place, one block (n is a cloud's size: a few hundred steps of 1024 at the most)
+__global__ void __launch_bounds__(1024) gicp_canon_scan_kernel(uint32_t* __restrict__ size, uint32_t n) {
+    __shared__ uint32_t x[1024];
+    __shared__ uint32_t base;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (uint32_t c0 = 0; c0 < n; c0 += 1024u) {
+        const uint32_t i = c0 + threadIdx.x;
+        const uint32_t v = i < n ? size[i] : 0u;
+        x[threadIdx.x] = v;
+        __syncthreads();
+        for (uint32_t d = 1; d < 1024u; d <<= 1) {  // Hillis-Steele, inclusive
+            const uint32_t a = threadIdx.x >= d ? x[threadIdx.x - d] : 0u;
+            __syncthreads();
+            x[threadIdx.x] += a;
+            __syncthreads();
+        }
+        if (i < n) size[i] = base + x[threadIdx.x] - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) base += x[1023];
+        __syncthreads();
+    }
+}
+// 4: every point to its place: the cell's new first place + its rank among the rows of its cell (read from the stamped pool)
+__global__ void __launch_bounds__(256) gicp_canon_place_kernel(const Slot* __restrict__ table, uint32_t table_cap, const uint32_t* __restrict__ slot_of_point,
+                                                               const float4* __restrict__ stamped_pool, const uint32_t* __restrict__ minrow,
+                                                               const uint32_t* __restrict__ first, const float4* __restrict__ cloud, uint32_t n,
+                                                               float4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t sp = slot_of_point[i];
+    if (sp == kNoIdx) return;
+    const uint32_t h = sp & 0x7FFFFFFFu;
+    if (h >= table_cap) return;
+    const Slot s = table[h];
+    const uint32_t mr = minrow[h];
+    if (mr >= n) return;
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < s.cnt; j++) {
+        if ((unsigned long long)s.ptr + j >= n) break;  // (a first batch is laid out exactly: ptr + cnt <= n)
+        rank += __float_as_uint(stamped_pool[s.ptr + j].w) < i;
+    }
+    const unsigned long long at = (unsigned long long)first[mr] + rank;
+    if (at < n) out[at] = cloud[i];
+}
+// 5: the cells' new first places into the table
+__global__ void __launch_bounds__(256) gicp_canon_table_kernel(Slot* __restrict__ table, uint32_t table_cap, const uint32_t* __restrict__ minrow,
+                                                               const uint32_t* __restrict__ first, uint32_t n) {
+    const uint32_t h = blockIdx.x * 256u + threadIdx.x;
+    if (h >= table_cap) return;
+    const Slot s = table[h];
+    if (s.key == kEmptyKey || s.cnt == 0 || minrow[h] >= n) return;
+    table[h].ptr = first[minrow[h]];
+}
+
+// Gaussian voxels of a target in canonical pool order: the rank of target point i (its pool index, which the voxel map's copy carries as its
+// stamp) among the points of its voxel, order[voxel's first + rank] = i -- vgicp_rank_rows_kernel with the pool index as the row
+__global__ void __launch_bounds__(256) vgicp_rank_stamps_kernel(const Slot* __restrict__ table, const uint32_t* __restrict__ slot_of_point,
+                                                                const float4* __restrict__ pool, uint32_t n, uint32_t* __restrict__ order) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t sp = slot_of_point[i];
+    if (sp == kNoIdx) return;
+    const Slot s = table[sp & 0x7FFFFFFFu];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < s.cnt; j++) {
+        if ((unsigned long long)s.ptr + j >= n) break;
+        rank += __float_as_uint(pool[s.ptr + j].w) < i;
+    }
+    if (rank < s.cnt && (unsigned long long)s.ptr + rank < n) order[s.ptr + rank] = i;
+}
+
+// points with a coordinate that is not finite (lio_gicp_set_target_device / _set_source_device: the host entry's check, on the device).  One
+// integer add per wave that holds such a point.
+__global__ void __launch_bounds__(256) gicp_count_nonfinite_kernel(const float4* __restrict__ pts, uint32_t n, uint32_t* __restrict__ count) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        const float4 p = pts[i];
+        bad = !(fabsf(p.x) <= FLT_MAX && fabsf(p.y) <= FLT_MAX && fabsf(p.z) <= FLT_MAX);
+    }
+    const unsigned long long m = __ballot(bad);
+    if (m != 0 && (threadIdx.x & 63) == 0) atomicAdd(count, (uint32_t)__popcll(m));
+}
+
 __global__ void __launch_bounds__(1024) gicp_report_kernel(const double* __restrict__ partial, uint32_t nb, GicpReport* __restrict__ out, uint32_t seq) {
     __shared__ double acc[kGicpAcc];
     const int tid = threadIdx.x, c = tid >> 5, l = tid & 31;
@@ -527,10 +612,19 @@ GicpXform to_gx(const double T[16]) {
     return x;
 }
 
-int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
+// what set_target / set_source refuse whatever side of the link the cloud is on
+static int gicp_cloud_args(lio_gicp* g, const void* xyzi, uint32_t n) {
     if (!g || (!xyzi && n)) return LIO_E_INVALID;
     if (n > g->max_points) { set_error("lio_gicp: cloud of %u points exceeds max_points %u", n, g->max_points); return LIO_E_CAPACITY; }
     if ((int)n < g->k) { set_error("lio_gicp: a cloud needs at least k = %d points", g->k); return LIO_E_INVALID; }
+    return LIO_OK;
+}
+
+static int gicp_stage_cloud(lio_gicp* g, int which, const void* xyzi, uint32_t n, hipMemcpyKind kind);
+
+int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
+    const int rc = gicp_cloud_args(g, xyzi, n);
+    if (rc != LIO_OK) return rc;
     // the searches are specified on finite points (a NaN is at no distance from anything); refused before anything is touched
     for (uint32_t i = 0; i < n; i++)
         if (!std::isfinite(xyzi[4 * (size_t)i]) || !std::isfinite(xyzi[4 * (size_t)i + 1]) || !std::isfinite(xyzi[4 * (size_t)i + 2])) {
@@ -538,6 +632,27 @@ int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
             return LIO_E_INVALID;
         }
     hipSetDevice(g->device);
+    return gicp_stage_cloud(g, which, xyzi, n, hipMemcpyHostToDevice);
+}
+
+// The same for a cloud that lies in HBM (complete: its producer has been waited for).  The finite check is a kernel and one word back; the
+// staging copy is device to device; everything after it is gicp_stage_cloud, the host entry's path, which leaves the pool in the one order
+// the cloud defines: the same bits downstream from either entry.
+int gicp_set_cloud_device(lio_gicp* g, int which, const void* d_xyzi, uint32_t n) {
+    const int rc = gicp_cloud_args(g, d_xyzi, n);
+    if (rc != LIO_OK) return rc;
+    hipSetDevice(g->device);
+    if (!g->bad) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->bad), sizeof(uint32_t)));
+    uint32_t bad = 0;
+    LIO_HIP_TRY(hipMemsetAsync(g->bad, 0, sizeof(uint32_t), 0));
+    if (n) hipLaunchKernelGGL(gicp_count_nonfinite_kernel, (n + 255) / 256, 256, 0, 0, static_cast<const float4*>(d_xyzi), n, g->bad);
+    LIO_HIP_TRY(hipGetLastError());
+    LIO_HIP_TRY(hipMemcpy(&bad, g->bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (bad) { set_error("lio_gicp: %u points of the device cloud have a coordinate that is not finite", bad); return LIO_E_INVALID; }
+    return gicp_stage_cloud(g, which, d_xyzi, n, hipMemcpyDeviceToDevice);
+}
+
+static int gicp_stage_cloud(lio_gicp* g, int which, const void* xyzi, uint32_t n, hipMemcpyKind kind) {
     // an EMPTY grid per cloud: the first batch into an empty map is laid out exactly (cell by cell, contiguous from the start of the pool).
     // The grid object is made once and emptied in place afterwards (map_clear: memsets; a fresh lio_map_create per call was 5-65 ms of
     // hipMalloc / hipFree, more than the covariances)
@@ -550,19 +665,43 @@ int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n) {
     }
     lio_map* m = g->grid[which];
     hipStream_t st = m->stream;
-    LIO_HIP_TRY(hipMemcpyAsync(g->stage, xyzi, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, st));
+    LIO_HIP_TRY(hipMemcpyAsync(g->stage, xyzi, (size_t)n * sizeof(float4), kind, st));
     if (which == 1) {  // the grid lays the cloud out cell by cell: lio_gicp_fitness_score adds in the caller's order
         g->src_order = 0;
         if (!g->src_rows) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->src_rows), (size_t)g->max_points * sizeof(float4)));
         LIO_HIP_TRY(hipMemcpyAsync(g->src_rows, g->stage, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, st));
     }
-    int rc = lio_map_insert_device(m, g->stage, n, 0.0);
+    // the grid is filled from a copy stamped with the caller's rows, then its pool is put into the one order the cloud defines (above)
+    if (!g->canon) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->canon), (size_t)g->max_points * sizeof(float4)));
+    if (!g->canon_first) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->canon_first), (size_t)g->max_points * sizeof(uint32_t)));
+    if (g->canon_minrow_cap < m->table_cap) {
+        if (g->canon_minrow) { hipFree(g->canon_minrow); g->canon_minrow = nullptr; g->canon_minrow_cap = 0; }
+        LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->canon_minrow), (size_t)m->table_cap * sizeof(uint32_t)));
+        g->canon_minrow_cap = m->table_cap;
+    }
+    hipLaunchKernelGGL(vgicp_stamp_kernel, (n + 255) / 256, 256, 0, st, g->stage, g->canon, n);
+    LIO_HIP_TRY(hipGetLastError());
+    int rc = lio_map_insert_device(m, g->canon, n, 0.0);
     if (rc != LIO_OK) return rc;
     g->n[which] = n;
     g->rows[which] = false;
     g->gridded[which] = true;
     if (which == 0) { g->vmap_valid = false; g->fit_valid = false; }
     else g->src_order = 1;
+    {
+        const uint32_t tb = (m->table_cap + 255) / 256, pb = (n + 255) / 256;
+        LIO_HIP_TRY(hipMemsetAsync(g->canon_minrow, 0xFF, (size_t)m->table_cap * sizeof(uint32_t), st));
+        LIO_HIP_TRY(hipMemsetAsync(g->canon_first, 0, (size_t)n * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(gicp_canon_minrow_kernel, pb, 256, 0, st, m->slot_of_point, n, (uint32_t)m->table_cap, g->canon_minrow);
+        hipLaunchKernelGGL(gicp_canon_sizes_kernel, tb, 256, 0, st, m->table, (uint32_t)m->table_cap, g->canon_minrow, n, g->canon_first);
+        hipLaunchKernelGGL(gicp_canon_scan_kernel, 1, 1024, 0, st, g->canon_first, n);
+        // (the stamped input has been copied into the pool: its buffer takes the ordered cloud)
+        hipLaunchKernelGGL(gicp_canon_place_kernel, pb, 256, 0, st, m->table, (uint32_t)m->table_cap, m->slot_of_point, m->pool, g->canon_minrow, g->canon_first, g->stage, n,
+                           g->canon);
+        hipLaunchKernelGGL(gicp_canon_table_kernel, tb, 256, 0, st, m->table, (uint32_t)m->table_cap, g->canon_minrow, g->canon_first, n);
+        LIO_HIP_TRY(hipGetLastError());
+        LIO_HIP_TRY(hipMemcpyAsync(m->pool, g->canon, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    }
     hipLaunchKernelGGL(gicp_cov_kernel<false>, (uint32_t)(((uint64_t)n * kGrp + kGrpThreads - 1) / kGrpThreads), kGrpThreads, 0, st, m->table, m->table_mask, m->pool, n, g->res, g->k, g->cov[which],
                        (int32_t*)nullptr);
     LIO_HIP_TRY(hipGetLastError());
@@ -598,9 +737,13 @@ int vgicp_build(lio_gicp* g) {
         hipLaunchKernelGGL(vgicp_fold_rows_kernel, (g->vmap->table_cap + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->table_cap, g->vorder, mt->pool, n,
                            g->cov[0], g->vvox);
     }
-    else
-        hipLaunchKernelGGL(vgicp_fold_kernel, (g->vmap->table_cap + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->table_cap, g->vmap->pool, g->cov[0],
-                           g->vvox);
+    else {  // a target set as a cloud: its pool order is the cloud's own (gicp_stage_cloud), a voxel's points are taken by rising pool index
+        if (!g->vorder) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->vorder), (size_t)g->max_points * sizeof(uint32_t)));
+        LIO_HIP_TRY(hipMemsetAsync(g->vorder, 0xFF, (size_t)n * sizeof(uint32_t), g->vmap->stream));
+        hipLaunchKernelGGL(vgicp_rank_stamps_kernel, (n + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->slot_of_point, g->vmap->pool, n, g->vorder);
+        hipLaunchKernelGGL(vgicp_fold_rows_kernel, (g->vmap->table_cap + 255) / 256, 256, 0, g->vmap->stream, g->vmap->table, g->vmap->table_cap, g->vorder, mt->pool, n,
+                           g->cov[0], g->vvox);
+    }
     LIO_HIP_TRY(hipGetLastError());
     LIO_HIP_TRY(hipStreamSynchronize(g->vmap->stream));
     g->vmap_valid = true;
@@ -798,6 +941,10 @@ void lio_gicp_destroy(lio_gicp* g) {
     if (g->partial) hipFree(g->partial);
     if (g->stage) hipFree(g->stage);
     if (g->src_rows) hipFree(g->src_rows);
+    if (g->bad) hipFree(g->bad);
+    if (g->canon) hipFree(g->canon);
+    if (g->canon_first) hipFree(g->canon_first);
+    if (g->canon_minrow) hipFree(g->canon_minrow);
     gicp_fit_free(g);
     if (g->report) hipHostFree(g->report);
     delete g;
@@ -805,6 +952,8 @@ void lio_gicp_destroy(lio_gicp* g) {
 
 int lio_gicp_set_target(lio_gicp* g, const float* xyzi, uint32_t n) { return gicp_set_cloud(g, 0, xyzi, n); }
 int lio_gicp_set_source(lio_gicp* g, const float* xyzi, uint32_t n) { return gicp_set_cloud(g, 1, xyzi, n); }
+int lio_gicp_set_target_device(lio_gicp* g, const void* d_xyzi, uint32_t n) { return gicp_set_cloud_device(g, 0, d_xyzi, n); }
+int lio_gicp_set_source_device(lio_gicp* g, const void* d_xyzi, uint32_t n) { return gicp_set_cloud_device(g, 1, d_xyzi, n); }
 
 int lio_gicp_set_voxel_mode(lio_gicp* g, double voxel_resolution, int search_method) {
     if (!g || voxel_resolution < 0.0 || (search_method != 1 && search_method != 7 && search_method != 27)) { set_error("lio_gicp_set_voxel_mode: bad argument"); return LIO_E_INVALID; }

@@ -109,12 +109,20 @@ struct lio_gicp {
     int src_order = 0;       // 0: not kept; 1: src_rows; 2: the source grid's pool is the caller's order (an adopted source)
     void* fit = nullptr;     // loop.hip's GicpFit
     bool fit_valid = false;  // the index is over the current target
+    uint32_t* bad = nullptr;  // the count of the device entries' finite check; made on first use
+    // gicp_stage_cloud's canonical pool order: the stamped / ordered cloud, the cells' first places (by lowest row), the lowest row per slot
+    float4* canon = nullptr;
+    uint32_t* canon_first = nullptr;
+    uint32_t* canon_minrow = nullptr;
+    uint64_t canon_minrow_cap = 0;
 };
 
 namespace lio {
 GicpXform to_gx(const double T[16]);
 // setInputTarget / setInputSource: the cloud into its hash grid (pool order), the regularised k-NN covariances beside it
 int gicp_set_cloud(lio_gicp* g, int which, const float* xyzi, uint32_t n);
+// the same for a cloud in HBM: finite check by a kernel, device-to-device staging copy, then the host entry's path
+int gicp_set_cloud_device(lio_gicp* g, int which, const void* d_xyzi, uint32_t n);
 // the same for a cloud on the device; the covariances also come back in the CLOUD's own row order (d_cov6_rows[i] belongs to d_pts[i]).
 // The order of a grid's pool is the points' arrival order inside a cell, which is any order: what has to be the same from one insertion of a
 // cloud to the next is kept by row

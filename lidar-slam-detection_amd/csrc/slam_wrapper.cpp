@@ -160,7 +160,16 @@ struct Loc {
     std::vector<float> reloc_ds;
     struct Reloc { bool searched = false, accepted = false; int match_id = -1, converged = 0; double score = 0, fitness = 0, dx = 0, da = 0; float yaw = 0; } last_reloc;
     int reloc_searches = 0;  // searches run since init_slam
+    // the operator's hint (GlobalLocalization::getEstimatePose / setInitPose's mLastFrame / initializePose's pose * delta).  The last frame is
+    // the downsampled cloud in `scan` (have_last_frame: the scan holds the reduced cloud of the most recent non-empty frame); an accepted hint
+    // keeps its pose and a device copy of that frame (slot 1 of the local map) until the next non-empty frame hands over to the filter
+    lio_gicp* est_gicp = nullptr;
+    bool have_last_frame = false, est_pending = false;
+    Mat4 est_pose = Mat4::identity();
+    struct Est { bool called = false, handover = false, delta_ran = false; int rc = 0, delta_converged = 0, delta_iterations = 0; lio_estimate_report rep = lio_estimate_report();
+                 Mat4 hint = Mat4::identity(), out = Mat4::identity(), delta = Mat4::identity(); } last_est;
     ~Loc() {
+        if (est_gicp) lio_gicp_destroy(est_gicp);
         if (reloc_gicp) lio_gicp_destroy(reloc_gicp);
         if (sc) lio_sc_destroy(sc);
         if (moverlap) lio_overlap_destroy(moverlap);
@@ -390,6 +399,18 @@ Mat4 yaw_matrix_f32(float y) {
     return m;
 }
 
+// GlobalLocalization::downsample of the cloud in L.staged: the VoxelGrid of the localizer's resolution, into L.scan.  The reduced cloud stays in
+// HBM as the last frame (mLastFrame) a hint is matched with
+bool loc_reduce_staged(Loc& L, uint32_t n, uint32_t& n_ds) {
+    L.have_last_frame = false;
+    if (lio_scan_upload(L.scan, L.staged.data(), n) != LIO_OK) return false;
+    n_ds = n;
+    if (L.resolution >= 0.1) { if (lio_scan_voxel_downsample(L.scan, (float)L.resolution, 1, &n_ds) != LIO_OK) return false; }
+    else if (lio_scan_set_ds(L.scan, L.staged.data(), n) != LIO_OK) return false;
+    L.have_last_frame = n_ds > 0;
+    return true;
+}
+
 // GlobalLocalization::globalSearch + registrationAlign with the cloud in L.staged: true when an initial pose was accepted into L.init_pose.
 // DEVIATION: synchronous, on every uninitialised frame (the reference's search thread drops the frames that arrive while it is busy and
 // registers the next one against the frame it searched with); localSearch (INS-aided) and the image search are not built
@@ -397,11 +418,9 @@ bool loc_relocalize(Loc& L, uint32_t n) {
     Loc::Reloc& r = L.last_reloc;
     r = Loc::Reloc();
     if (!L.sc || n == 0) return false;
-    // GlobalLocalization::downsample: the VoxelGrid of the localizer's resolution
-    if (lio_scan_upload(L.scan, L.staged.data(), n) != LIO_OK) return false;
     uint32_t n_ds = n;
+    if (!loc_reduce_staged(L, n, n_ds)) return false;
     if (L.resolution >= 0.1) {
-        if (lio_scan_voxel_downsample(L.scan, (float)L.resolution, 1, &n_ds) != LIO_OK) return false;
         L.reloc_ds.resize(4 * (size_t)n_ds);
         if (n_ds && lio_scan_download_ds(L.scan, L.reloc_ds.data(), n_ds) < 0) return false;
     } else {
@@ -452,6 +471,59 @@ bool loc_relocalize(Loc& L, uint32_t n) {
     L.have_init_pose = true;
     r.accepted = true;
     return true;
+}
+
+// GlobalLocalization::getEstimatePose for the hint (a pose on the ground, z = 0): ends the current localisation, matches the last frame against the
+// key frames near the hint on the device (lio_localmap_estimate_pose) and, when the match is good, keeps the pose and the frame for the hand-over.
+// `out` is the pose to answer with.  Returns the reference's result
+int loc_estimate_pose(Loc& L, const Mat4& hint, Mat4& out) {
+    Loc::Est& e = L.last_est;
+    e = Loc::Est();
+    e.called = true;
+    e.hint = hint;
+    out = hint;
+    L.initialized = false;     // Localization::getEstimatePose: mInitialized = false, whatever follows
+    L.have_init_pose = false;  // (a pose from set_init_pose that no frame has taken up yet is replaced by the hint)
+    L.est_pending = false;
+    lio_loop_params lp;
+    lio_loop_default_params(&lp);
+    if (!L.est_gicp) {  // select_registration_method("FAST_VGICP"); room for five of the largest key frames
+        L.est_gicp = lio_gicp_create(0, lp.grid_resolution, std::max<uint32_t>(1u << 18, 5u * L.ndt_biggest), lp.k_correspondences);
+        if (!L.est_gicp || lio_gicp_set_voxel_mode(L.est_gicp, lp.voxel_resolution, 1) != LIO_OK) { e.rc = LIO_E_DEVICE; return 0; }
+    }
+    uint32_t ns = 0;
+    const void* src = L.have_last_frame ? lio_scan_ds_device(L.scan, &ns) : nullptr;
+    e.rc = lio_localmap_estimate_pose(L.lm, L.est_gicp, src, src ? ns : 0, hint.m, &e.rep, out.m);
+    e.out = out;
+    if (e.rc != LIO_OK || e.rep.result != 1) return 0;
+    // mInitialized = true; setInputTarget(mLastFrame); mPoseQueue.enqueue(t)
+    require(lio_localmap_store_frame(L.lm, 1, src, ns) == LIO_OK, "get_estimate_pose: keeping the matched frame failed");
+    L.est_pose = out;
+    L.est_pending = true;
+    return 1;
+}
+
+// initializePose's second branch (global_localization.cpp:85-91): the new frame (reduced, in L.scan) aligned to the frame the hint was matched with,
+// from the identity, by the same matcher; delta = getFinalTransformation() (f32).  The identity when the matcher cannot run (a cloud below k points)
+Mat4 loc_handover_delta(Loc& L) {
+    Loc::Est& e = L.last_est;
+    e.handover = true;
+    e.delta = Mat4::identity();
+    lio_loop_params lp;
+    lio_loop_default_params(&lp);
+    uint32_t nt = 0, ns = 0;
+    const void* tgt = lio_localmap_frame(L.lm, 1, &nt);
+    const void* src = lio_scan_ds_device(L.scan, &ns);
+    if (!L.est_gicp || !tgt || !src || (int)nt < lp.k_correspondences || (int)ns < lp.k_correspondences) return e.delta;
+    if (lio_gicp_set_target_device(L.est_gicp, tgt, nt) != LIO_OK || lio_gicp_set_source_device(L.est_gicp, src, ns) != LIO_OK) return e.delta;
+    lio_ndt_params p;
+    lio_estimate_matcher_params(&p);
+    const Mat4 I = Mat4::identity();
+    double T[16];
+    if (lio_gicp_align(L.est_gicp, I.m, &p, 1.0, T, &e.delta_iterations, &e.delta_converged) != LIO_OK) return e.delta;
+    e.delta_ran = true;
+    for (int i = 0; i < 12; i++) e.delta.m[i] = (double)(float)T[i];
+    return e.delta;
 }
 
 // Localization::init (localization.cpp:91-131) without the graph back end: the key frames of the map go to HBM once
@@ -522,8 +594,21 @@ bool loc_timed_pose(Loc& L, uint64_t stamp, Mat4& out) {
 bool loc_localize(Slam* s, uint32_t n, uint64_t stamp, Mat4& pose_out) {
     Loc& L = *s->loc;
     if (!L.initialized) {
-        // no pose from set_init_pose: the global locator (scan context + FAST_VGICP) looks for one when it is switched on
-        if (!L.have_init_pose && !(L.reloc && loc_relocalize(L, n))) return false;
+        if (L.est_pending) {  // an accepted hint: the next non-empty frame hands over, the filter starts from pose * delta
+            uint32_t m = 0;
+            if (n == 0 || !loc_reduce_staged(L, n, m)) return false;
+            L.init_pose = mul(L.est_pose, loc_handover_delta(L));
+            L.have_init_pose = true;
+            L.est_pending = false;
+        } else if (!L.have_init_pose) {
+            // no pose from set_init_pose: the global locator (scan context + FAST_VGICP) looks for one when it is switched on.  Either way the
+            // frame is reduced and stays on the device: it is what a hint would be matched with
+            bool found = false;
+            uint32_t m = 0;
+            if (L.reloc) found = loc_relocalize(L, n);
+            else if (n) loc_reduce_staged(L, n, m);
+            if (!found) return false;
+        }
         // Localization::initLocalizer -> initialpose_callback (hdl_localization_nodelet.cpp:304-317): normalised quaternion of the pose, cool time 0.2 s
         float ext[16];
         for (int i = 0; i < 16; i++) ext[i] = (float)s->T_imu.m[i];
@@ -587,8 +672,10 @@ bool loc_localize(Slam* s, uint32_t n, uint64_t stamp, Mat4& pose_out) {
         lio_scan_undistort_delta(L.scan, L.stamps.data(), 0, df, s->scan_period);
     }
     uint32_t n_ds = 0;
+    L.have_last_frame = false;
     if (L.resolution >= 0.1) { if (lio_scan_voxel_downsample(L.scan, (float)L.resolution, 1, &n_ds) != LIO_OK) return false; }
-    else { std::vector<float> raw(4 * (size_t)n); lio_scan_download_raw(L.scan, raw.data(), n); lio_scan_set_ds(L.scan, raw.data(), n); }
+    else { std::vector<float> raw(4 * (size_t)n); lio_scan_download_raw(L.scan, raw.data(), n); lio_scan_set_ds(L.scan, raw.data(), n); n_ds = n; }
+    L.have_last_frame = n_ds > 0;  // DEVIATION: mLastFrame is refreshed while localising too (the reference matches a hint against a stale scan)
     // correct
     float obs[7], cov[49];
     bool result = false;
@@ -1047,9 +1134,27 @@ void set_init_pose(double x, double y, double z, double yaw, double pitch, doubl
         g->loc->initialized = false;
     }
 }
+// SLAM::getEstimatePose (slam.cpp:137-146) -> Localization::getEstimatePose, and the answer of slam_wrapper.cpp:45-56.  The hint's rotation is
+// Rz(atan2(y1 - y0, x1 - x0)) (the project's rule: FromTwoVectors is ambiguous for an arrow along -x and NaN for one of zero length)
 py::list get_estimate_pose(double x0, double y0, double x1, double y1) {
-    (void)x0; (void)y0; (void)x1; (void)y1;
-    return py::cast(std::vector<double>{0, 0, 0, 0, 0, 0, 0});  // x, y, z, roll, pitch, -yaw, result (0 = no estimate)
+    const std::vector<double> none{0, 0, 0, 0, 0, 0, 0};  // x, y, z, roll, pitch, -yaw, result (0 = no estimate)
+    if (!g || !g->loc || !g->loc->lm || !g->loc->scan) return py::cast(none);
+    const double dx = x1 - x0, dy = y1 - y0;
+    if (!(dx * dx + dy * dy > 0.0) || !std::isfinite(x0) || !std::isfinite(y0) || !std::isfinite(dx) || !std::isfinite(dy)) return py::cast(none);
+    const double yaw0 = std::atan2(dy, dx);
+    Mat4 hint = Mat4::identity(), out = Mat4::identity();
+    hint(0, 0) = std::cos(yaw0); hint(0, 1) = -std::sin(yaw0);
+    hint(1, 0) = std::sin(yaw0); hint(1, 1) = std::cos(yaw0);
+    hint(0, 3) = x0; hint(1, 3) = y0;
+    int result = 0;
+    {
+        py::gil_scoped_release release;
+        std::lock_guard<std::mutex> lk(g->mtx);
+        result = loc_estimate_pose(*g->loc, hint, out);
+    }
+    double yaw, pitch, roll;
+    rpy_from_transform(out, yaw, pitch, roll);
+    return py::cast(std::vector<double>{out(0, 3), out(1, 3), out(2, 3), roll, pitch, -yaw, (double)result});
 }
 void set_destination(bool enable, std::string dest, int port) { (void)enable; if (g) { g->dest = dest; g->dest_port = port; } }
 // GraphSLAM::optimize(1024) and what optimization_timer_callback does with the result (hdl_graph_slam_nodelet.cpp:634-651): the estimates, trans_odom2map
@@ -1289,6 +1394,49 @@ py::dict _last_relocalization() {
     d["da"] = r.da;
     d["accepted"] = r.accepted;
     d["searches"] = g->loc->reloc_searches;
+    return d;
+}
+// test visibility: the report of the last get_estimate_pose call, and the delta of the hand-over once it has happened
+py::dict _last_estimate_pose() {
+    py::dict d;
+    if (!g || !g->loc) return d;
+    Loc::Est e;
+    {
+        std::lock_guard<std::mutex> lk(g->mtx);
+        e = g->loc->last_est;
+    }
+    auto mat = [](const double* m) {
+        py::array_t<double> a({4, 4});
+        std::memcpy(a.mutable_data(), m, 16 * sizeof(double));
+        return a;
+    };
+    const lio_estimate_report& r = e.rep;
+    d["called"] = e.called;
+    d["rc"] = e.rc;
+    d["result"] = r.result;
+    d["converged"] = (bool)r.converged;
+    d["iterations"] = r.iterations;
+    d["score"] = r.score;
+    d["pose_replaced"] = (bool)r.pose_replaced;
+    d["ids"] = std::vector<int>(r.ids, r.ids + r.n_ids);
+    d["n_target"] = r.n_target;
+    d["n_source"] = r.n_source;
+    d["z_mean_target"] = r.z_mean_target;
+    d["z_mean_source"] = r.z_mean_source;
+    d["hint"] = mat(e.hint.m);
+    d["guess"] = mat(r.guess);
+    d["out_T"] = mat(e.out.m);
+    py::dict t;
+    t["nearest_us"] = r.nearest_us; t["gather_us"] = r.gather_us; t["set_target_us"] = r.set_target_us; t["set_source_us"] = r.set_source_us;
+    t["z_source_us"] = r.z_source_us; t["align_us"] = r.align_us; t["fitness_us"] = r.fitness_us;
+    d["times"] = t;
+    d["handover"] = e.handover;
+    if (e.handover) {
+        d["delta"] = mat(e.delta.m);
+        d["delta_ran"] = e.delta_ran;
+        d["delta_converged"] = (bool)e.delta_converged;
+        d["delta_iterations"] = e.delta_iterations;
+    }
     return d;
 }
 // not in the reference's module: the pose graph over the key frames and the loops (off by default; LSD_AMD_GRAPH=1 at init_slam switches it on for
@@ -2691,6 +2839,7 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("set_loop_detection", &set_loop_detection, "loop detection over the key frames update_odom() hands out", py::arg("enable"));
     m.def("set_global_localization", &set_global_localization, "scan-context relocalisation in localisation mode", py::arg("enable"));
     m.def("_last_relocalization", &_last_relocalization);
+    m.def("_last_estimate_pose", &_last_estimate_pose);
     m.def("set_pose_graph", &set_pose_graph, "the pose graph over the key frames and the loops", py::arg("enable"));
     m.def("_push_keyframe", &_push_keyframe, "test hook: a key frame for the next update_odom()", py::arg("points"), py::arg("pose"), py::arg("stamp"), py::arg("accum_distance"));
     m.def("set_loop_config", &set_loop_config, "LoopDetector thresholds", py::arg("dict"));

@@ -34,6 +34,8 @@ SYMBOLS = [
     "lio_state_boxplus", "lio_state_boxminus",
     "lio_localmap_create", "lio_localmap_destroy", "lio_localmap_add_keyframe", "lio_localmap_num_keyframes", "lio_localmap_update",
     "lio_localmap_download",
+    "lio_localmap_nearest", "lio_localmap_gather", "lio_localmap_z_mean", "lio_localmap_download_gather", "lio_localmap_gather_device", "lio_localmap_store_frame",
+    "lio_localmap_frame", "lio_estimate_matcher_params", "lio_localmap_estimate_pose", "lio_scan_ds_device", "lio_gicp_set_target_device", "lio_gicp_set_source_device",
     "lio_cloud_create", "lio_cloud_destroy", "lio_cloud_clear", "lio_cloud_size", "lio_cloud_append_scan", "lio_cloud_append_host",
     "lio_cloud_voxel_downsample", "lio_cloud_download", "lio_cloud_scratch_bytes", "lio_cloud_last_times",
     "lio_knn_index_create", "lio_knn_index_destroy", "lio_knn_index_build", "lio_knn_index_query", "lio_knn_index_colour", "lio_knn_index_last_times",
@@ -205,6 +207,16 @@ class AlignJob(C.Structure):  # lio_align_job
                 ("evaluations", C.c_int32), ("rc", C.c_int32)]
 
 
+ESTIMATE_K = 5  # LIO_ESTIMATE_K
+
+
+class EstimateReport(C.Structure):  # lio_estimate_report
+    _fields_ = [("n_ids", C.c_int32), ("ids", C.c_int32 * ESTIMATE_K), ("n_target", C.c_uint32), ("n_source", C.c_uint32), ("converged", C.c_int32),
+                ("iterations", C.c_int32), ("result", C.c_int32), ("pose_replaced", C.c_int32), ("z_mean_target", C.c_double), ("z_mean_source", C.c_double),
+                ("guess", C.c_double * 16), ("score", C.c_double), ("nearest_us", C.c_double), ("gather_us", C.c_double), ("set_target_us", C.c_double),
+                ("set_source_us", C.c_double), ("z_source_us", C.c_double), ("align_us", C.c_double), ("fitness_us", C.c_double)]
+
+
 class NdtTimes(C.Structure):  # lio_ndt_times
     _fields_ = [("cost_us", C.c_double), ("launches", C.c_uint64), ("update_launches", C.c_uint64), ("pairs", C.c_uint64), ("source_points", C.c_uint64)]
 
@@ -334,6 +346,16 @@ def lib():
     sig("lio_localmap_num_keyframes", cint, vp)
     sig("lio_localmap_update", cint, vp, vp, f64p, dbl, dbl, dbl, flt, C.POINTER(cint), C.POINTER(u32))
     sig("lio_localmap_download", cint, vp, f32p, u32)
+    sig("lio_localmap_nearest", cint, vp, f64p, u32, i32p, f32p)
+    sig("lio_localmap_gather", cint, vp, i32p, u32, C.POINTER(u32), f64p)
+    sig("lio_localmap_z_mean", cint, vp, vp, u32, f64p)
+    sig("lio_localmap_download_gather", cint, vp, f32p, u32)
+    sig("lio_localmap_gather_device", vp, vp, C.POINTER(u32))
+    sig("lio_localmap_store_frame", cint, vp, cint, vp, u32)
+    sig("lio_localmap_frame", vp, vp, cint, C.POINTER(u32))
+    sig("lio_estimate_matcher_params", None, C.POINTER(NdtParams))
+    sig("lio_localmap_estimate_pose", cint, vp, vp, vp, u32, f64p, C.POINTER(EstimateReport), f64p)
+    sig("lio_scan_ds_device", vp, vp, C.POINTER(u32))
     sig("lio_cloud_create", vp, cint, u64)
     sig("lio_cloud_destroy", None, vp)
     sig("lio_cloud_clear", cint, vp)
@@ -447,6 +469,8 @@ def lib():
     sig("lio_gicp_destroy", None, vp)
     sig("lio_gicp_set_target", cint, vp, f32p, u32)
     sig("lio_gicp_set_source", cint, vp, f32p, u32)
+    sig("lio_gicp_set_target_device", cint, vp, vp, u32)
+    sig("lio_gicp_set_source_device", cint, vp, vp, u32)
     sig("lio_gicp_set_voxel_mode", cint, vp, C.c_double, cint)
     sig("lio_gicp_voxel_at", cint, vp, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double))
     sig("lio_gicp_download", cint, vp, cint, f32p, f64p, u32)

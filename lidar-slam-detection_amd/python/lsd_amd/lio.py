@@ -619,6 +619,13 @@ class Gicp:
         p = f32(pts).reshape(-1, 4)
         check(lib().lio_gicp_set_source(self.h, ptr(p, C.c_float), len(p)), "gicp set_source")
 
+    def set_target_device(self, d_ptr, n):
+        """a cloud that lies in HBM (d_ptr: device address of n float4) through set_target's path"""
+        check(lib().lio_gicp_set_target_device(self.h, C.c_void_p(d_ptr), int(n)), "gicp set_target_device")
+
+    def set_source_device(self, d_ptr, n):
+        check(lib().lio_gicp_set_source_device(self.h, C.c_void_p(d_ptr), int(n)), "gicp set_source_device")
+
     def set_voxel_mode(self, voxel_resolution=1.0, search_method=1):
         """fast_gicp::FastVGICP: Gaussian-voxel target of `voxel_resolution` (0 = back to the kd-tree form), DIRECT1 / 7 / 27 lookup"""
         check(lib().lio_gicp_set_voxel_mode(self.h, float(voxel_resolution), int(search_method)), "gicp set_voxel_mode")
@@ -2289,3 +2296,53 @@ class LocalMap:
         out = np.zeros((self._cap, 4), np.float32)
         n = check(lib().lio_localmap_download(self.h, ptr(out, C.c_float), self._cap))
         return out[:n].copy()
+
+    # ---- the operator's pose hint (GlobalLocalization::getEstimatePose) ----
+    def nearest(self, xy, k=5):
+        """(ids, d2) of the min(k, frames) key frames nearest (x, y), rising (d2, id); d2 in f32 as the C entry computes it"""
+        x = f64(xy)
+        ids, d2 = np.zeros(max(int(k), 1), np.int32), np.zeros(max(int(k), 1), np.float32)
+        n = check(lib().lio_localmap_nearest(self.h, ptr(x, C.c_double), int(k), ptr(ids, C.c_int32), ptr(d2, C.c_float)), "localmap nearest")
+        return ids[:n].copy(), d2[:n].copy()
+
+    def gather(self, ids):
+        """the named key frames back to back in a device buffer -> (points, mean z by the chunked sum)"""
+        i = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        n, z = C.c_uint32(0), C.c_double(0)
+        check(lib().lio_localmap_gather(self.h, ptr(i, C.c_int32), len(i), C.byref(n), C.byref(z)), "localmap gather")
+        return n.value, z.value
+
+    def gather_device(self):
+        """(device address, points) of the last gather"""
+        n = C.c_uint32(0)
+        p = lib().lio_localmap_gather_device(self.h, C.byref(n))
+        return p, n.value
+
+    def download_gather(self):
+        p, n = self.gather_device()
+        out = np.zeros((max(n, 1), 4), np.float32)
+        m = check(lib().lio_localmap_download_gather(self.h, ptr(out, C.c_float), len(out)), "localmap download_gather")
+        return out[:m].copy()
+
+    def z_mean(self, d_ptr, n):
+        z = C.c_double(0)
+        check(lib().lio_localmap_z_mean(self.h, C.c_void_p(d_ptr), int(n), C.byref(z)), "localmap z_mean")
+        return z.value
+
+    def store_frame(self, slot, d_ptr, n):
+        check(lib().lio_localmap_store_frame(self.h, int(slot), C.c_void_p(d_ptr), int(n)), "localmap store_frame")
+
+    def frame(self, slot):
+        n = C.c_uint32(0)
+        p = lib().lio_localmap_frame(self.h, int(slot), C.byref(n))
+        return p, n.value
+
+    def estimate_pose(self, gicp, d_source, n_source, hint):
+        """lio_localmap_estimate_pose -> (out_T 4 x 4, report dict)"""
+        h, out, rep = f64(hint).reshape(4, 4), np.zeros((4, 4)), capi.EstimateReport()
+        check(lib().lio_localmap_estimate_pose(self.h, gicp.h, C.c_void_p(d_source), int(n_source), ptr(h, C.c_double), C.byref(rep), ptr(out, C.c_double)),
+              "localmap estimate_pose")
+        r = {k: getattr(rep, k) for k, _ in capi.EstimateReport._fields_ if k not in ("ids", "guess")}
+        r["ids"] = [int(v) for v in rep.ids[:rep.n_ids]]
+        r["guess"] = np.array(rep.guess).reshape(4, 4)
+        return out, r
