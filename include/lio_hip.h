@@ -79,8 +79,10 @@ int lio_device_count(void);
  * 19 = lio_gicp_set_target_device / _set_source_device (a cloud in HBM through the host entry's path), lio_scan_ds_device, lio_localmap_nearest /
  *      _gather / _z_mean / _download_gather / _gather_device / _store_frame / _frame / _estimate_pose, lio_estimate_matcher_params (the operator's
  *      pose hint, GlobalLocalization::getEstimatePose, on the device).  lio_gicp_set_target / _set_source now leave the cloud in an internal
- *      order that is a function of the cloud (it was the grid's arrival order: lio_gicp_download differed from call to call, T in its last bits). */
-#define LIO_ABI_VERSION 19
+ *      order that is a function of the cloud (it was the grid's arrival order: lio_gicp_download differed from call to call, T in its last bits).
+ * 20 = lio_render_* (the road-surface colour map of slam/localization/map_render: voxels of floor points painted from camera images -- insert,
+ *      projection, z-buffer, depth continuity, bilinear sample, running blend, export). */
+#define LIO_ABI_VERSION 20
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1584,6 +1586,92 @@ int lio_graph_prior_error(const double X16[16], int type, const double m4[4], co
 /* manifold helpers exposed for known-answer tests (mtk SO3/S2 boxplus/boxminus, SOn.hpp:233-245, S2.hpp:136-167) */
 void lio_state_boxplus(const double s26[26], const double d23[23], double out26[26]);
 void lio_state_boxminus(const double a26[26], const double b26[26], double d23[23]);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * Colour map on the device (csrc/render.hip): MapRender of slam/localization/map_render/ -- map_render.cpp (MR), render_common.h (RC),
+ * image_render.hpp's ImageRenderCpu (IR), camera_model.{h,cpp} (CM) -- and the same painter behind graph_utils.cpp:503-622.  PCL, OpenCV and
+ * Boost are restated from their published behaviour; where the reference has no order of its own (it iterates hash containers of pointers)
+ * the rule is THE PROJECT'S and is marked so.  NULL from lio_render_create without a device: there is no CPU fallback.
+ * Constants (RC:10-15): point resolution 0.02, voxel 0.2, their inverses 1.0 / 0.02 and 1.0 / 0.2 in f64, depth 2.0 to 80.0.
+ *   gate     (render, MR:197-211) nothing happens while the painter is inactive, nor while the translation of last_pose^-1 pose is shorter
+ *            than 0.1 m; last_pose starts as identity (a first frame near the origin is skipped) and is updated BEFORE the ground test.
+ *            Then detect_ground (MR:81-134): lio_ground preset 0 (clip 1.5 / 1.5, normals 20 deg, 1024 points, floor 10 deg) with
+ *            distance_threshold = 0.2 (MR:101) and the seeded draws of lio_ground; no floor: nothing else happens.  On success the frame IS
+ *            REPLACED by the floor inliers (MR:129-132); only they are inserted and painted.  PROJECT: poses are taken as rigid, the inverse
+ *            of (R, t) is (R^T, -(R^T t)), every sum of three products left to right in f64.
+ *   world    pose (f64) applied to the f32 points and rounded to f32 by the rule of lio_cloud_append_host (MR:215).
+ *   insert   (updateMap, MR:165-195) in f64 from the f32 world point: box = round(x * (1 / 0.2)) half away from zero; voxel centre
+ *            c = int64((box * 0.2) * (1 / 0.02)) truncating; per axis o = int64(x * (1 / 0.02)) - c + 5; key = ox * 100 + oy * 10 + oz.  A
+ *            point is stored only if its voxel does not hold that key yet.  (The key is kept as it is: it is not injective over offsets 0 .. 10,
+ *            but x * 5 and x * 50 are exact in f64 for an f32 x, so the offsets of one voxel are ten consecutive values per axis, 0 .. 9 or
+ *            1 .. 10, and over those distinct cells never share a key.)  Of several points of
+ *            one frame with the same (voxel, key) the one earliest in the input is stored.  Every voxel touched by the frame, by stored
+ *            and rejected points alike, is a hit: hits + 1 per rendered frame, before any image is looked at, also without images.
+ *            PROJECT: voxels are numbered in order of the input index that created them, points get serial numbers in input order; a
+ *            point that is not finite or whose box leaves +-2^20 is dropped.
+ *   camera   (CameraModel, ImageRender::setPose, IR:13-38, CM:3-26) K is read as f32 and widened; static_trans = camera_extrinsic *
+ *            lidar_static^-1 (setParameter, MR:152-157), ext = static_trans^-1; R_w2c = R_pose R_ext, t_w2c = R_pose t_ext + t_pose; the
+ *            camera-from-world map is R = R_w2c^T, t = -(R t_w2c).  PROJECT: pt_cam = R p + t with R as a matrix (the reference goes through
+ *            an Eigen quaternion), every sum of three products left to right in f64, no fusion.  project3DPoints (CM:39-47) fails if
+ *            z < 0.001; u = x fx / z + cx, v = y fy / z + cy.  point2DAvailable (CM:49-57): u >= 0.005 cols + 1 && ceil(u) < (1 - 0.005) cols,
+ *            the same for v with rows.
+ *   voxel    (MR:251-297, per image and hit voxel) the centre c * 0.02 must project, be available and have 2.0 < z < 80.0, else the voxel
+ *            contributes nothing to this image.  Then every stored point of the voxel (of earlier frames too) is projected; one that does
+ *            not project or is not available is skipped.  The bounding box of (u, v) starts at the centre's and grows over the kept points;
+ *            max_u - min_u <= 10 && max_v - min_v <= 10 masks the whole voxel for this image.
+ *   z-buffer (MR:299-316) pixel (round(u), round(v)) half away from zero; the winner of a pixel is the kept, unmasked point with the smallest
+ *            (float)z.  PROJECT: ties go to the smaller serial number (a 64-bit atomicMin over (f32 depth bits, serial)).
+ *   window   (checkDepthContinuous, IR:66-90, the f64 variant: the CUDA one narrows u and v to f32 first) for each winner the 9 x 9 cells
+ *            ((int)(u + i), (int)(v + j)), i, j = -4 .. 4 (truncation here, where the z-buffer rounds); cells outside the image or without
+ *            an owner are skipped; min / max are f32 and start at (float)z; the winner is valid iff max - min <= 2.0.
+ *   blend    (update_voxel_rgb, RC:192-217, for every valid winner; images in ascending name order, each finished before the next)
+ *            score = (float)(1 - |u - cols / 2| / (cols / 2)) (MR:288); skip if score < 0.1; skip if z > 1.5 m_depth (m_depth f32, starts at
+ *            100, compared in f64); if z < m_depth, m_depth = (float)z; rgb[k] = (float)((rgb[k] s1 + c_k s2) / (s1 + s2)) with s1 = m_score
+ *            and s2 = score widened to f64 and c = (R, G, B) of the BGR sample; m_score = max(s1, s2).  Tracks and COLMAP are out of scope.
+ *   sample   (getSubPixel<cv::Vec3b>(image, v, u), CM's header :22-42, OpenCV's Matx operators) weights (1 - fr)(1 - fc), fr (1 - fc),
+ *            (1 - fr) fc, fr fc for (floor, floor), (ceil row, floor col), (floor row, ceil col), (ceil, ceil), ceil = floor + 1; each term
+ *            w * pixel per channel rounded to u8 on its own (half to even, saturated), the four added left to right with saturation.  A tap
+ *            of weight zero is not read and contributes 0 (the reference reads past the edge of images under 200 px there).  Images are
+ *            rows x cols x 3 u8, BGR; imageCvtColor's conversions are out of scope.
+ *   export   (getColorMap, MR:327-353) a point is written when its voxel has hits > 2 and its own score >= 0.1; PROJECT: in ascending voxel
+ *            number, then serial number; x, y, z as stored, each channel truncated to u8 and packed r << 16 | g << 8 | b, the word
+ *            reinterpreted as f32 (pointcloud_to_numpy(PointCloudRGB), py_utils.cpp:118-129).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_render lio_render;
+typedef struct lio_render_image {
+    int32_t camera;      /* index into the cameras of lio_render_set_cameras */
+    int32_t rows, cols;
+    int32_t reserved;
+    const uint8_t* bgr;  /* rows x cols x 3, host */
+    double pose[16];     /* row-major, the pose at the image's stamp */
+} lio_render_image;
+#define LIO_RENDER_SKIPPED 0  /* inactive, or moved less than 0.1 m */
+#define LIO_RENDER_NO_FLOOR 1 /* the ground test found no floor (last_pose has moved) */
+#define LIO_RENDER_DONE 2     /* inserted and painted */
+/* the map holds at most max_voxels voxels and max_points points (4 max_points + 8 max_voxels < 2^32) */
+lio_render* lio_render_create(int device, uint64_t max_voxels, uint64_t max_points);
+void lio_render_destroy(lio_render*);
+/* drops the map (MapRender::clear); cameras, the active flag and last_pose stay */
+int lio_render_clear(lio_render*);
+/* n cameras: names (distinct), intrinsics n x (fx, fy, cx, cy), extrinsics n x 16 row-major, lidar_static 16 or NULL (identity) */
+int lio_render_set_cameras(lio_render*, int n, const char* const* names, const double* intrinsics, const double* extrinsics, const double* lidar_static);
+int lio_render_set_active(lio_render*, int active);
+/* render(pose, frame, images) over n host points (x, y, z, intensity): LIO_RENDER_* or an error.  use_ground = 0 takes the points as they are
+ * (no ground test).  At most one image per camera; they are painted in ascending camera name.  Capacity is checked before anything is
+ * committed: a frame that does not fit returns LIO_E_CAPACITY and leaves the map unchanged (last_pose has moved). */
+int lio_render_frame(lio_render*, const float* xyzi, uint64_t n, const double pose[16], int use_ground, uint32_t seed, const lio_render_image* images,
+                     int n_images);
+int lio_render_size(lio_render*, uint64_t* n_voxels, uint64_t* n_points);
+/* the export above: n x 4 f32; returns n, or -n when cap (points) is too small */
+int64_t lio_render_download(lio_render*, float* xyzrgb, uint64_t cap);
+/* read-backs for tests, in voxel number / serial number order; any array may be NULL; the count, or -(count) when cap is too small.
+ * voxels: box triple, hits, stored points; points: position, voxel number, rgb (f32), m_score, m_depth;
+ * last_image: of the last image of the last rendered frame -- depth buffer (-1: no owner), owner serial (-1) and valid flag per pixel */
+int64_t lio_render_download_voxels(lio_render*, int32_t* box3, uint32_t* hits, uint32_t* counts, uint64_t cap);
+int64_t lio_render_download_points(lio_render*, float* xyz, uint32_t* voxel, float* rgb, float* score, float* depth, uint64_t cap);
+int64_t lio_render_download_last_image(lio_render*, float* depth, int32_t* owner, uint8_t* valid, uint64_t cap, int* rows, int* cols);
+/* device time (HIP events) of the last rendered frame: insert chain, all images, finish + read-back */
+int lio_render_last_times(lio_render*, double* insert_us, double* image_us, double* finish_us);
 
 #ifdef __cplusplus
 }

@@ -467,6 +467,12 @@ int64_t download_u32(lio_ground* g, const uint32_t* src, uint64_t n, uint32_t* o
 
 }  // namespace
 
+// the inlier cloud of the last call where it lies (render.hip paints it without a trip to the host); the detector's stream is idle
+const float4* lio::ground::inliers_view(lio_ground* g, uint32_t* n) {
+    *n = g->n_inliers;
+    return g->ipt;
+}
+
 extern "C" {
 
 void lio_ground_default_params(lio_ground_params* p, int preset) {

@@ -264,6 +264,9 @@ struct lio_map {
 
 namespace lio {
 struct KernelTimer;  // capi.hip
+namespace ground {
+const float4* inliers_view(lio_ground* g, uint32_t* n);  // ground.hip: the device inliers of the last detect call
+}
 }
 struct lio_scan {
     lio::KernelTimer* kt;

@@ -246,6 +246,13 @@ struct Slam {
     std::vector<uint8_t> graph_has_gnss;  // keyframe->utm_coord is set
     struct InjectedKeyFrame { std::vector<float> pts; Mat4 pose; uint64_t stamp; double accum; };
     std::deque<InjectedKeyFrame> injected;  // test visibility: key frames handed to update_odom() without the front end (_push_keyframe)
+    // the colour map of the localisation mode (MapLoader::mRender, map_render.cpp; lio_render_*): cameras from set_camera_param, switched by
+    // set_map_colouration, painted by process() after a stable localisation; guarded by mtx
+    struct CamCfg { std::string name; double K[4]; Mat4 ext; };
+    std::vector<CamCfg> cameras;
+    lio_render* painter = nullptr;
+    bool painter_stale = true;            // the cameras or the static transform changed since the painter got them
+    uint32_t colour_seed = 0;             // of the ground test's draws (lio_ground)
 };
 std::unique_ptr<Slam> g;  // one global instance per process, like the reference's slam_ptr (slam_wrapper.cpp:4)
 
@@ -814,6 +821,7 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
 void set_ins_external_param(double x, double y, double z, double yaw, double pitch, double roll) {
     require((bool)g, "init_slam first");
     g->T_static = transform_from_rpyt(x, y, z, yaw, pitch, roll);
+    g->painter_stale = true;
 }
 void set_imu_external_param(double x, double y, double z, double yaw, double pitch, double roll) {
     require((bool)g, "init_slam first");
@@ -848,13 +856,129 @@ void deinit_slam() {
     if (g->loop) lio_loop_destroy(g->loop);
     if (g->graph) lio_graph_destroy(g->graph);
     if (g->floor_ground) lio_ground_destroy(g->floor_ground);
+    if (g->painter) lio_render_destroy(g->painter);
     g->loc.reset(nullptr);
     g.reset(nullptr);
 }
 
+
+// ---- the colour map (slam/localization/map_render; csrc/render.hip) ---------------------------------------------------------------------------
+using CamCfg = Slam::CamCfg;
+constexpr uint64_t kColourVoxels = 1ull << 20, kColourPoints = 1ull << 25;  // 0.2 m voxels and 0.02 m cells: about 3.5 GB of HBM
+
+// pylist_to_camera_config (py_utils.cpp:329-358): K entries cast to float, the extrinsic through getTransformFromRPYT(e0, e1, e2, e5, e4, e3)
+std::vector<CamCfg> camera_config(py::list& cameras) {
+    std::vector<CamCfg> out;
+    for (py::handle obj : cameras) {
+        py::dict cam = obj.cast<py::dict>();
+        CamCfg c;
+        c.name = py::cast<std::string>(cam["name"]);
+        py::list in = py::cast<py::list>(cam["intrinsic_parameters"]), ex = py::cast<py::list>(cam["extrinsic_parameters"]);
+        if (py::len(in) < 4 || py::len(ex) < 6) throw std::invalid_argument("slam_wrapper: camera '" + c.name + "': 4 intrinsic and 6 extrinsic parameters are needed");
+        c.K[0] = (double)py::cast<float>(in[0]);  // fx
+        c.K[1] = (double)py::cast<float>(in[1]);  // fy
+        c.K[2] = (double)py::cast<float>(in[2]);  // cx
+        c.K[3] = (double)py::cast<float>(in[3]);  // cy
+        c.ext = transform_from_rpyt(py::cast<double>(ex[0]), py::cast<double>(ex[1]), py::cast<double>(ex[2]), py::cast<double>(ex[5]), py::cast<double>(ex[4]),
+                                    py::cast<double>(ex[3]));
+        bool seen = false;
+        for (CamCfg& o : out)
+            if (o.name == c.name) { o = c; seen = true; }  // (a std::map in the reference: the later entry of a name wins)
+        if (!seen) out.push_back(c);
+    }
+    return out;
+}
+
+// a fresh painter with these cameras (MapRender::setParameter); throws without a device
+lio_render* make_painter(const std::vector<CamCfg>& cams, const Mat4& lidar_static, const char* what) {
+    lio_render* r = lio_render_create(0, kColourVoxels, kColourPoints);
+    if (!r) throw std::runtime_error(std::string("slam_wrapper: ") + what + ": the colour map needs a HIP device (there is no CPU fallback): " + lio_last_error());
+    std::vector<const char*> names;
+    std::vector<double> in, ex;
+    for (const CamCfg& c : cams) {
+        names.push_back(c.name.c_str());
+        in.insert(in.end(), c.K, c.K + 4);
+        ex.insert(ex.end(), c.ext.m, c.ext.m + 16);
+    }
+    if (lio_render_set_cameras(r, (int)cams.size(), names.data(), in.data(), ex.data(), lidar_static.m) != LIO_OK) {
+        lio_render_destroy(r);
+        require(false, what);
+    }
+    return r;
+}
+
+// pydict_to_image (py_utils.cpp:198-212) for the cameras that are configured: BGR rows x cols x 3 u8 and the stamp of image_param[name].  A 2-D
+// (I420) image raises ValueError: imageCvtColor's conversion is out of scope.
+struct FrameImage { int camera; uint64_t stamp; int rows, cols; std::vector<uint8_t> bgr; Mat4 pose; };
+std::vector<FrameImage> frame_images(py::dict& image_dict, py::dict& image_param, const std::vector<CamCfg>& cams, const char* what) {
+    std::vector<FrameImage> out;
+    for (auto item : image_dict) {
+        const std::string name = py::cast<std::string>(item.first);
+        py::array ar = py::cast<py::array>(item.second);
+        if (ar.ndim() != 3 || ar.shape(2) != 3)
+            throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": image '" + name + "' must be rows x cols x 3 (BGR); an I420 image is not converted");
+        int cam = -1;
+        for (size_t k = 0; k < cams.size(); k++)
+            if (cams[k].name == name) cam = (int)k;
+        if (cam < 0 || !image_param.contains(name.c_str())) continue;  // (no camera of that name: nothing to paint with)
+        auto a = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(ar);
+        if (!a) throw std::invalid_argument(std::string("slam_wrapper: ") + what + ": image '" + name + "' is not a uint8 array");
+        FrameImage im;
+        im.camera = cam;
+        im.stamp = py::cast<uint64_t>(py::cast<py::dict>(image_param[name.c_str()])["timestamp"]);
+        im.rows = (int)a.shape(0);
+        im.cols = (int)a.shape(1);
+        im.bgr.assign(a.data(), a.data() + (size_t)a.size());
+        im.pose = Mat4::identity();
+        out.push_back(std::move(im));
+    }
+    return out;
+}
+
+// MapRender::render over the images that have a pose; LIO_RENDER_* or a negative error
+int paint_frame(lio_render* r, const float* xyzi, size_t n, const Mat4& pose, uint32_t seed, const std::vector<FrameImage>& imgs) {
+    std::vector<lio_render_image> li(imgs.size());
+    for (size_t k = 0; k < imgs.size(); k++) {
+        li[k].camera = imgs[k].camera;
+        li[k].rows = imgs[k].rows;
+        li[k].cols = imgs[k].cols;
+        li[k].reserved = 0;
+        li[k].bgr = imgs[k].bgr.data();
+        std::memcpy(li[k].pose, imgs[k].pose.m, sizeof(li[k].pose));
+    }
+    return lio_render_frame(r, xyzi, n, pose.m, 1, seed, li.data(), (int)li.size());
+}
+
+// getColorMap as pointcloud_to_numpy(PointCloudRGB) packs it (py_utils.cpp:118-129): N x 4; nothing painted: the empty array this module has
+// always returned
+std::vector<float> colour_map_points(lio_render* r) {
+    std::vector<float> out;
+    if (!r) return out;
+    const int64_t n = -lio_render_download(r, nullptr, 0);
+    if (n <= 0) return out;
+    out.resize(4 * (size_t)n);
+    require(lio_render_download(r, out.data(), (uint64_t)n) == n, "get_color_map: download failed");
+    return out;
+}
+
+// the live painter as the cameras and the static transform stand (Localization::init: mMap->setParameter(mStaticTrans, mCameraParams))
+lio_render* live_painter(Slam* s) {
+    if (s->painter && !s->painter_stale) return s->painter;
+    if (s->painter) lio_render_destroy(s->painter);
+    s->painter = nullptr;
+    s->painter = make_painter(s->cameras, s->T_static, "process");
+    lio_render_set_active(s->painter, 1);
+    s->painter_stale = false;
+    return s->painter;
+}
+
 // SLAM::run, localisation branch (slam.cpp:273-367) over Localization::feedImuData / feedPointData / getPose
-py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, py::dict& rtk_dict, py::array_t<double>& imu_list, uint64_t timestamp) {
+py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, py::dict& image_dict, py::dict& image_param, py::dict& rtk_dict,
+                              py::array_t<double>& imu_list, uint64_t timestamp) {
     Loc& L = *s->loc;
+    // with colouration off the images are not looked at
+    std::vector<FrameImage> images;
+    if (s->colouration && !s->cameras.empty()) images = frame_images(image_dict, image_param, s->cameras, "process");
     int status = 0;
     if (rtk_dict.contains("Status")) status = py::cast<int>(rtk_dict["Status"]);
     std::string name = s->lidar;
@@ -903,6 +1027,18 @@ py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, 
         located = loc_localize(s, n, header_stamp, out_pose);
         if (!located) out_pose = L.last_odom;
         inited = L.initialized && L.age >= 10;  // Localization::isInited: mInitialized && isStable()
+        // Localization::feedPointData, localization.cpp:237-244: a located frame of a stable localisation is painted (renderMap, :22-30: the
+        // images whose stamp getTimedPose answers), with the frame as the localiser left it (undistorted, INS frame)
+        if (located && inited && s->colouration && !s->cameras.empty()) {
+            lio_render* r = live_painter(s);
+            std::vector<FrameImage> posed;
+            for (FrameImage& im : images)
+                if (loc_timed_pose(L, im.stamp, im.pose)) posed.push_back(std::move(im));
+            std::vector<float> frame(4 * (size_t)n + 4);
+            const int m = lio_scan_download_raw(L.scan, frame.data(), n);
+            // (a frame that does not fit leaves the map as it is: the drive goes on without it)
+            if (m > 0) (void)paint_frame(r, frame.data(), (size_t)m, out_pose, s->colour_seed, posed);
+        }
     }
     double heading, pitch, roll;
     rpy_from_transform(out_pose, heading, pitch, roll);
@@ -936,10 +1072,10 @@ py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, 
 
 py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, py::dict& image_stream_dict, py::dict& image_param,
                  py::dict& rtk_dict, py::array_t<double>& imu_list, uint64_t timestamp) {
-    (void)image_dict; (void)image_stream_dict; (void)image_param;
+    (void)image_stream_dict;
     require(g && (g->engine || (g->loc && g->loc->scan)), "init_slam / setup_slam first");
     Slam* s = g.get();
-    if (s->loc) return process_localization(s, points, points_attr, rtk_dict, imu_list, timestamp);
+    if (s->loc) return process_localization(s, points, points_attr, image_dict, image_param, rtk_dict, imu_list, timestamp);
     // pydict_to_rtk: only the fields SLAM::run copies into the pose in mapping mode (slam.cpp:344-348)
     double lat = 0, lon = 0, alt = 0;
     int status = 0;
@@ -1104,7 +1240,14 @@ py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, 
 }
 
 // ---- off the hot path: type-correct minimal implementations -------------------------------------------
-void set_camera_param(py::list& cameras) { (void)cameras; }
+// SLAM::setCameraParameter: kept for the colour map (the painter takes them with the static transform at its next frame)
+void set_camera_param(py::list& cameras) {
+    if (!g) return;
+    std::vector<CamCfg> cams = camera_config(cameras);
+    std::lock_guard<std::mutex> lk(g->mtx);
+    g->cameras = std::move(cams);
+    g->painter_stale = true;
+}
 // pydict_to_ins_config (py_utils.cpp:295-317): ins_normal / ins_float / ins_fix entries with use, status, stable_time, precision
 void set_ins_config(py::dict& dict) {
     if (!g) return;
@@ -1922,7 +2065,18 @@ py::dict get_graph_map() {
     d["stamps"] = stamps;
     return d;
 }
-py::array_t<float> get_color_map() { return py::array_t<float>(std::vector<py::ssize_t>{0, 6}); }
+// get_color_map (slam_wrapper.cpp -> SLAM::getColorMap -> MapRender::getColorMap): N x 4 (x, y, z, r << 16 | g << 8 | b as f32 bits)
+py::array_t<float> get_color_map() {
+    std::vector<float> pts;
+    if (g) {
+        std::lock_guard<std::mutex> lk(g->mtx);
+        pts = colour_map_points(g->painter);
+    }
+    if (pts.empty()) return py::array_t<float>(std::vector<py::ssize_t>{0, 6});
+    py::array_t<float> a({(py::ssize_t)(pts.size() / 4), (py::ssize_t)4});
+    std::memcpy(a.mutable_data(), pts.data(), pts.size() * sizeof(float));
+    return a;
+}
 // the graph's live edges (graph_get_edges, hdl_graph_slam_nodelet.cpp:842-860; vector_to_pydict, py_utils.cpp:29-48): str(id) -> [prev, next]; {} without a graph
 namespace {
 struct GraphEdges { std::vector<int32_t> from, to, id; std::vector<uint8_t> fixed; };
@@ -2032,7 +2186,13 @@ void set_mapping_ground_constraint(bool enable) {
 }
 bool get_mapping_ground_constraint() { return g ? g->ground_constraint : false; }
 void set_mapping_constraint(bool loop_closure, bool gravity_constraint) { if (g) { g->loop_closure = loop_closure; g->gravity_constraint = gravity_constraint; } }
-void set_map_colouration(bool enable) { if (g) g->colouration = enable; }
+// Localization::setMapRender -> MapRender::setActive
+void set_map_colouration(bool enable) {
+    if (!g) return;
+    std::lock_guard<std::mutex> lk(g->mtx);
+    g->colouration = enable;
+    if (g->painter) lio_render_set_active(g->painter, enable ? 1 : 0);
+}
 void del_graph_vertex(int id) { (void)id; }
 // graph_add_edge (hdl_graph_slam_nodelet.cpp:893-912) with score <= 0: calc_information_matrix(prev, next, relative) -- taken on the bank's frames
 // prev_id and next_id, which hold the two clouds -- and Huber 1.0; nothing without a graph
@@ -2331,7 +2491,7 @@ void set_export_map_config(double z_min, double z_max, std::string color) {
     g_export.color = color;
 }
 void export_points(py::array_t<float>& points_input, py::array_t<float>& odom_input) {
-    if (g_export.color == "rgb") return;  // the colour map is out of scope (get_color_map is empty)
+    if (g_export.color == "rgb") return;  // (graph_utils.cpp:169: the colour map comes from the painter, not from the exported frames)
     auto od = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(odom_input);
     if (!od || od.size() != 16) throw std::invalid_argument("slam_wrapper: export_points: odom must be 4 x 4");
     Mat4 T;
@@ -2339,8 +2499,35 @@ void export_points(py::array_t<float>& points_input, py::array_t<float>& odom_in
     g_export.points.push_back(xyzi_of(points_input, "export_points"));
     g_export.odom.push_back(T);
 }
+// savePCDFileBinary of a PointXYZRGB cloud: FIELDS x y z rgb, the colour word with PCL's alpha of 255 on top
+bool write_pcd_rgb(const std::string& path, const float* xyzrgb, size_t n) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) return false;
+    f << "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\nWIDTH " << n
+      << "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " << n << "\nDATA binary\n";
+    std::vector<float> rows(xyzrgb, xyzrgb + 4 * n);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t w;
+        std::memcpy(&w, &rows[4 * i + 3], 4);
+        w |= 0xFF000000u;
+        std::memcpy(&rows[4 * i + 3], &w, 4);
+    }
+    f.write(reinterpret_cast<const char*>(rows.data()), (std::streamsize)(n * 16));
+    return (bool)f;
+}
 void dump_map_points(std::string file) {
-    if (g_export.color == "rgb") return;  // getColorMap: nothing without the colour map, and an empty cloud is not written
+    if (g_export.color == "rgb") {  // graph_utils.cpp:189-203: the colour map between z_min and z_max; an empty cloud is not written
+        std::vector<float> pts, kept;
+        if (g) {
+            std::lock_guard<std::mutex> lk(g->mtx);
+            pts = colour_map_points(g->painter);
+        }
+        for (size_t i = 0; i + 3 < pts.size(); i += 4)
+            if ((double)pts[i + 2] >= g_export.z_min && (double)pts[i + 2] <= g_export.z_max) kept.insert(kept.end(), pts.begin() + i, pts.begin() + i + 4);
+        if (kept.empty()) return;
+        require(write_pcd_rgb(file, kept.data(), kept.size() / 4), "dump_map_points: cannot write the file");
+        return;
+    }
     uint64_t total = 0;
     for (const auto& p : g_export.points) total += p.size() / 4;
     if (total == 0) return;
@@ -2676,12 +2863,203 @@ void texture_mesh(std::string mesh_path, std::string cloud_path, std::string out
     const std::string out = output_path + "/texture_mesh.ply";
     if (!write_mesh_ply(out, verts.data(), colour.data(), nv, faces.data(), face_size.data(), face_size.size())) refuse(who, "cannot write '" + out + "'");
 }
-void set_colouration_config(py::list& cameras) { (void)cameras; }
-void set_map_odometrys(py::array_t<double>& poses) { (void)poses; }
-void colouration_frame(std::string lidar_name, py::dict& points, py::dict& points_attr, py::dict& image_dict, py::dict& image_stream_dict, py::dict& image_param) {
-    (void)lidar_name; (void)points; (void)points_attr; (void)image_dict; (void)image_stream_dict; (void)image_param;
+// ---- the offline painter (graph_utils.cpp:503-622): set_colouration_config, set_map_odometrys, colouration_frame, save_render_cloud ----------
+struct Colouration {
+    lio_render* map = nullptr;
+    std::vector<CamCfg> cameras;
+    int odometry_idx = 0;
+    std::vector<TumPose> odometrys;
+    uint32_t seed = 0;
+    // test visibility: what the last colouration_frame handed to the painter
+    int last_outcome = -1;
+    std::vector<float> last_frame;
+    Mat4 last_pose = Mat4::identity();
+    std::vector<std::pair<std::string, Mat4>> last_images;
+};
+Colouration g_col;
+
+// Eigen's Quaterniond(Matrix3d) (w, x, y, z), q * v, q1 * q2 and toRotationMatrix
+void quat_of(const Mat4& T, double q[4]) {
+    const double t = T(0, 0) + T(1, 1) + T(2, 2);
+    if (t > 0) {
+        const double r = std::sqrt(t + 1.0), k = 0.5 / r;
+        q[0] = 0.5 * r; q[1] = (T(2, 1) - T(1, 2)) * k; q[2] = (T(0, 2) - T(2, 0)) * k; q[3] = (T(1, 0) - T(0, 1)) * k;
+        return;
+    }
+    int i = 0;
+    if (T(1, 1) > T(0, 0)) i = 1;
+    if (T(2, 2) > T(i, i)) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    const double r = std::sqrt(T(i, i) - T(j, j) - T(k, k) + 1.0), kk = 0.5 / r;
+    q[1 + i] = 0.5 * r;
+    q[0] = (T(k, j) - T(j, k)) * kk; q[1 + j] = (T(j, i) + T(i, j)) * kk; q[1 + k] = (T(k, i) + T(i, k)) * kk;
 }
-void save_render_cloud(std::string file) { (void)file; }
+void quat_rotate(const double q[4], const double v[3], double o[3]) {
+    const double uv[3] = {2 * (q[2] * v[2] - q[3] * v[1]), 2 * (q[3] * v[0] - q[1] * v[2]), 2 * (q[1] * v[1] - q[2] * v[0])};
+    o[0] = v[0] + q[0] * uv[0] + (q[2] * uv[2] - q[3] * uv[1]);
+    o[1] = v[1] + q[0] * uv[1] + (q[3] * uv[0] - q[1] * uv[2]);
+    o[2] = v[2] + q[0] * uv[2] + (q[1] * uv[1] - q[2] * uv[0]);
+}
+void quat_mul(const double a[4], const double b[4], double o[4]) {
+    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
+    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
+    o[2] = a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3];
+    o[3] = a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1];
+}
+// interpolateTransform (slam_utils.cpp:126-161): the pose a fraction `ratio` of the way from pre to next, along the translation and the
+// angle-axis of pre^-1 next
+Mat4 interpolate_transform(const Mat4& pre, const Mat4& next, double ratio) {
+    double q[4], qi[4], qn[4], dq[4];
+    quat_of(pre, q);
+    qi[0] = q[0]; qi[1] = -q[1]; qi[2] = -q[2]; qi[3] = -q[3];
+    quat_of(next, qn);
+    const double t[3] = {pre(0, 3), pre(1, 3), pre(2, 3)}, tn[3] = {next(0, 3), next(1, 3), next(2, 3)};
+    double a[3], b[3];
+    quat_rotate(qi, t, a);
+    quat_rotate(qi, tn, b);
+    const double dt[3] = {-a[0] + b[0], -a[1] + b[1], -a[2] + b[2]};
+    quat_mul(qi, qn, dq);
+    // Eigen::AngleAxisd(q): angle = 2 atan2(|vec|, |w|), the axis vec / |vec| with the sign of w; no rotation: angle 0 about x
+    double n = std::sqrt(dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]), angle = 0, axis[3] = {1, 0, 0};
+    if (n != 0.0) {
+        angle = 2.0 * std::atan2(n, std::fabs(dq[0]));
+        if (dq[0] < 0) n = -n;
+        for (int i = 0; i < 3; i++) axis[i] = dq[1 + i] / n;
+    }
+    const double lt[3] = {ratio * dt[0], ratio * dt[1], ratio * dt[2]};
+    const double lr[3] = {ratio * (angle * axis[0]), ratio * (angle * axis[1]), ratio * (angle * axis[2])};
+    const double norm = std::sqrt(lr[0] * lr[0] + lr[1] * lr[1] + lr[2] * lr[2]);
+    double tq[4] = {1, 0, 0, 0};
+    if (!(norm < 1e-8)) {
+        const double sh = std::sin(0.5 * norm), ch = std::cos(0.5 * norm);
+        tq[0] = ch; tq[1] = sh * (lr[0] / norm); tq[2] = sh * (lr[1] / norm); tq[3] = sh * (lr[2] / norm);
+    }
+    double rt[3], nq[4];
+    quat_rotate(q, lt, rt);
+    quat_mul(q, tq, nq);
+    Mat4 R = Mat4::identity();
+    const double w = nq[0], x = nq[1], y = nq[2], z = nq[3];
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R(0, 0) = 1 - (tyy + tzz); R(0, 1) = txy - twz; R(0, 2) = txz + twy;
+    R(1, 0) = txy + twz; R(1, 1) = 1 - (txx + tzz); R(1, 2) = tyz - twx;
+    R(2, 0) = txz - twy; R(2, 1) = tyz + twx; R(2, 2) = 1 - (txx + tyy);
+    for (int i = 0; i < 3; i++) R(i, 3) = t[i] + rt[i];
+    return R;
+}
+
+// get_stamp_pose (graph_utils.cpp:514-544): the odometry pair around the stamp, searched from start_idx on, and the pose between them.  Its three
+// refusals: no odometry, a stamp before the first or after the last, no pair found from start_idx on.
+bool get_stamp_pose(uint64_t stamp, int start_idx, int& out_idx, TumPose& pose) {
+    const std::vector<TumPose>& od = g_col.odometrys;
+    if (od.empty()) return false;
+    if (stamp < od.front().stamp) return false;
+    if (stamp > od.back().stamp) return false;
+    size_t first = (size_t)std::max(start_idx, 0), second = first;
+    if (first >= od.size()) return false;
+    for (; second != od.size(); second++) {
+        const double dt = ((double)od[first].stamp - (double)stamp) / 1000000.0, dt2 = ((double)od[second].stamp - (double)stamp) / 1000000.0;
+        if (dt <= 0 && dt2 >= 0) break;
+        first = second;
+    }
+    if (first == second || second == od.size()) return false;
+    out_idx = (int)first;
+    const double ratio = ((double)stamp - (double)od[first].stamp) / (double)(od[second].stamp - od[first].stamp);
+    pose.stamp = stamp;
+    pose.T = interpolate_transform(od[first].T, od[second].T, ratio);
+    return true;
+}
+
+// starts a fresh, active painter with an identity lidar transform (graph_utils.cpp:546-557)
+void set_colouration_config(py::list& cameras) {
+    std::vector<CamCfg> cams = camera_config(cameras);
+    if (g_col.map) lio_render_destroy(g_col.map);
+    g_col.map = nullptr;
+    g_col.map = make_painter(cams, Mat4::identity(), "set_colouration_config");
+    lio_render_set_active(g_col.map, 1);
+    g_col.cameras = cams;
+    g_col.last_outcome = -1;
+}
+void set_map_odometrys(py::array_t<double>& poses) {
+    g_col.odometry_idx = 0;
+    g_col.odometrys = tum_poses(poses);
+}
+// the seed of the ground test's draws (lio_ground; 0 unless set)
+void set_colouration_seed(uint32_t seed) { g_col.seed = seed; }
+void colouration_frame(std::string lidar_name, py::dict& points, py::dict& points_attr, py::dict& image_dict, py::dict& image_stream_dict, py::dict& image_param) {
+    (void)image_stream_dict;
+    if (!g_col.map) throw std::runtime_error("slam_wrapper: colouration_frame: set_colouration_config first (save_render_cloud releases the painter)");
+    if (!points.contains(lidar_name.c_str()) || !points_attr.contains(lidar_name.c_str()))
+        throw std::invalid_argument("slam_wrapper: colouration_frame: no cloud named '" + lidar_name + "'");
+    std::vector<FrameImage> images = frame_images(image_dict, image_param, g_col.cameras, "colouration_frame");
+    py::array_t<float> cloud = py::cast<py::array>(points[lidar_name.c_str()]);
+    py::dict attr = py::cast<py::dict>(points_attr[lidar_name.c_str()]);
+    const uint64_t header = py::cast<uint64_t>(attr["timestamp"]);
+    g_col.last_outcome = -1;
+    // the poses at the start of the scan and 100 ms later
+    int start_idx = 0, end_idx = 0;
+    TumPose start, end;
+    if (!get_stamp_pose(header, g_col.odometry_idx, start_idx, start)) return;
+    if (!get_stamp_pose(header + 100000ULL, g_col.odometry_idx, end_idx, end)) return;
+    g_col.odometry_idx = start_idx;
+    std::vector<TumPose> poses;
+    poses.push_back(start);
+    for (int i = start_idx + 1; i < end_idx; i++) poses.push_back(g_col.odometrys[(size_t)i]);
+    poses.push_back(end);
+    undistort_frame(cloud, attr, poses, "colouration_frame");  // (relative to the first pose, as :594-597)
+    std::vector<float> frame(4 * (size_t)g_acc.scan_cap + 4);
+    const int n = lio_scan_download_raw(g_acc.scan, frame.data(), g_acc.scan_cap);
+    require(n >= 0, "colouration_frame: download failed");
+    std::vector<FrameImage> posed;
+    for (FrameImage& im : images) {
+        int idx = 0;
+        TumPose ip;
+        if (get_stamp_pose(im.stamp, g_col.odometry_idx, idx, ip)) {
+            im.pose = ip.T;
+            posed.push_back(std::move(im));
+        }
+    }
+    const int rc = paint_frame(g_col.map, frame.data(), (size_t)n, start.T, g_col.seed, posed);
+    require(rc >= 0, "colouration_frame: render failed");
+    g_col.last_outcome = rc;
+    frame.resize(4 * (size_t)n);
+    g_col.last_frame = frame;
+    g_col.last_pose = start.T;
+    g_col.last_images.clear();
+    for (const FrameImage& im : posed) g_col.last_images.emplace_back(g_col.cameras[(size_t)im.camera].name, im.pose);
+}
+// the colour map as a binary PCD (x y z rgb); the painter is released; an empty cloud writes nothing, like the module's other savers
+void save_render_cloud(std::string file) {
+    if (!g_col.map) return;
+    std::vector<float> pts = colour_map_points(g_col.map);
+    lio_render_destroy(g_col.map);
+    g_col.map = nullptr;
+    if (pts.empty()) return;
+    require(write_pcd_rgb(file, pts.data(), pts.size() / 4), "save_render_cloud: cannot write the file");
+}
+// test visibility: (outcome, frame N x 4, pose 4 x 4, {camera: pose}) of the last colouration_frame -- outcome -1: refused by get_stamp_pose,
+// else LIO_RENDER_*; _stamp_pose(stamp, start_idx) -> (found, idx, pose) of get_stamp_pose
+py::tuple _colouration_last() {
+    auto to_np = [](const Mat4& T) {
+        py::array_t<double> a({4, 4});
+        std::memcpy(a.mutable_data(), T.m, sizeof(T.m));
+        return a;
+    };
+    py::array_t<float> f({(py::ssize_t)(g_col.last_frame.size() / 4), (py::ssize_t)4});
+    if (!g_col.last_frame.empty()) std::memcpy(f.mutable_data(), g_col.last_frame.data(), g_col.last_frame.size() * sizeof(float));
+    py::dict im;
+    for (const auto& p : g_col.last_images) im[p.first.c_str()] = to_np(p.second);
+    return py::make_tuple(g_col.last_outcome, f, to_np(g_col.last_pose), im);
+}
+py::tuple _stamp_pose(uint64_t stamp, int start_idx) {
+    int idx = -1;
+    TumPose p;
+    p.T = Mat4::identity();
+    const bool ok = get_stamp_pose(stamp, start_idx, idx, p);
+    py::array_t<double> a({4, 4});
+    std::memcpy(a.mutable_data(), p.T.m, sizeof(p.T.m));
+    return py::make_tuple(ok, idx, a);
+}
 
 // test visibility (not in the reference's module): the engine behind the module, so that a test can hold the C++ path against the C ABI
 uintptr_t _engine_handle() { return g ? reinterpret_cast<uintptr_t>(g->engine) : 0; }
@@ -2835,6 +3213,9 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("colouration_frame", &colouration_frame, "colouration frame", py::arg("lidar_name"), py::arg("points"), py::arg("points_attr"), py::arg("image_dict"),
           py::arg("image_stream_dict"), py::arg("image_param"));
     m.def("save_render_cloud", &save_render_cloud, "save render cloud", py::arg("file"));
+    m.def("set_colouration_seed", &set_colouration_seed, "seed of the ground test's draws in colouration_frame", py::arg("seed"));
+    m.def("_colouration_last", &_colouration_last);
+    m.def("_stamp_pose", &_stamp_pose, py::arg("stamp"), py::arg("start_idx"));
     m.def("set_keyframe_output", &set_keyframe_output, "key frames from process() through update_odom()", py::arg("enable"));
     m.def("set_loop_detection", &set_loop_detection, "loop detection over the key frames update_odom() hands out", py::arg("enable"));
     m.def("set_global_localization", &set_global_localization, "scan-context relocalisation in localisation mode", py::arg("enable"));

@@ -69,6 +69,8 @@ SYMBOLS = [
     "lio_graph_num_nodes", "lio_graph_get_fixed", "lio_graph_add_edge", "lio_graph_remove_edge", "lio_graph_optimize", "lio_graph_estimates", "lio_graph_edges",
     "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
     "lio_graph_add_prior", "lio_graph_set_kernel", "lio_graph_priors", "lio_graph_prior_error", "lio_graph_remove_gnss_outliers",
+    "lio_render_create", "lio_render_destroy", "lio_render_clear", "lio_render_set_cameras", "lio_render_set_active", "lio_render_frame", "lio_render_size",
+    "lio_render_download", "lio_render_download_voxels", "lio_render_download_points", "lio_render_download_last_image", "lio_render_last_times",
 ]
 
 
@@ -121,6 +123,13 @@ class GroundParams(C.Structure):  # lio_ground_params
     _fields_ = [("sensor_height", C.c_double), ("clip_low", C.c_double), ("clip_high", C.c_double), ("use_normal_filter", C.c_int32),
                 ("normal_thresh_deg", C.c_double), ("k", C.c_int32), ("distance_threshold", C.c_double), ("min_points", C.c_int32),
                 ("floor_normal_thresh_deg", C.c_double), ("max_iterations", C.c_int32), ("probability", C.c_double), ("seed", C.c_uint32)]
+
+
+class RenderImage(C.Structure):  # lio_render_image
+    _fields_ = [("camera", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32), ("bgr", C.c_void_p), ("pose", C.c_double * 16)]
+
+
+RENDER_SKIPPED, RENDER_NO_FLOOR, RENDER_DONE = 0, 1, 2  # lio_render_frame
 
 
 class KeyframerParams(C.Structure):  # lio_keyframer_params
@@ -551,6 +560,18 @@ def lib():
     sig("lio_graph_priors", cint, vp, i32p, i32p, i32p, f64p, f64p, f64p, i32p, f64p, u32)
     sig("lio_graph_prior_error", cint, f64p, cint, f64p, f64p, f64p)
     sig("lio_graph_remove_gnss_outliers", cint, vp, dbl, cint, i32p, u32, gr)
+    sig("lio_render_create", vp, cint, u64, u64)
+    sig("lio_render_destroy", None, vp)
+    sig("lio_render_clear", cint, vp)
+    sig("lio_render_set_cameras", cint, vp, cint, C.POINTER(C.c_char_p), f64p, f64p, f64p)
+    sig("lio_render_set_active", cint, vp, cint)
+    sig("lio_render_frame", cint, vp, f32p, u64, f64p, cint, u32, C.POINTER(RenderImage), cint)
+    sig("lio_render_size", cint, vp, C.POINTER(u64), C.POINTER(u64))
+    sig("lio_render_download", C.c_int64, vp, f32p, u64)
+    sig("lio_render_download_voxels", C.c_int64, vp, i32p, u32p, u32p, u64)
+    sig("lio_render_download_points", C.c_int64, vp, f32p, u32p, f32p, f32p, f32p, u64)
+    sig("lio_render_download_last_image", C.c_int64, vp, f32p, i32p, u8p, u64, C.POINTER(cint), C.POINTER(cint))
+    sig("lio_render_last_times", cint, vp, f64p, f64p, f64p)
     sig("lio_state_boxplus", None, f64p, f64p, f64p)
     sig("lio_state_boxminus", None, f64p, f64p, f64p)
     _lib = L

@@ -2346,3 +2346,121 @@ class LocalMap:
         r["ids"] = [int(v) for v in rep.ids[:rep.n_ids]]
         r["guess"] = np.array(rep.guess).reshape(4, 4)
         return out, r
+
+
+class ColourMap:
+    """lio_render: the road-surface colour map of slam/localization/map_render on the device (include/lio_hip.h states every rule): floor
+    points of a frame enter 0.2 m voxels, every stored point of the touched voxels is projected into the frame's camera images, a z-buffer
+    and a 9 x 9 depth test decide what is seen, and the seen points blend a bilinear sample into their colour.  `frame` returns "skipped",
+    "no_floor" or "rendered"; an invalid argument raises ValueError, a frame that does not fit LioError (the map is unchanged)."""
+
+    OUTCOME = {capi.RENDER_SKIPPED: "skipped", capi.RENDER_NO_FLOOR: "no_floor", capi.RENDER_DONE: "rendered"}
+
+    def __init__(self, max_voxels=1 << 20, max_points=1 << 24, device=0, active=True):
+        self.h = lib().lio_render_create(device, int(max_voxels), int(max_points))
+        if not self.h:
+            raise capi.LioError("lio_render_create failed: " + lib().lio_last_error().decode())
+        self.names = []
+        self.set_active(active)
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_render_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _check(rc, what):
+        if rc == capi.LIO_E_INVALID:
+            raise ValueError(f"{what}: {lib().lio_last_error().decode()}")
+        return check(rc, what)
+
+    def set_cameras(self, cameras, lidar_static=None):
+        """cameras: {name: (K, extrinsic)} with K = (fx, fy, cx, cy) or a 3 x 3 matrix and a 4 x 4 extrinsic; lidar_static: 4 x 4 or None"""
+        names = list(cameras)
+        intr, ext = np.zeros((len(names), 4)), np.zeros((len(names), 16))
+        for i, n in enumerate(names):
+            K, E = cameras[n]
+            K = np.asarray(K, np.float64)
+            intr[i] = (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.ndim == 2 else K.ravel()[:4]
+            ext[i] = f64(E).reshape(16)
+        arr = (C.c_char_p * max(len(names), 1))(*[str(n).encode() for n in names])
+        ls = f64(lidar_static).reshape(16) if lidar_static is not None else None
+        self._check(lib().lio_render_set_cameras(self.h, len(names), arr, ptr(intr, C.c_double), ptr(ext, C.c_double),
+                                                 ptr(ls, C.c_double) if ls is not None else None), "render set_cameras")
+        self.names = [str(n) for n in names]
+
+    def set_active(self, active):
+        check(lib().lio_render_set_active(self.h, int(bool(active))), "render set_active")
+
+    def frame(self, xyzi, pose, images=None, use_ground=True, seed=0):
+        """images: {camera name: (bgr image rows x cols x 3 u8, 4 x 4 pose)}"""
+        p = f32(xyzi).reshape(-1, 4)
+        T = f64(pose).reshape(16)
+        images = images or {}
+        buf, keep = (capi.RenderImage * max(len(images), 1))(), []
+        for i, (name, (img, ipose)) in enumerate(images.items()):
+            a = np.asarray(img)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("ColourMap.frame: an image must be rows x cols x 3 (BGR); the I420 conversion of imageCvtColor is out of scope")
+            if str(name) not in self.names:
+                raise ValueError(f"ColourMap.frame: no camera named {name}")
+            a = np.ascontiguousarray(a, np.uint8)
+            keep.append(a)
+            buf[i].camera, buf[i].rows, buf[i].cols, buf[i].bgr = self.names.index(str(name)), a.shape[0], a.shape[1], a.ctypes.data
+            buf[i].pose[:] = list(f64(ipose).reshape(16))
+        rc = self._check(lib().lio_render_frame(self.h, ptr(p, C.c_float), len(p), ptr(T, C.c_double), int(bool(use_ground)), int(seed) & 0xFFFFFFFF, buf,
+                                                len(images)), "render frame")
+        return self.OUTCOME[rc]
+
+    def clear(self):
+        check(lib().lio_render_clear(self.h), "render clear")
+
+    def size(self):
+        """(voxels, points) the map holds"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        check(lib().lio_render_size(self.h, C.byref(a), C.byref(b)), "render size")
+        return a.value, b.value
+
+    def colour_map(self):
+        """getColorMap as pointcloud_to_numpy(PointCloudRGB) returns it: n x 4 f32, the last column r << 16 | g << 8 | b as f32 bits"""
+        n = max(-int(lib().lio_render_download(self.h, None, 0)), 0)
+        out = np.zeros((n, 4), np.float32)
+        if n:
+            check(int(lib().lio_render_download(self.h, ptr(out, C.c_float), n)), "render download")
+        return out
+
+    def voxels(self):
+        """dict box (n x 3 i32), hits, counts (u32) in voxel number order"""
+        n = self.size()[0]
+        box, hits, cnt = np.zeros((n, 3), np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        if n:
+            check(int(lib().lio_render_download_voxels(self.h, ptr(box, C.c_int32), ptr(hits, C.c_uint32), ptr(cnt, C.c_uint32), n)), "render voxels")
+        return dict(box=box, hits=hits, counts=cnt)
+
+    def points(self):
+        """dict xyz (n x 3 f32), voxel (u32), rgb (n x 3 f32), score, depth (f32) in serial number order"""
+        n = self.size()[1]
+        xyz, vox, rgb = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32), np.zeros((n, 3), np.float32)
+        score, depth = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        if n:
+            check(int(lib().lio_render_download_points(self.h, ptr(xyz, C.c_float), ptr(vox, C.c_uint32), ptr(rgb, C.c_float), ptr(score, C.c_float),
+                                                       ptr(depth, C.c_float), n)), "render points")
+        return dict(xyz=xyz, voxel=vox, rgb=rgb, score=score, depth=depth)
+
+    def last_image(self):
+        """dict depth (rows x cols f32, -1: no owner), owner (i32 serial, -1), valid (u8) of the last image of the last rendered frame"""
+        r, c = C.c_int(0), C.c_int(0)
+        n = max(-int(lib().lio_render_download_last_image(self.h, None, None, None, 0, C.byref(r), C.byref(c))), 0)
+        d, o, v = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        if n:
+            check(int(lib().lio_render_download_last_image(self.h, ptr(d, C.c_float), ptr(o, C.c_int32), ptr(v, C.c_uint8), n, C.byref(r), C.byref(c))),
+                  "render last_image")
+        shape = (r.value, c.value)
+        return dict(depth=d.reshape(shape), owner=o.reshape(shape), valid=v.reshape(shape))
+
+    def last_times(self):
+        v = [C.c_double(0) for _ in range(3)]
+        check(lib().lio_render_last_times(self.h, *[C.byref(x) for x in v]), "render times")
+        return dict(insert_us=v[0].value, image_us=v[1].value, finish_us=v[2].value)
