@@ -81,8 +81,10 @@ int lio_device_count(void);
  *      pose hint, GlobalLocalization::getEstimatePose, on the device).  lio_gicp_set_target / _set_source now leave the cloud in an internal
  *      order that is a function of the cloud (it was the grid's arrival order: lio_gicp_download differed from call to call, T in its last bits).
  * 20 = lio_render_* (the road-surface colour map of slam/localization/map_render: voxels of floor points painted from camera images -- insert,
- *      projection, z-buffer, depth continuity, bilinear sample, running blend, export). */
-#define LIO_ABI_VERSION 20
+ *      projection, z-buffer, depth continuity, bilinear sample, running blend, export).
+ * 21 = lio_graph_remove_node, lio_graph_node_live, lio_graph_edge_records, lio_loop_retire (a key frame leaves the map: graph_del_vertex; and
+ *      the graph hands back its edges as they were added: graph_save).  A removed node's id, and a retired frame's, is refused as unknown. */
+#define LIO_ABI_VERSION 21
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1221,6 +1223,14 @@ int lio_loop_reset(lio_loop*);
  * n > max_points.  pose = node->estimate(), row-major 4 x 4 */
 int lio_loop_add_keyframe_host(lio_loop*, const float* xyzi, uint32_t n, const double pose[16], double accum_distance);
 int lio_loop_set_pose(lio_loop*, int id, const double pose[16]);
+/* a frame leaves the matching for good (graph_del_vertex, hdl_graph_slam_nodelet.cpp:868-891, erases the key frame from `keyframes`, the list
+ * LoopDetector::detect searches): lio_loop_detect passes it over as a new frame and leaves it out of find_candidates as if it had never been
+ * added, the stage doors (lio_loop_align_candidates, lio_loop_align_fine, lio_loop_pair_information, lio_overlap_gate_batch, _align_pairs,
+ * _accumulate) answer LIO_E_INVALID for it as for an unknown id, and lio_overlap_detect drops it from the reference list -- so it is neither a
+ * candidate nor a neighbour in the accumulated cloud -- and gives it no candidate as a new frame.  The slot, the id and the device storage stay:
+ * no other frame's id moves, lio_loop_set_pose and lio_loop_download_keyframe still take the id, edges found earlier stay in lio_loop_edges.
+ * LIO_E_INVALID for an unknown or already retired frame */
+int lio_loop_retire(lio_loop*, int frame);
 int lio_loop_num_keyframes(lio_loop*, int* n_queued);
 /* a frame's resident cloud (the order it was added in) and covariances (xx, xy, xz, yy, yz, zz); the count, or -(count) when cap is too small */
 int lio_loop_download_keyframe(lio_loop*, int id, float* xyzi, double* cov6, uint32_t cap);
@@ -1548,6 +1558,21 @@ int lio_graph_get_fixed(lio_graph*, uint8_t* out, uint32_t cap);
  * symmetric to 1e-9 of its largest entry */
 int lio_graph_add_edge(lio_graph*, int from, int to, const double M16[16], const double info36[36], int kernel, double delta);
 int lio_graph_remove_edge(lio_graph*, int id);
+/* graph_del_vertex / GraphSLAM::del_se3_node (hdl_graph_slam_nodelet.cpp:868-891, graph_slam.cpp:154-156: g2o's removeVertex, which removes every
+ * edge incident to the vertex as well): the node is marked removed and every live edge and prior on it is removed as lio_graph_remove_edge
+ * removes it.  Ids are g2o ids and stay: no other node or edge is renumbered, the id is never handed out again, lio_graph_num_nodes goes on
+ * counting the slot.  Afterwards the id is unknown: lio_graph_add_edge, _add_prior, _set_fixed, _set_estimate and a second _remove_node answer
+ * LIO_E_INVALID.  A removed node is never active (no row, no block, no preconditioner entry); lio_graph_estimates leaves its row as it last
+ * was, lio_graph_get_fixed reports 0 for it.  When the only fixed node is removed the next optimisation runs as the graph always has without a
+ * fixed node: every connected node is active, nothing but the LM damping holds the gauge, chi2 still falls and the whole graph may drift rigidly */
+int lio_graph_remove_node(lio_graph*, int id);
+/* 1 for a live node, 0 for a removed one, all slots; the count, or -(count) when cap is too small (as lio_graph_get_fixed) */
+int lio_graph_node_live(lio_graph*, uint8_t* out, uint32_t cap);
+/* the live binary edges in rising id as they were added -- what graph_save (hdl_graph_slam_nodelet.cpp:1088-1110) hands to g2o's writer: id, ends,
+ * the measurement as the row-major 4 x 4 and the 6 x 6 information bit for bit as lio_graph_add_edge received them (the graph keeps a host copy;
+ * the device holds the measurement as t + q), the kernel and delta as lio_graph_set_kernel last left them.  Any array may be NULL; the count, or
+ * -(count) when cap is too small (as lio_graph_priors, whose counterpart this is) */
+int lio_graph_edge_records(lio_graph*, int32_t* id, int32_t* from, int32_t* to, double* M16, double* info36, int32_t* kernel, double* delta, uint32_t cap);
 /* a prior on one node: type LIO_GRAPH_PRIOR_*; m4 = x, y, z (XYZ; m4[3] is not read), a quaternion x, y, z, w (QUAT) or a plane n, d in the node's
  * frame (PLANE); plane4 = the world plane of a PLANE prior (NULL otherwise); info9 row-major 3 x 3.  The id; LIO_E_INVALID for an unknown node,
  * type or kernel, a kernel with delta <= 0, a value that is not finite, a zero normal or quaternion, or an information matrix that is not

@@ -752,6 +752,10 @@ struct lio_graph {
     // host mirror of the topology; a prior has to = -1, and pslot = its index in priors (-1 for a binary edge)
     std::vector<int32_t> from, to, pslot;
     std::vector<uint8_t> live, fixed;
+    std::vector<uint8_t> gone;  // per node: removed (lio_graph_remove_node); its slot, its device row and its id stay
+    // host mirror of every binary edge as it was added (lio_graph_edge_records); a prior's id holds an empty record
+    struct EdgeRec { double M[16], info[36], delta; int32_t kernel; };
+    std::vector<EdgeRec> rec;
     std::vector<PriorDev> priors;  // host mirror of every prior ever added; the first n_dev_priors are on the device
     uint32_t n_dev_priors = 0, prior_cap = 0;
     PriorDev* d_priors = nullptr;
@@ -784,6 +788,7 @@ namespace {
 
 uint32_t num_nodes(const lio_graph* g) { return (uint32_t)g->fixed.size(); }
 uint32_t num_edges(const lio_graph* g) { return (uint32_t)g->from.size(); }
+bool node_ok(const lio_graph* g, int id) { return id >= 0 && (uint32_t)id < num_nodes(g) && !g->gone[id]; }  // a removed id is as unknown as one never handed out
 
 template <typename T>
 int grow_copy(T** p, uint64_t old_n, uint64_t new_cap, hipStream_t st) {
@@ -894,7 +899,7 @@ int build_topology(lio_graph* g) {
     std::vector<int32_t> aidx(N, -1);
     g->act.clear();
     for (uint32_t n = 0; n < N; n++)
-        if (!g->fixed[n] && deg[n]) { aidx[n] = (int32_t)g->act.size(); g->act.push_back(n); }
+        if (!g->gone[n] && !g->fixed[n] && deg[n]) { aidx[n] = (int32_t)g->act.size(); g->act.push_back(n); }
     const uint32_t Na = (uint32_t)g->act.size();
     std::vector<std::vector<uint32_t>> dl(Na);
     std::map<std::pair<uint32_t, uint32_t>, std::vector<uint32_t>> pairs;  // (lo, hi) in active indices
@@ -1111,7 +1116,7 @@ int lio_graph_reset(lio_graph* g) {
     if (!g) return LIO_E_INVALID;
     hipSetDevice(g->device);
     LIO_HIP_TRY(hipStreamSynchronize(g->st));
-    g->from.clear(); g->to.clear(); g->pslot.clear(); g->live.clear(); g->fixed.clear(); g->pend_nodes.clear(); g->pend_edges.clear(); g->priors.clear();
+    g->from.clear(); g->to.clear(); g->pslot.clear(); g->live.clear(); g->fixed.clear(); g->gone.clear(); g->rec.clear(); g->pend_nodes.clear(); g->pend_edges.clear(); g->priors.clear();
     g->n_dev_nodes = g->n_dev_edges = g->n_dev_priors = 0;
     g->topo_dirty = true;
     g->Na = g->P = g->n_live = 0;
@@ -1127,19 +1132,20 @@ int lio_graph_add_node(lio_graph* g, const double pose16[16]) {
     g->pend_nodes.insert(g->pend_nodes.end(), t, t + 3);
     g->pend_nodes.insert(g->pend_nodes.end(), q, q + 4);
     g->fixed.push_back(0);
+    g->gone.push_back(0);
     g->topo_dirty = true;
     return (int)g->fixed.size() - 1;
 }
 
 int lio_graph_set_fixed(lio_graph* g, int id, int flag) {
-    if (!g || id < 0 || (uint32_t)id >= num_nodes(g)) return LIO_E_INVALID;
+    if (!g || !node_ok(g, id)) return LIO_E_INVALID;
     const uint8_t f = flag ? 1 : 0;
     if (g->fixed[id] != f) { g->fixed[id] = f; g->topo_dirty = true; }
     return LIO_OK;
 }
 
 int lio_graph_set_estimate(lio_graph* g, int id, const double pose16[16]) {
-    if (!g || id < 0 || (uint32_t)id >= num_nodes(g) || !pose16 || !pose_ok(pose16)) return LIO_E_INVALID;
+    if (!g || !node_ok(g, id) || !pose16 || !pose_ok(pose16)) return LIO_E_INVALID;
     double tq[7];
     T_to_tq(pose16, tq, tq + 3);
     if ((uint32_t)id >= g->n_dev_nodes) {
@@ -1153,7 +1159,7 @@ int lio_graph_set_estimate(lio_graph* g, int id, const double pose16[16]) {
 }
 
 int lio_graph_add_edge(lio_graph* g, int from, int to, const double M16[16], const double info36[36], int kernel, double delta) {
-    if (!g || !M16 || !info36 || from < 0 || to < 0 || (uint32_t)from >= num_nodes(g) || (uint32_t)to >= num_nodes(g) || !pose_ok(M16)) return LIO_E_INVALID;
+    if (!g || !M16 || !info36 || !node_ok(g, from) || !node_ok(g, to) || !pose_ok(M16)) return LIO_E_INVALID;
     if (from == to) { set_error("lio_graph_add_edge: an edge from node %d to itself", from); return LIO_E_INVALID; }
     if (!kernel_ok("lio_graph_add_edge", kernel, delta)) return LIO_E_INVALID;
     double amax = 0.0;
@@ -1169,13 +1175,17 @@ int lio_graph_add_edge(lio_graph* g, int from, int to, const double M16[16], con
     T_to_tq(M16, e.mt, e.mq);
     memcpy(e.info, info36, sizeof(e.info));
     g->pend_edges.push_back(e);
+    lio_graph::EdgeRec r;
+    memcpy(r.M, M16, sizeof(r.M)); memcpy(r.info, info36, sizeof(r.info));
+    r.kernel = kernel; r.delta = delta;
+    g->rec.push_back(r);
     g->from.push_back(from); g->to.push_back(to); g->pslot.push_back(-1); g->live.push_back(1);
     g->topo_dirty = true;
     return (int)g->from.size() - 1;
 }
 
 int lio_graph_add_prior(lio_graph* g, int node, int type, const double m4[4], const double plane4[4], const double info9[9], int kernel, double delta) {
-    if (!g || !m4 || !info9 || node < 0 || (uint32_t)node >= num_nodes(g)) return LIO_E_INVALID;
+    if (!g || !m4 || !info9 || !node_ok(g, node)) return LIO_E_INVALID;
     if (type != LIO_GRAPH_PRIOR_XYZ && type != LIO_GRAPH_PRIOR_QUAT && type != LIO_GRAPH_PRIOR_PLANE) { set_error("lio_graph_add_prior: unknown type %d", type); return LIO_E_INVALID; }
     if (type == LIO_GRAPH_PRIOR_PLANE && !plane4) { set_error("lio_graph_add_prior: a PLANE prior needs its world plane"); return LIO_E_INVALID; }
     if (!kernel_ok("lio_graph_add_prior", kernel, delta) || !(delta - delta == 0.0)) return LIO_E_INVALID;
@@ -1216,6 +1226,7 @@ int lio_graph_add_prior(lio_graph* g, int node, int type, const double m4[4], co
     hole.from = (int32_t)g->priors.size(); hole.to = -1; hole.live = kPriorSlot;
     g->pend_edges.push_back(hole);
     g->priors.push_back(p);
+    g->rec.push_back(lio_graph::EdgeRec());
     g->from.push_back(node); g->to.push_back(-1); g->pslot.push_back(hole.from); g->live.push_back(1);
     g->topo_dirty = true;
     return p.id;
@@ -1226,6 +1237,7 @@ int lio_graph_set_kernel(lio_graph* g, int id, int kernel, double delta) {
     if (!kernel_ok("lio_graph_set_kernel", kernel, delta) || !(delta - delta == 0.0)) return LIO_E_INVALID;
     hipSetDevice(g->device);
     if (g->pslot[id] >= 0) return prior_set(g, (uint32_t)g->pslot[id], kernel, delta, 1);
+    g->rec[id].kernel = kernel; g->rec[id].delta = delta;
     if ((uint32_t)id >= g->n_dev_edges) {
         EdgeDev& e = g->pend_edges[(uint32_t)id - g->n_dev_edges];
         e.kernel = kernel; e.delta = delta;
@@ -1294,6 +1306,48 @@ int lio_graph_remove_edge(lio_graph* g, int id) {
     const int32_t zero = 0;
     LIO_HIP_TRY(hipMemcpy(&g->d_edges[id].live, &zero, sizeof(zero), hipMemcpyHostToDevice));
     return LIO_OK;
+}
+
+int lio_graph_remove_node(lio_graph* g, int id) {
+    if (!g || !node_ok(g, id)) return LIO_E_INVALID;
+    for (uint32_t e = 0; e < num_edges(g); e++) {  // g2o's removeVertex: every edge and prior on the node goes with it
+        if (!g->live[e] || (g->from[e] != id && g->to[e] != id)) continue;
+        const int rc = lio_graph_remove_edge(g, (int)e);
+        if (rc != LIO_OK) return rc;
+    }
+    g->gone[id] = 1;
+    g->fixed[id] = 0;
+    g->topo_dirty = true;
+    return LIO_OK;
+}
+
+int lio_graph_node_live(lio_graph* g, uint8_t* out, uint32_t cap) {
+    if (!g) return LIO_E_INVALID;
+    const uint32_t N = num_nodes(g);
+    if (N > cap || (N && !out)) return -(int)N;
+    for (uint32_t n = 0; n < N; n++) out[n] = g->gone[n] ? 0 : 1;
+    return (int)N;
+}
+
+int lio_graph_edge_records(lio_graph* g, int32_t* id, int32_t* from, int32_t* to, double* M16, double* info36, int32_t* kernel, double* delta, uint32_t cap) {
+    if (!g) return LIO_E_INVALID;
+    uint32_t n = 0;
+    for (uint32_t e = 0; e < num_edges(g); e++) n += (g->live[e] && g->pslot[e] < 0) ? 1 : 0;
+    if (n > cap) return -(int)n;
+    uint32_t k = 0;
+    for (uint32_t e = 0; e < num_edges(g); e++) {
+        if (!g->live[e] || g->pslot[e] >= 0) continue;
+        const lio_graph::EdgeRec& r = g->rec[e];
+        if (id) id[k] = (int32_t)e;
+        if (from) from[k] = g->from[e];
+        if (to) to[k] = g->to[e];
+        if (M16) memcpy(M16 + 16ull * k, r.M, sizeof(r.M));
+        if (info36) memcpy(info36 + 36ull * k, r.info, sizeof(r.info));
+        if (kernel) kernel[k] = r.kernel;
+        if (delta) delta[k] = r.delta;
+        k++;
+    }
+    return (int)n;
 }
 
 int lio_graph_num_nodes(lio_graph* g) { return g ? (int)num_nodes(g) : LIO_E_INVALID; }

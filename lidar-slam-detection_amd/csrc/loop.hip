@@ -543,6 +543,7 @@ void free_frames(lio_loop* h) {
 }
 
 bool id_ok(lio_loop* h, int id) { return h && id >= 0 && (size_t)id < h->frames.size(); }
+bool live_ok(lio_loop* h, int id) { return id_ok(h, id) && !h->frames[id].retired; }  // a retired frame is no longer matched: to the matchers it is unknown
 
 }  // namespace
 
@@ -781,6 +782,12 @@ int lio_loop_set_pose(lio_loop* h, int id, const double pose[16]) {
     return LIO_OK;
 }
 
+int lio_loop_retire(lio_loop* h, int frame) {
+    if (!live_ok(h, frame)) return LIO_E_INVALID;
+    h->frames[frame].retired = true;
+    return LIO_OK;
+}
+
 int lio_loop_num_keyframes(lio_loop* h, int* n_queued) {
     if (!h) return LIO_E_INVALID;
     if (n_queued) *n_queued = (int)(h->frames.size() - h->n_keyframes);
@@ -804,16 +811,23 @@ int lio_loop_detect(lio_loop* h, lio_loop_edge* out_loops, uint32_t cap) {
     const size_t first_edge = h->edges.size();
     double accum_distance_new_keyframe = 0;
     std::vector<double> accum(h->n_keyframes), xy(2 * h->n_keyframes);
-    std::vector<int32_t> cand;
+    std::vector<int32_t> cand, kept(h->n_keyframes);
     for (size_t id = h->n_keyframes; id < h->frames.size(); id++) {
         const Frame& f = h->frames[id];
+        if (f.retired) continue;  // neither a new frame nor, below, a candidate: the search runs as if the frame had never been there
         if ((f.accum - accum_distance_new_keyframe) < h->par.distance_new_keyframe_thresh) continue;
         accum_distance_new_keyframe = f.accum;
-        for (size_t k = 0; k < h->n_keyframes; k++) { accum[k] = h->frames[k].accum; xy[2 * k] = h->frames[k].pose[3]; xy[2 * k + 1] = h->frames[k].pose[7]; }
-        cand.assign(h->n_keyframes, 0);
+        uint32_t nk = 0;
+        for (size_t k = 0; k < h->n_keyframes; k++) {
+            if (h->frames[k].retired) continue;
+            accum[nk] = h->frames[k].accum; xy[2 * nk] = h->frames[k].pose[3]; xy[2 * nk + 1] = h->frames[k].pose[7];
+            kept[nk++] = (int32_t)k;
+        }
+        cand.assign(nk, 0);
         const double nxy[2] = {f.pose[3], f.pose[7]};
-        const int nc = lio_loop_find_candidates(accum.data(), xy.data(), (uint32_t)h->n_keyframes, f.accum, nxy, h->last_edge_accum, &h->par, cand.data(), (uint32_t)cand.size());
+        const int nc = lio_loop_find_candidates(accum.data(), xy.data(), nk, f.accum, nxy, h->last_edge_accum, &h->par, cand.data(), nk);
         cand.resize(nc > 0 ? nc : 0);
+        for (int32_t& c : cand) c = kept[c];
         bool found = false;
         const int rc = matching(h, (int)id, cand, &found);
         if (rc != LIO_OK) {  // a device error: the queue is emptied all the same (the frame that failed and those behind it become key frames that
@@ -863,9 +877,9 @@ int lio_loop_last_times(lio_loop* h, double* insert_us, double* target_us, doubl
 
 int lio_loop_align_candidates(lio_loop* h, int target_id, const int32_t* source_ids, uint32_t n, const double* guesses, double* out_T, int32_t* iterations,
                               int32_t* converged, double* scores, uint32_t* nr) {
-    if (!id_ok(h, target_id) || (n && (!source_ids || !guesses))) return LIO_E_INVALID;
+    if (!live_ok(h, target_id) || (n && (!source_ids || !guesses))) return LIO_E_INVALID;
     for (uint32_t k = 0; k < n; k++)
-        if (!id_ok(h, source_ids[k])) return LIO_E_INVALID;
+        if (!live_ok(h, source_ids[k])) return LIO_E_INVALID;
     if (n == 0) return LIO_OK;
     hipSetDevice(h->device);
     h->t_target = h->t_coarse = h->t_fitness = h->t_fine = 0;
@@ -902,7 +916,7 @@ int lio_loop_align_candidates(lio_loop* h, int target_id, const int32_t* source_
 
 int lio_loop_align_fine(lio_loop* h, int target_id, int source_id, const double guess[16], double out_T[16], int32_t* iterations, int32_t* converged, double* score,
                         uint32_t* nr) {
-    if (!id_ok(h, target_id) || !id_ok(h, source_id) || !guess) return LIO_E_INVALID;
+    if (!live_ok(h, target_id) || !live_ok(h, source_id) || !guess) return LIO_E_INVALID;
     hipSetDevice(h->device);
     int rc = prepare_target(h, target_id);
     if (rc != LIO_OK) return rc;
@@ -923,7 +937,7 @@ int lio_loop_align_fine(lio_loop* h, int target_id, int source_id, const double 
 }
 
 int lio_loop_pair_information(lio_loop* h, int id1, int id2, const double relpose[16], double* score, uint32_t* nr, double info36[36]) {
-    if (!id_ok(h, id1) || !id_ok(h, id2) || !relpose) return LIO_E_INVALID;
+    if (!live_ok(h, id1) || !live_ok(h, id2) || !relpose) return LIO_E_INVALID;
     hipSetDevice(h->device);
     int rc = prepare_target(h, id1);
     if (rc != LIO_OK) return rc;

@@ -42,6 +42,7 @@ struct Frame {
     uint32_t n = 0;
     double pose[16];
     double accum = 0;
+    bool retired = false;  // lio_loop_retire: the slot and its storage stay, the frame is never matched again
 };
 
 struct AlignOut {

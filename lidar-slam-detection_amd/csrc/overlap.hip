@@ -247,7 +247,8 @@ struct Span {  // HIP events around a stretch of host-synchronous work on the ba
     }
 };
 
-bool bank_id_ok(const lio_overlap* h, int id) { return id >= 0 && (size_t)id < h->L->frames.size(); }
+bool bank_slot_ok(const lio_overlap* h, int id) { return id >= 0 && (size_t)id < h->L->frames.size(); }
+bool bank_id_ok(const lio_overlap* h, int id) { return bank_slot_ok(h, id) && !h->L->frames[id].retired; }  // a retired frame (lio_loop_retire) is unknown to the stage doors
 
 using ConnMap = std::map<int, std::set<int>>;
 
@@ -721,10 +722,25 @@ int lio_overlap_detect(lio_overlap* h, const int32_t* ref_ids, const int32_t* re
                        const int32_t* edge_from, const int32_t* edge_to, uint32_t n_edges, lio_overlap_edge* out, uint32_t cap) {
     if (!h || (n_ref && !ref_ids) || (n_new && !new_ids) || (n_edges && (!edge_from || !edge_to))) return LIO_E_INVALID;
     for (uint32_t k = 0; k < n_ref; k++)
-        if (!bank_id_ok(h, ref_ids[k])) return LIO_E_INVALID;
+        if (!bank_slot_ok(h, ref_ids[k])) return LIO_E_INVALID;
     for (uint32_t k = 0; k < n_new; k++)
-        if (!bank_id_ok(h, new_ids[k])) return LIO_E_INVALID;
+        if (!bank_slot_ok(h, new_ids[k])) return LIO_E_INVALID;
     lio_loop* L = h->L;
+    // a retired frame is skipped: as a reference it is left out of the list (so it is no candidate and no neighbour of the accumulated cloud), as a
+    // new frame it keeps its place in the reports with no candidate
+    std::vector<int32_t> live_ids, live_kf;
+    bool any_retired = false;
+    for (uint32_t k = 0; k < n_ref; k++) any_retired = any_retired || L->frames[ref_ids[k]].retired;
+    if (any_retired) {
+        for (uint32_t k = 0; k < n_ref; k++) {
+            if (L->frames[ref_ids[k]].retired) continue;
+            live_ids.push_back(ref_ids[k]);
+            live_kf.push_back(ref_kf ? ref_kf[k] : ref_ids[k]);
+        }
+        n_ref = (uint32_t)live_ids.size();
+        ref_ids = live_ids.data();
+        ref_kf = live_kf.data();
+    }
     hipSetDevice(L->device);
     memset(&h->tm, 0, sizeof(h->tm));
     h->reports.assign(n_new, FrameReport());
@@ -750,6 +766,7 @@ int lio_overlap_detect(lio_overlap* h, const int32_t* ref_ids, const int32_t* re
         FrameReport& fr = h->reports[i];
         blank_report(fr, new_ids[i]);
         const loop::Frame& nf = L->frames[new_ids[i]];
+        if (nf.retired) continue;
         const auto t0 = std::chrono::steady_clock::now();
         const double q[3] = {nf.pose[3], nf.pose[7], nf.pose[11]};
         const std::vector<int32_t> cand = find_candidates(pos.data(), rkf.data(), n_ref, conn, kf_of_new(i), q, h->par);

@@ -244,6 +244,13 @@ struct Slam {
     double floor_last_distance = 0;       // floor_last_update_distance
     double gnss_last[3] = {0, 0, 0};      // gps_last_update_pose
     std::vector<uint8_t> graph_has_gnss;  // keyframe->utm_coord is set
+    std::vector<uint8_t> graph_gone;      // del_graph_vertex took the key frame out (its node is removed, its bank frame retired; ids stay)
+    // every key frame the bank took, by bank id (= node id with a graph): what get_graph_map needs beside the bank's cloud; guarded by kf_mtx
+    std::vector<uint64_t> bank_stamp;
+    std::vector<Mat4> bank_odom;
+    // HDL_FastLIO::mOdometrys (fastlio.cpp:242-250) in mapping mode, MapLoader::mOdometrys (map_loader.cpp:223-253, 141-142) in localisation mode:
+    // what dump_odometry writes; guarded by mtx
+    std::vector<std::pair<uint64_t, Mat4>> odometrys;
     struct InjectedKeyFrame { std::vector<float> pts; Mat4 pose; uint64_t stamp; double accum; };
     std::deque<InjectedKeyFrame> injected;  // test visibility: key frames handed to update_odom() without the front end (_push_keyframe)
     // the colour map of the localisation mode (MapLoader::mRender, map_render.cpp; lio_render_*): cameras from set_camera_param, switched by
@@ -828,9 +835,31 @@ void set_imu_external_param(double x, double y, double z, double yaw, double pit
     g->T_imu = transform_from_rpyt(x, y, z, yaw, pitch, roll);
 }
 
+// MapLoader::loadOdometry (map_loader.cpp:223-253): <map>/graph/odometrys.txt, one `stamp x y z qx qy qz qw` a line; the stamp goes to whole
+// microseconds, the quaternion through toRotationMatrix as it stands.  A missing file adds nothing
+void read_odometrys(const std::string& map_path, std::vector<std::pair<uint64_t, Mat4>>& out) {
+    std::ifstream fs(map_path + "/graph/odometrys.txt");
+    if (!fs) return;
+    double stamp, v[7];
+    while (fs >> stamp >> v[0] >> v[1] >> v[2] >> v[3] >> v[4] >> v[5] >> v[6]) {
+        const double x = v[3], y = v[4], z = v[5], w = v[6];
+        Mat4 T = Mat4::identity();
+        T(0, 0) = 1 - 2 * (y * y + z * z); T(0, 1) = 2 * (x * y - z * w); T(0, 2) = 2 * (x * z + y * w);
+        T(1, 0) = 2 * (x * y + z * w); T(1, 1) = 1 - 2 * (x * x + z * z); T(1, 2) = 2 * (y * z - x * w);
+        T(2, 0) = 2 * (x * z - y * w); T(2, 1) = 2 * (y * z + x * w); T(2, 2) = 1 - 2 * (x * x + y * y);
+        T(0, 3) = v[0]; T(1, 3) = v[1]; T(2, 3) = v[2];
+        out.emplace_back((uint64_t)(stamp * 1000000), T);
+    }
+}
+
 bool setup_slam() {
     require((bool)g, "init_slam first");
     if (g->loc) load_keyframes(g->map_path, g->loc->frames);  // host side of MapLoader: get_graph_map serves the key frames whatever follows
+    if (g->loc) {
+        std::lock_guard<std::mutex> lk(g->mtx);
+        g->odometrys.clear();
+        read_odometrys(g->map_path, g->odometrys);
+    }
     if (lio_device_count() < 1) return false;  // the reference logs and returns false from setup() when the back end cannot start
     if (g->loc) return loc_setup(g.get());
     // HDL_FastLIO::init (fastlio.cpp:153-171): T_imu_ins = T_imu * T_static^-1 is the (INS-frame cloud) -> IMU extrinsic
@@ -1181,6 +1210,10 @@ py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, 
             s->odom_queue.pop_front();
             s->last_odom_start = out_pose;
             s->last_odom_end = odom_end;
+            // mOdometrys (fastlio.cpp:242-250): the reference pushes the IMU-predicted poses inside the frame; here the frame's end-of-scan pose
+            // at the end-of-scan stamp, and a stamp that does not exceed the last is dropped as there
+            const uint64_t end_stamp = header_stamp + (uint64_t)std::llround(s->scan_period * 1e6);
+            if (s->odometrys.empty() || s->odometrys.back().first < end_stamp) s->odometrys.emplace_back(end_stamp, odom_end);
         }
         lk.unlock();
         // SLAM::runMappingThread -> enqueue_graph -> cloud_callback (slam.cpp:398-411, hdl_graph_slam_nodelet.cpp:163-246): the frame with its
@@ -1310,11 +1343,15 @@ bool graph_optimize_locked(Slam* s, const char* who) {
     const size_t n = s->graph_odom.size();
     std::vector<double> est(16 * n);
     require(lio_graph_estimates(s->graph, est.data(), (uint32_t)n) == (int)n, "lio_graph_estimates failed");
+    size_t last = n;  // the last key frame still in the graph
     for (size_t k = 0; k < n; k++) {
+        if (s->graph_gone[k]) continue;
+        last = k;
         std::memcpy(s->graph_pose[k].m, &est[16 * k], sizeof(double) * 16);
         if (s->loop) require(lio_loop_set_pose(s->loop, (int)k, s->graph_pose[k].m) == LIO_OK, "lio_loop_set_pose failed");
     }
-    const Mat4 trans = mul(s->graph_pose[n - 1], rigid_inverse(s->graph_odom[n - 1]));
+    if (last == n) return false;
+    const Mat4 trans = mul(s->graph_pose[last], rigid_inverse(s->graph_odom[last]));
     for (int k = 0; k < 16; k++) s->odom2map.m[k] = (double)(float)trans.m[k];
     return it >= 0;
 }
@@ -1336,6 +1373,7 @@ void graph_prior_state_reset(Slam* s) {
     s->floor_last_distance = 0;
     s->gnss_last[0] = s->gnss_last[1] = s->gnss_last[2] = 0;
     s->graph_has_gnss.clear();
+    s->graph_gone.clear();
 }
 // "Release the first node" (hdl_graph_slam_nodelet.cpp:448-455, 581-588)
 void release_first_node(Slam* s, const char* who) {
@@ -1429,11 +1467,16 @@ py::dict update_odom() {
                 g->graph_odom.push_back(f.pose);
                 g->graph_pose.push_back(node_pose);
                 g->graph_has_gnss.push_back(0);
-                if (node > 0) {  // the edge key frame -> previous: relative_pose = odom^-1 * prev.odom, the pair's information, no kernel
-                    const Mat4 relp = mul(rigid_inverse(f.pose), g->graph_odom[(size_t)node - 1]);
+                g->graph_gone.push_back(0);
+                g->bank_stamp.push_back(f.stamp);
+                g->bank_odom.push_back(f.pose);
+                int prev = node - 1;  // keyframes.back() (hdl_graph_slam_nodelet.cpp:318): the last key frame del_graph_vertex has left in the list
+                while (prev >= 0 && g->graph_gone[(size_t)prev]) prev--;
+                if (prev >= 0) {  // the edge key frame -> previous: relative_pose = odom^-1 * prev.odom, the pair's information, no kernel
+                    const Mat4 relp = mul(rigid_inverse(f.pose), g->graph_odom[(size_t)prev]);
                     double info[36];
-                    require(lio_loop_pair_information(g->loop, node, node - 1, relp.m, nullptr, nullptr, info) == LIO_OK, "update_odom: lio_loop_pair_information failed");
-                    require(lio_graph_add_edge(g->graph, node, node - 1, relp.m, info, LIO_GRAPH_KERNEL_NONE, 1.0) >= 0, "update_odom: lio_graph_add_edge failed");
+                    require(lio_loop_pair_information(g->loop, node, prev, relp.m, nullptr, nullptr, info) == LIO_OK, "update_odom: lio_loop_pair_information failed");
+                    require(lio_graph_add_edge(g->graph, node, prev, relp.m, info, LIO_GRAPH_KERNEL_NONE, 1.0) >= 0, "update_odom: lio_graph_add_edge failed");
                 }
                 if (g->ground_constraint) floor_constraint(g.get(), node, f.pts.data(), (uint64_t)f.n, accum);
             } else if (g->loop_detection) {  // the key frame joins the detector's bank (new_keyframes); one with fewer than k points is left out (lio_last_warning)
@@ -1444,6 +1487,7 @@ py::dict update_odom() {
                 const int id = lio_loop_add_keyframe_host(g->loop, f.pts.data(), (uint32_t)f.n, f.pose.m, accum);
                 require(id >= 0 || id == LIO_E_INVALID, "update_odom: lio_loop_add_keyframe_host failed");
                 banked = banked || id >= 0;
+                if (id >= 0) { g->bank_stamp.push_back(f.stamp); g->bank_odom.push_back(f.pose); }
             }
         }
         if (banked) {  // LoopDetector::detect over the frames just queued (optimization_timer_callback, hdl_graph_slam_nodelet.cpp:588-623)
@@ -1469,7 +1513,8 @@ py::dict update_odom() {
             }
         }
         if (g->graph_updated) {  // graph_update_odom (hdl_graph_slam_nodelet.cpp:821-833)
-            for (size_t k = 0; k < g->graph_pose.size(); k++) odoms.emplace_back((int)k, g->graph_pose[k]);
+            for (size_t k = 0; k < g->graph_pose.size(); k++)
+                if (!g->graph_gone[k]) odoms.emplace_back((int)k, g->graph_pose[k]);
             g->graph_updated = false;
         }
     }
@@ -1634,6 +1679,7 @@ void set_loop_config(py::dict cfg) {
     // the graph's nodes are the old bank's frames: it starts over with the detector (odom -> map keeps its value)
     if (g->graph) { lio_graph_destroy(g->graph); g->graph = nullptr; }
     g->graph_odom.clear(); g->graph_pose.clear();
+    g->bank_stamp.clear(); g->bank_odom.clear();
     g->graph_loops = 0;
     g->graph_updated = false;
     graph_prior_state_reset(g.get());
@@ -1688,9 +1734,15 @@ void set_map_origin(double lat, double lon, double alt, double heading, double p
 struct G2oFile {
     struct Vertex { int id; double v[7]; };
     struct Edge { int from, to; double m[7], info[36]; };
+    // a unary edge of the reference's own classes (EDGE_SE3_PRIORXYZ / EDGE_SE3_PRIORQUAT): the numbers behind the vertex id as the class's write()
+    // puts them -- x y z (edge_se3_priorxyz.hpp:61-67) or w x y z (edge_se3_priorquat.hpp:68-74), then the 6 values of the information's upper triangle
+    struct Prior { std::string tag; int node; std::vector<double> values; };
+    struct Kernel { std::vector<int> vertices; std::string type; double delta; };  // a line of graph.g2o.kernels (robust_kernel_io.cpp:72-76)
     std::vector<Vertex> vertices;
     std::vector<Edge> edges;
     std::vector<int> fixed;
+    std::vector<Prior> priors;    // counted in `skipped` as before: the graph built from the file does not take them
+    std::vector<Kernel> kernels;  // of <path>.kernels when that file exists
     int skipped = 0;
 };
 bool pose_ok(const double v[7]) {  // x y z qx qy qz qw: finite, and a quaternion that can be normalised
@@ -1731,7 +1783,27 @@ bool read_g2o(const std::string& path, G2oFile& out, std::string& err) {
             if (!n) { err = path + ":" + std::to_string(ln) + ": truncated FIX"; return false; }
         } else {
             out.skipped++;
+            if (tag == "EDGE_SE3_PRIORXYZ" || tag == "EDGE_SE3_PRIORQUAT") {  // kept for the writer's sake, passed over all the same
+                G2oFile::Prior p;
+                p.tag = tag;
+                double v;
+                if (ls >> p.node) {
+                    while (ls >> v) p.values.push_back(v);
+                    out.priors.push_back(p);
+                }
+            }
         }
+    }
+    std::ifstream kf(path + ".kernels");
+    while (kf && std::getline(kf, line)) {
+        std::istringstream ls(line);
+        size_t nv = 0;
+        G2oFile::Kernel k;
+        if (!(ls >> nv) || nv > 8) continue;
+        k.vertices.resize(nv);
+        bool ok = true;
+        for (size_t i = 0; i < nv && ok; i++) ok = (bool)(ls >> k.vertices[i]);
+        if (ok && (ls >> k.type >> k.delta)) out.kernels.push_back(k);
     }
     return true;
 }
@@ -1745,7 +1817,8 @@ Mat4 mat_from_tq(const double v[7]) {  // x y z qx qy qz qw -> the pose, the qua
     T(0, 3) = v[0]; T(1, 3) = v[1]; T(2, 3) = v[2];
     return T;
 }
-// test visibility: _read_g2o(path) -> {vertices: {id: [x y z qx qy qz qw]}, edges: [(from, to, [7], 6 x 6)], fixed: [ids], skipped: tags passed over}
+// test visibility: _read_g2o(path) -> {vertices: {id: [x y z qx qy qz qw]}, edges: [(from, to, [7], 6 x 6)], fixed: [ids], skipped: tags passed over,
+// priors: [(tag, vertex, values)] of the passed-over tags that are GNSS priors, kernels: [([vertices], type, delta)] of <path>.kernels}
 py::dict _read_g2o(std::string path) {
     G2oFile gf;
     std::string err;
@@ -1762,6 +1835,11 @@ py::dict _read_g2o(std::string path) {
     d["edges"] = es;
     d["fixed"] = py::cast(gf.fixed);
     d["skipped"] = gf.skipped;
+    py::list ps, ks;
+    for (const auto& pr : gf.priors) ps.append(py::make_tuple(pr.tag, pr.node, py::array_t<double>((py::ssize_t)pr.values.size(), pr.values.data())));
+    for (const auto& k : gf.kernels) ks.append(py::make_tuple(py::cast(k.vertices), k.type, k.delta));
+    d["priors"] = ps;
+    d["kernels"] = ks;
     return d;
 }
 
@@ -2025,6 +2103,8 @@ py::dict merge_map(const std::string& directory) {
         }
     }
     if (!failure.empty()) throw std::runtime_error(failure);
+    s->odometrys.emplace_back((uint64_t)0, Mat4::identity());  // "add a zero odometry as spliter", then the new map's list (map_loader.cpp:141-142)
+    read_odometrys(directory, s->odometrys);
     std::fprintf(stderr, "slam_wrapper: merge_map: merge success, total %zu key frames, %zu overlaps\n", L.frames.size(), L.merge_report.overlaps.size());
     return keyframes_to_pydict(L.frames, first_new);
 }
@@ -2043,10 +2123,48 @@ py::dict _last_merge() {
     return d;
 }
 // get_graph_map (slam_wrapper.cpp:180-184 -> keyframe_to_pydict, py_utils.cpp:272-293): the key frames of the loaded map in localisation mode
-// (points N x 4 f32 as stored, pose 4 x 4 f32, stamp); empty in mapping mode (the graph back end is out of scope)
+// (points N x 4 f32 as stored, pose 4 x 4 f32, stamp).  In mapping mode the key frames update_odom has handed out and del_graph_vertex has not
+// taken back, in the same shape: the cloud as it was handed out (downloaded from the loop detector's bank, which holds every key frame in its
+// own order), the pose the graph's estimate (the odometry pose without a graph), the stamp; four empty dictionaries with no key frame -- nothing
+// is kept without a bank
 py::dict get_graph_map() {
     py::dict d;
     py::dict points, images, poses, stamps;
+    if (g && !g->loc) {
+        struct Out { int id; std::vector<float> pts; Mat4 pose; uint64_t stamp; };
+        std::vector<Out> frames;
+        {
+            py::gil_scoped_release rel;
+            std::lock_guard<std::mutex> kl(g->kf_mtx);
+            for (size_t k = 0; g->loop && k < g->bank_stamp.size(); k++) {
+                const bool in_graph = g->graph && k < g->graph_pose.size();
+                if (in_graph && g->graph_gone[k]) continue;
+                Out o;
+                o.id = (int)k;
+                const int n = -lio_loop_download_keyframe(g->loop, (int)k, nullptr, nullptr, 0);
+                require(n > 0, "get_graph_map: lio_loop_download_keyframe failed");
+                o.pts.resize(4 * (size_t)n);
+                require(lio_loop_download_keyframe(g->loop, (int)k, o.pts.data(), nullptr, (uint32_t)n) == n, "get_graph_map: lio_loop_download_keyframe failed");
+                o.pose = in_graph ? g->graph_pose[k] : g->bank_odom[k];
+                o.stamp = g->bank_stamp[k];
+                frames.push_back(std::move(o));
+            }
+        }
+        for (const Out& o : frames) {
+            const std::string id = std::to_string(o.id);
+            py::array_t<float> a({(py::ssize_t)(o.pts.size() / 4), (py::ssize_t)4});
+            std::memcpy(a.mutable_data(), o.pts.data(), o.pts.size() * sizeof(float));
+            points[id.c_str()] = a;
+            poses[id.c_str()] = mat4_to_numpy_f32(o.pose);
+            stamps[id.c_str()] = o.stamp;
+            images[id.c_str()] = py::dict();
+        }
+        d["points"] = points;
+        d["images"] = images;
+        d["poses"] = poses;
+        d["stamps"] = stamps;
+        return d;
+    }
     static const std::vector<KeyFrameDisk> none;
     for (const KeyFrameDisk& kf : (g && g->loc) ? g->loc->frames : none) {
         const std::string id = std::to_string(kf.id);
@@ -2079,7 +2197,7 @@ py::array_t<float> get_color_map() {
 }
 // the graph's live edges (graph_get_edges, hdl_graph_slam_nodelet.cpp:842-860; vector_to_pydict, py_utils.cpp:29-48): str(id) -> [prev, next]; {} without a graph
 namespace {
-struct GraphEdges { std::vector<int32_t> from, to, id; std::vector<uint8_t> fixed; };
+struct GraphEdges { std::vector<int32_t> from, to, id; std::vector<uint8_t> fixed, live; };
 GraphEdges graph_edges_snapshot() {
     GraphEdges e;
     if (!g) return e;
@@ -2098,7 +2216,9 @@ GraphEdges graph_edges_snapshot() {
     const int nn = lio_graph_num_nodes(g->graph);
     if (nn > 0) {
         e.fixed.resize(nn);
+        e.live.resize(nn);
         require(lio_graph_get_fixed(g->graph, e.fixed.data(), (uint32_t)nn) == nn, "lio_graph_get_fixed failed");
+        require(lio_graph_node_live(g->graph, e.live.data(), (uint32_t)nn) == nn, "lio_graph_node_live failed");
     }
     return e;
 }
@@ -2118,6 +2238,7 @@ py::dict get_graph_meta() {
     for (size_t k = 0; k < e.id.size(); k++) { deg[e.from[k]]++; deg[e.to[k]]++; }
     py::dict vertex, edge;
     for (size_t n = 0; n < e.fixed.size(); n++) {
+        if (!e.live[n]) continue;  // a vertex del_graph_vertex removed is no vertex of the graph
         py::dict v;
         v["fix"] = (bool)e.fixed[n];
         v["edge_num"] = deg[n];
@@ -2193,7 +2314,7 @@ void set_map_colouration(bool enable) {
     g->colouration = enable;
     if (g->painter) lio_render_set_active(g->painter, enable ? 1 : 0);
 }
-void del_graph_vertex(int id) { (void)id; }
+void del_graph_vertex(int id);  // with dump_graph, below
 // graph_add_edge (hdl_graph_slam_nodelet.cpp:893-912) with score <= 0: calc_information_matrix(prev, next, relative) -- taken on the bank's frames
 // prev_id and next_id, which hold the two clouds -- and Huber 1.0; nothing without a graph
 void add_graph_edge(py::array_t<float>& prev, int prev_id, py::array_t<float>& next, int next_id, py::array_t<float>& relative) {
@@ -2239,7 +2360,8 @@ py::dict run_graph_optimization() {
         std::lock_guard<std::mutex> kl(g->kf_mtx);
         if (g->graph && !g->graph_odom.empty()) {
             graph_optimize_locked(g.get(), "run_graph_optimization");
-            for (size_t k = 0; k < g->graph_pose.size(); k++) odoms.emplace_back((int)k, g->graph_pose[k]);
+            for (size_t k = 0; k < g->graph_pose.size(); k++)
+                if (!g->graph_gone[k]) odoms.emplace_back((int)k, g->graph_pose[k]);
         }
     }
     return odoms_to_pydict(odoms);
@@ -2256,7 +2378,8 @@ py::dict run_robust_graph_optimization(std::string mode) {
         if (g->graph && !g->graph_odom.empty()) {
             require(lio_graph_remove_gnss_outliers(g->graph, 1.0, 1024, nullptr, 0, nullptr) >= -1, "run_robust_graph_optimization: lio_graph_remove_gnss_outliers failed");
             graph_optimize_locked(g.get(), "run_robust_graph_optimization");
-            for (size_t k = 0; k < g->graph_pose.size(); k++) odoms.emplace_back((int)k, g->graph_pose[k]);
+            for (size_t k = 0; k < g->graph_pose.size(); k++)
+                if (!g->graph_gone[k]) odoms.emplace_back((int)k, g->graph_pose[k]);
         }
     }
     return odoms_to_pydict(odoms);
@@ -2282,7 +2405,7 @@ std::vector<int> add_graph_gnss(int id, py::array_t<double, py::array::c_style |
     }
     py::gil_scoped_release rel;
     std::lock_guard<std::mutex> kl(g->kf_mtx);
-    if (!g->graph || id < 0 || (size_t)id >= g->graph_has_gnss.size() || g->graph_has_gnss[(size_t)id]) return added;
+    if (!g->graph || id < 0 || (size_t)id >= g->graph_has_gnss.size() || g->graph_has_gnss[(size_t)id] || g->graph_gone[(size_t)id]) return added;
     const double threshold = precision < 100.0 ? 10.0 : (precision < 1000.0 ? 20.0 : 50.0);
     const double* last = g->gnss_last;
     const double d[3] = {last[0] - xyz[0], last[1] - xyz[1], last[2] - xyz[2]};
@@ -2354,7 +2477,7 @@ void dump_keyframe(const std::string& directory, uint64_t stamp, int id, py::arr
     write_pcd_binary(directory + "/cloud.pcd", xyzi.data(), n);
     write_keyframe_data(directory, stamp, id, T);
 }
-void dump_odometry(const std::string& directory) { (void)directory; }
+void dump_odometry(const std::string& directory);  // with dump_graph, below
 // ---- dense-map export (graph_utils.cpp:160-200 and 384-446) over lio_cloud: the frames go to the device, are moved into the world frame there
 // and, for save_accumulate_cloud, filtered as one cloud by the device-wide VoxelGrid ----
 // set_export_map_config / export_points / dump_map_points: the reference keeps g_map_config (a static, independent of the SLAM instance).
@@ -2551,12 +2674,9 @@ void dump_map_points(std::string file) {
     if (m == 0) return;
     require(write_pcd_binary(file, out.data(), (size_t)m), "dump_map_points: cannot write the file");
 }
-py::list dump_graph(const std::string& directory) { (void)directory; return py::list(); }
+py::list dump_graph(const std::string& directory);  // below, with the rest of the map's way to disk
 py::list align_pose(double stamp1, double stamp2, py::array_t<double>& estimate1_py, py::array_t<double>& estimate2_py, py::array_t<double>& poses_stamp,
-                    py::list& poses_py) {
-    (void)stamp1; (void)stamp2; (void)estimate1_py; (void)estimate2_py; (void)poses_stamp;
-    return poses_py;
-}
+                    py::list& poses_py);
 void save_undistortion_cloud(std::string file, py::array_t<float>& points, py::dict& points_attr, py::array_t<double>& poses) {
     const std::vector<TumPose> tum = tum_poses(poses);
     undistort_frame(points, points_attr, tum, "save_undistortion_cloud");
@@ -3039,6 +3159,297 @@ void save_render_cloud(std::string file) {
 }
 // test visibility: (outcome, frame N x 4, pose 4 x 4, {camera: pose}) of the last colouration_frame -- outcome -1: refused by get_stamp_pose,
 // else LIO_RENDER_*; _stamp_pose(stamp, start_idx) -> (found, idx, pose) of get_stamp_pose
+// ---- the map's way to disk from mapping mode: dump_graph, dump_odometry, del_graph_vertex, align_pose ---------------------------------------------
+// graph.g2o as g2o's OptimizableGraph::save writes it (tag, ids, the element's own write()): every vertex in rising id, a FIX line behind a
+// fixed one, then the edges.  DEVIATION: numbers go out with 17 significant digits (g2o leaves the stream at its default 6), so that a reader
+// gets the same doubles back; any g2o reader takes both.  <path>.kernels in the format of robust_kernel_io.cpp:72-76 when the record has kernels
+bool write_g2o(const std::string& path, const G2oFile& gf) {
+    std::ofstream f(path);
+    if (!f) return false;
+    f << std::setprecision(17);
+    std::vector<const G2oFile::Vertex*> vs;
+    for (const auto& v : gf.vertices) vs.push_back(&v);
+    std::stable_sort(vs.begin(), vs.end(), [](const G2oFile::Vertex* a, const G2oFile::Vertex* b) { return a->id < b->id; });
+    const std::set<int> fixed(gf.fixed.begin(), gf.fixed.end());
+    for (const auto* v : vs) {
+        f << "VERTEX_SE3:QUAT " << v->id;
+        for (int k = 0; k < 7; k++) f << " " << v->v[k];
+        f << "\n";
+        if (fixed.count(v->id)) f << "FIX " << v->id << "\n";
+    }
+    for (const auto& e : gf.edges) {
+        f << "EDGE_SE3:QUAT " << e.from << " " << e.to;
+        for (int k = 0; k < 7; k++) f << " " << e.m[k];
+        for (int r = 0; r < 6; r++)
+            for (int c = r; c < 6; c++) f << " " << e.info[r * 6 + c];
+        f << "\n";
+    }
+    for (const auto& p : gf.priors) {
+        f << p.tag << " " << p.node;
+        for (double v : p.values) f << " " << v;
+        f << "\n";
+    }
+    if (!f) return false;
+    if (gf.kernels.empty()) return true;
+    std::ofstream k(path + ".kernels");
+    if (!k) return false;
+    k << std::setprecision(17);
+    for (const auto& kn : gf.kernels) {
+        k << kn.vertices.size() << " ";
+        for (int v : kn.vertices) k << v << " ";
+        k << kn.type << " " << kn.delta << "\n";
+    }
+    return (bool)k;
+}
+// a pose as the 7 numbers of g2o's toVectorQT: x y z qx qy qz qw, the quaternion Eigen's Quaterniond(Matrix3d), normalised
+void tq_of(const double T16[16], double v[7]) {
+    Mat4 T;
+    std::memcpy(T.m, T16, sizeof(T.m));
+    double q[4];
+    quat_of(T, q);
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    v[0] = T(0, 3); v[1] = T(1, 3); v[2] = T(2, 3);
+    v[3] = q[1] / n; v[4] = q[2] / n; v[5] = q[3] / n; v[6] = q[0] / n;
+}
+const char* kernel_name(int kernel) { return kernel == LIO_GRAPH_KERNEL_HUBER ? "Huber" : kernel == LIO_GRAPH_KERNEL_DCS2 ? "DCS2" : ""; }
+// test visibility: _write_g2o(path, record) -- the dictionary _read_g2o returns (skipped is not read; priors and kernels may be missing)
+void _write_g2o(std::string path, py::dict rec) {
+    G2oFile gf;
+    for (auto item : py::cast<py::dict>(rec["vertices"])) {
+        G2oFile::Vertex v;
+        v.id = py::cast<int>(item.first);
+        auto a = py::cast<py::array_t<double, py::array::c_style | py::array::forcecast>>(item.second);
+        require(a.size() == 7, "_write_g2o: a vertex is x y z qx qy qz qw");
+        std::memcpy(v.v, a.data(), sizeof(v.v));
+        gf.vertices.push_back(v);
+    }
+    for (auto item : py::cast<py::list>(rec["edges"])) {
+        py::tuple t = py::cast<py::tuple>(item);
+        require(t.size() == 4, "_write_g2o: an edge is (from, to, [7], 6 x 6)");
+        G2oFile::Edge e;
+        e.from = py::cast<int>(t[0]); e.to = py::cast<int>(t[1]);
+        auto m = py::cast<py::array_t<double, py::array::c_style | py::array::forcecast>>(t[2]);
+        auto w = py::cast<py::array_t<double, py::array::c_style | py::array::forcecast>>(t[3]);
+        require(m.size() == 7 && w.size() == 36, "_write_g2o: an edge is (from, to, [7], 6 x 6)");
+        std::memcpy(e.m, m.data(), sizeof(e.m));
+        std::memcpy(e.info, w.data(), sizeof(e.info));
+        gf.edges.push_back(e);
+    }
+    gf.fixed = py::cast<std::vector<int>>(rec["fixed"]);
+    if (rec.contains("priors"))
+        for (auto item : py::cast<py::list>(rec["priors"])) {
+            py::tuple t = py::cast<py::tuple>(item);
+            require(t.size() == 3, "_write_g2o: a prior is (tag, vertex, values)");
+            G2oFile::Prior p;
+            p.tag = py::cast<std::string>(t[0]); p.node = py::cast<int>(t[1]);
+            auto a = py::cast<py::array_t<double, py::array::c_style | py::array::forcecast>>(t[2]);
+            p.values.assign(a.data(), a.data() + a.size());
+            gf.priors.push_back(p);
+        }
+    if (rec.contains("kernels"))
+        for (auto item : py::cast<py::list>(rec["kernels"])) {
+            py::tuple t = py::cast<py::tuple>(item);
+            require(t.size() == 3, "_write_g2o: a kernel is ([vertices], type, delta)");
+            gf.kernels.push_back({py::cast<std::vector<int>>(t[0]), py::cast<std::string>(t[1]), py::cast<double>(t[2])});
+        }
+    require(write_g2o(path, gf), "_write_g2o: cannot write the file");
+}
+// graph_save (hdl_graph_slam_nodelet.cpp:1088-1110): graph.g2o (+ .kernels, GraphSLAM::save) and special_nodes.csv into `directory`, the ids of
+// the SE3 vertices as strings.  [] and no file without a pose graph.  The floor plane is not written: its vertex and edge classes are g2o's own,
+// and the plane of this graph lives in the edge, not in a vertex -- floor_node is -1.  In localisation mode after a merge the merged graph's
+// host record goes out the same way
+py::list dump_graph(const std::string& directory) {
+    py::list out;
+    if (!g) return out;
+    G2oFile gf;
+    bool have = false, ok = true;
+    {
+        py::gil_scoped_release rel;
+        if (g->loc) {
+            std::lock_guard<std::mutex> lk(g->mtx);
+            const Loc& L = *g->loc;
+            if (L.have_mgraph) {
+                have = true;
+                for (const KeyFrameDisk& kf : L.frames) {
+                    G2oFile::Vertex v;
+                    v.id = kf.id;
+                    tq_of(kf.odom.m, v.v);
+                    gf.vertices.push_back(v);
+                }
+                gf.fixed.assign(L.mfixed.begin(), L.mfixed.end());
+                for (const Loc::MergeEdge& me : L.medges) {
+                    G2oFile::Edge e;
+                    e.from = me.a; e.to = me.b;
+                    tq_of(me.M, e.m);
+                    std::memcpy(e.info, me.info, sizeof(e.info));
+                    gf.edges.push_back(e);
+                    if (me.kernel != LIO_GRAPH_KERNEL_NONE) gf.kernels.push_back({{me.a, me.b}, kernel_name(me.kernel), 1.0});
+                }
+            }
+        } else {
+            std::lock_guard<std::mutex> kl(g->kf_mtx);
+            if (g->graph) {
+                have = true;
+                lio_graph* gr = g->graph;
+                const int nn = lio_graph_num_nodes(gr);
+                std::vector<uint8_t> live((size_t)std::max(nn, 1)), fixed((size_t)std::max(nn, 1));
+                std::vector<double> est(16 * (size_t)std::max(nn, 1));
+                require(lio_graph_node_live(gr, live.data(), (uint32_t)nn) == nn && lio_graph_get_fixed(gr, fixed.data(), (uint32_t)nn) == nn &&
+                            lio_graph_estimates(gr, est.data(), (uint32_t)nn) == nn, "dump_graph: reading the nodes failed");
+                for (int n = 0; n < nn; n++) {
+                    if (!live[(size_t)n]) continue;
+                    G2oFile::Vertex v;
+                    v.id = n;
+                    tq_of(&est[16 * (size_t)n], v.v);
+                    gf.vertices.push_back(v);
+                    if (fixed[(size_t)n]) gf.fixed.push_back(n);
+                }
+                const int ne = -lio_graph_edge_records(gr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+                if (ne > 0) {
+                    std::vector<int32_t> from((size_t)ne), to((size_t)ne), kernel((size_t)ne);
+                    std::vector<double> M(16 * (size_t)ne), W(36 * (size_t)ne), delta((size_t)ne);
+                    require(lio_graph_edge_records(gr, nullptr, from.data(), to.data(), M.data(), W.data(), kernel.data(), delta.data(), (uint32_t)ne) == ne,
+                            "dump_graph: lio_graph_edge_records failed");
+                    for (int k = 0; k < ne; k++) {
+                        G2oFile::Edge e;
+                        e.from = from[(size_t)k]; e.to = to[(size_t)k];
+                        tq_of(&M[16 * (size_t)k], e.m);
+                        std::memcpy(e.info, &W[36 * (size_t)k], sizeof(e.info));
+                        gf.edges.push_back(e);
+                        if (kernel[(size_t)k] != LIO_GRAPH_KERNEL_NONE) gf.kernels.push_back({{e.from, e.to}, kernel_name(kernel[(size_t)k]), delta[(size_t)k]});
+                    }
+                }
+                const int np = -lio_graph_priors(gr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+                if (np > 0) {
+                    std::vector<int32_t> node((size_t)np), type((size_t)np), kernel((size_t)np);
+                    std::vector<double> m(4 * (size_t)np), W(9 * (size_t)np), delta((size_t)np);
+                    require(lio_graph_priors(gr, nullptr, node.data(), type.data(), m.data(), nullptr, W.data(), kernel.data(), delta.data(), (uint32_t)np) == np,
+                            "dump_graph: lio_graph_priors failed");
+                    for (int k = 0; k < np; k++) {
+                        if (type[(size_t)k] == LIO_GRAPH_PRIOR_PLANE) continue;
+                        const double* mk = &m[4 * (size_t)k];
+                        const double* Wk = &W[9 * (size_t)k];
+                        G2oFile::Prior p;
+                        p.node = node[(size_t)k];
+                        if (type[(size_t)k] == LIO_GRAPH_PRIOR_XYZ) { p.tag = "EDGE_SE3_PRIORXYZ"; p.values = {mk[0], mk[1], mk[2]}; }
+                        else { p.tag = "EDGE_SE3_PRIORQUAT"; p.values = {mk[3], mk[0], mk[1], mk[2]}; }
+                        for (int r = 0; r < 3; r++)
+                            for (int c = r; c < 3; c++) p.values.push_back(Wk[r * 3 + c]);
+                        gf.priors.push_back(p);
+                        if (kernel[(size_t)k] != LIO_GRAPH_KERNEL_NONE) gf.kernels.push_back({{p.node}, kernel_name(kernel[(size_t)k]), delta[(size_t)k]});
+                    }
+                }
+            }
+        }
+        if (have) {
+            ok = write_g2o(directory + "/graph.g2o", gf);
+            if (ok && gf.kernels.empty()) ok = (bool)std::ofstream(directory + "/graph.g2o.kernels");  // (save_robust_kernels always makes the file)
+            std::ofstream ofs(directory + "/special_nodes.csv");
+            ofs << "anchor_node " << -1 << std::endl << "anchor_edge " << -1 << std::endl << "floor_node " << -1 << std::endl;
+            ok = ok && (bool)ofs;
+        }
+    }
+    require(ok, "dump_graph: cannot write into the directory");
+    std::vector<int> ids;
+    for (const auto& v : gf.vertices) ids.push_back(v.id);
+    std::sort(ids.begin(), ids.end());
+    for (int id : ids) out.append(std::to_string(id));
+    return out;
+}
+// dump_odometry (graph_utils.cpp:133-145): odometrys.txt, `stamp x y z qx qy qz qw` a line in fixed notation with 6 decimals; an empty list
+// still makes the file
+void dump_odometry(const std::string& directory) {
+    std::vector<std::pair<uint64_t, Mat4>> od;
+    if (g) {
+        std::lock_guard<std::mutex> lk(g->mtx);
+        od = g->odometrys;
+    }
+    std::ofstream ofs(directory + "/odometrys.txt");
+    for (const auto& o : od) {
+        double q[4];
+        quat_of(o.second, q);
+        ofs << std::fixed << std::setprecision(6) << (double)o.first / 1000000.0 << " " << o.second(0, 3) << " " << o.second(1, 3) << " " << o.second(2, 3) << " " << q[1] << " "
+            << q[2] << " " << q[3] << " " << q[0] << std::endl;
+    }
+}
+// graph_del_vertex (hdl_graph_slam_nodelet.cpp:868-891): the key frame leaves the list, its vertex and every edge on it leave the graph; here its
+// frame of the detector's bank is retired as well, which is what leaving `keyframes` means to LoopDetector::detect.  Nothing without a graph, a
+// warning for an id the graph does not hold
+void del_graph_vertex(int id) {
+    if (!g) return;
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    if (!g->graph) return;
+    if (id < 0 || (size_t)id >= g->graph_gone.size() || g->graph_gone[(size_t)id]) {
+        std::fprintf(stderr, "slam_wrapper: del_graph_vertex: Vertex ID %d does not exist!!\n", id);
+        return;
+    }
+    require(lio_graph_remove_node(g->graph, id) == LIO_OK, "del_graph_vertex: lio_graph_remove_node failed");
+    if (g->loop) require(lio_loop_retire(g->loop, id) == LIO_OK, "del_graph_vertex: lio_loop_retire failed");
+    g->graph_gone[(size_t)id] = 1;
+    g->graph_updated = false;
+}
+// align_pose (graph_utils.cpp:230-282), statement for statement in f64: the poses between two aligned frames are made relative to the first
+// (from the back of the list forward, so poses[0] is still the original while the others use it), the difference between the estimates' delta
+// and the list's own is spread over the list by time -- with stamp2 - stamp1 as the duration, not the list's span -- as a translation and a
+// rotation vector whose norm goes through a float before the 1e-8 test.  An empty list returns an empty list (the reference reads poses.back())
+py::list align_pose(double stamp1, double stamp2, py::array_t<double>& estimate1_py, py::array_t<double>& estimate2_py, py::array_t<double>& poses_stamp,
+                    py::list& poses_py) {
+    py::list out;
+    std::vector<Mat4> poses;
+    auto mat_of = [](py::handle h, const char* what) {
+        auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(py::reinterpret_borrow<py::object>(h));
+        require(a && a.size() == 16, what);
+        Mat4 T;
+        std::memcpy(T.m, a.data(), sizeof(T.m));
+        return T;
+    };
+    for (auto pose : poses_py) poses.push_back(mat_of(pose, "align_pose: a pose is 4 x 4"));
+    if (poses.empty()) return out;
+    auto st = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(poses_stamp);
+    require(st && (size_t)st.size() >= poses.size(), "align_pose: a stamp for every pose");
+    const double* pose_stamp = st.data();
+    const int n = (int)poses.size();
+    for (int i = n - 1; i >= 0; i--) poses[(size_t)i] = mul(inverse4(poses[0]), poses[(size_t)i]);
+    const Mat4 estimate1 = mat_of(estimate1_py, "align_pose: estimate1 is 4 x 4"), estimate2 = mat_of(estimate2_py, "align_pose: estimate2 is 4 x 4");
+    const Mat4 delta_odom = mul(inverse4(estimate1), estimate2);
+    const Mat4 dd = mul(inverse4(poses.back()), delta_odom);
+    double dq[4];
+    quat_of(dd, dq);
+    // Eigen::AngleAxisd(q): angle = 2 atan2(|vec|, |w|), the axis vec / |vec| with the sign of w; no rotation: angle 0 about x
+    double vn = std::sqrt(dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]), angle = 0, axis[3] = {1, 0, 0};
+    if (vn != 0.0) {
+        angle = 2.0 * std::atan2(vn, std::fabs(dq[0]));
+        if (dq[0] < 0) vn = -vn;
+        for (int i = 0; i < 3; i++) axis[i] = dq[1 + i] / vn;
+    }
+    const double duration = stamp2 - stamp1;
+    for (int i = 0; i < n; i++) {
+        const double ratio = (pose_stamp[i] - pose_stamp[0]) / duration;
+        const double lt[3] = {ratio * dd(0, 3), ratio * dd(1, 3), ratio * dd(2, 3)};
+        const double lr[3] = {ratio * (angle * axis[0]), ratio * (angle * axis[1]), ratio * (angle * axis[2])};
+        const float norm = (float)std::sqrt(lr[0] * lr[0] + lr[1] * lr[1] + lr[2] * lr[2]);
+        Mat4 plus = Mat4::identity();
+        if (!(norm < 1e-8)) {  // Quaterniond(AngleAxisd(norm, lr / norm)).toRotationMatrix()
+            const double a = (double)norm, sh = std::sin(0.5 * a), w = std::cos(0.5 * a);
+            const double x = sh * (lr[0] / a), y = sh * (lr[1] / a), z = sh * (lr[2] / a);
+            const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+            const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+            plus(0, 0) = 1 - (tyy + tzz); plus(0, 1) = txy - twz; plus(0, 2) = txz + twy;
+            plus(1, 0) = txy + twz; plus(1, 1) = 1 - (txx + tzz); plus(1, 2) = tyz - twx;
+            plus(2, 0) = txz - twy; plus(2, 1) = tyz + twx; plus(2, 2) = 1 - (txx + tyy);
+        }
+        for (int r = 0; r < 3; r++) plus(r, 3) = lt[r];
+        poses[(size_t)i] = mul(estimate1, mul(poses[(size_t)i], plus));
+    }
+    for (const Mat4& T : poses) {
+        py::array_t<double> a({4, 4});
+        std::memcpy(a.mutable_data(), T.m, sizeof(T.m));
+        out.append(a);
+    }
+    return out;
+}
+
 py::tuple _colouration_last() {
     auto to_np = [](const Mat4& T) {
         py::array_t<double> a({4, 4});
@@ -3177,6 +3588,7 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("get_color_map", &get_color_map, "get color map");
     m.def("merge_map", &merge_map, "merge map", py::arg("directory"));
     m.def("_read_g2o", &_read_g2o, py::arg("path"));
+    m.def("_write_g2o", &_write_g2o, py::arg("path"), py::arg("record"));
     m.def("_last_merge", &_last_merge);
     m.def("get_graph_map", &get_graph_map, "get graph map");
     m.def("get_graph_edges", &get_graph_edges, "get graph edges");

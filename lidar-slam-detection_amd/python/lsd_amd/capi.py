@@ -69,6 +69,7 @@ SYMBOLS = [
     "lio_graph_num_nodes", "lio_graph_get_fixed", "lio_graph_add_edge", "lio_graph_remove_edge", "lio_graph_optimize", "lio_graph_estimates", "lio_graph_edges",
     "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
     "lio_graph_add_prior", "lio_graph_set_kernel", "lio_graph_priors", "lio_graph_prior_error", "lio_graph_remove_gnss_outliers",
+    "lio_graph_remove_node", "lio_graph_node_live", "lio_graph_edge_records", "lio_loop_retire",
     "lio_render_create", "lio_render_destroy", "lio_render_clear", "lio_render_set_cameras", "lio_render_set_active", "lio_render_frame", "lio_render_size",
     "lio_render_download", "lio_render_download_voxels", "lio_render_download_points", "lio_render_download_last_image", "lio_render_last_times",
 ]
@@ -560,6 +561,10 @@ def lib():
     sig("lio_graph_priors", cint, vp, i32p, i32p, i32p, f64p, f64p, f64p, i32p, f64p, u32)
     sig("lio_graph_prior_error", cint, f64p, cint, f64p, f64p, f64p)
     sig("lio_graph_remove_gnss_outliers", cint, vp, dbl, cint, i32p, u32, gr)
+    sig("lio_graph_remove_node", cint, vp, cint)
+    sig("lio_graph_node_live", cint, vp, u8p, u32)
+    sig("lio_graph_edge_records", cint, vp, i32p, i32p, i32p, f64p, f64p, i32p, f64p, u32)
+    sig("lio_loop_retire", cint, vp, cint)
     sig("lio_render_create", vp, cint, u64, u64)
     sig("lio_render_destroy", None, vp)
     sig("lio_render_clear", cint, vp)

@@ -842,6 +842,10 @@ class LoopDetector:
         T = f64(pose).reshape(4, 4)
         check(lib().lio_loop_set_pose(self.h, int(kid), ptr(T, C.c_double)), "loop set_pose")
 
+    def retire(self, kid):
+        """the frame leaves the matching for good (its id and storage stay): never again a new frame, a candidate or a neighbour"""
+        check(lib().lio_loop_retire(self.h, int(kid)), "loop retire")
+
     def num_keyframes(self):
         q = C.c_int(0)
         n = check(lib().lio_loop_num_keyframes(self.h, C.byref(q)), "loop num_keyframes")
@@ -1117,6 +1121,27 @@ class PoseGraph:
 
     def remove_edge(self, eid):
         check(lib().lio_graph_remove_edge(self.h, int(eid)), "graph remove_edge")
+
+    def remove_node(self, nid):
+        """the node and every edge and prior on it leave the graph; ids stay, the removed id is unknown from here on"""
+        check(lib().lio_graph_remove_node(self.h, int(nid)), "graph remove_node")
+
+    def node_live(self):
+        n = self.num_nodes
+        out = np.zeros(max(n, 1), np.uint8)
+        check(lib().lio_graph_node_live(self.h, ptr(out, C.c_uint8), len(out)), "graph node_live")
+        return out[:n].astype(bool)
+
+    def edge_records(self):
+        """the live binary edges in rising id as they were added: a list of dicts (id, from, to, measurement (4, 4), information (6, 6), kernel, delta)"""
+        n = abs(lib().lio_graph_edge_records(self.h, None, None, None, None, None, None, None, 0))
+        c = max(n, 1)
+        i, a, b, kn = (np.zeros(c, np.int32) for _ in range(4))
+        M, W, dl = np.zeros((c, 4, 4)), np.zeros((c, 6, 6)), np.zeros(c)
+        check(lib().lio_graph_edge_records(self.h, ptr(i, C.c_int32), ptr(a, C.c_int32), ptr(b, C.c_int32), ptr(M, C.c_double), ptr(W, C.c_double), ptr(kn, C.c_int32),
+                                           ptr(dl, C.c_double), c), "graph edge_records")
+        return [{"id": int(i[k]), "from": int(a[k]), "to": int(b[k]), "measurement": M[k].copy(), "information": W[k].copy(), "kernel": int(kn[k]),
+                 "delta": float(dl[k])} for k in range(n)]
 
     @staticmethod
     def _prior_args(kind, measurement, plane):
