@@ -83,8 +83,11 @@ int lio_device_count(void);
  * 20 = lio_render_* (the road-surface colour map of slam/localization/map_render: voxels of floor points painted from camera images -- insert,
  *      projection, z-buffer, depth continuity, bilinear sample, running blend, export).
  * 21 = lio_graph_remove_node, lio_graph_node_live, lio_graph_edge_records, lio_loop_retire (a key frame leaves the map: graph_del_vertex; and
- *      the graph hands back its edges as they were added: graph_save).  A removed node's id, and a retired frame's, is refused as unknown. */
-#define LIO_ABI_VERSION 21
+ *      the graph hands back its edges as they were added: graph_save).  A removed node's id, and a retired frame's, is refused as unknown.
+ * 22 = lio_utm_* / lio_grid_convergence / lio_transform_from_rpyt / lio_quat_of_transform / lio_interpolate_transform / lio_rtk_transform_* /
+ *      lio_rtk_track_* / lio_gnss_queue_* (the GNSS side of mapping mode on the host: UTM projection, the RTK track of RTKM, the graph's GNSS
+ *      queue) and lio_scan_merge_* (several lidars into one frame on the device: mergePoints + preprocessPoints). */
+#define LIO_ABI_VERSION 22
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1697,6 +1700,130 @@ int64_t lio_render_download_points(lio_render*, float* xyz, uint32_t* voxel, flo
 int64_t lio_render_download_last_image(lio_render*, float* depth, int32_t* owner, uint8_t* valid, uint64_t cap, int* rows, int* cols);
 /* device time (HIP events) of the last rendered frame: insert chain, all images, finish + read-back */
 int lio_render_last_times(lio_render*, double* insert_us, double* image_us, double* finish_us);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Geodesy and the RTK track: the GNSS side of mapping mode.  Host code, f64, no device (csrc/geodesy.cpp).
+ * Reference files: UP = sensor_driver/common_lib/cpp_utils/UTMProjector.cpp, SU = slam/common/slam_utils.cpp,
+ * RK = slam/mapping/rtkm/src/rtkm.cpp, HG = slam/backend/hdl_graph_slam/apps/hdl_graph_slam_nodelet.cpp.  Every function restates its
+ * original statement for statement, in the original's order of evaluation; the library is built without contraction.
+ *   lio_utm     UTMProjector.  forward = FromGlobalToLocal (UP:13-55), inverse = FromLocalToGlobal (UP:57-109), longitude0 = GetLongitude0
+ *               (UP:111-117).  Quirks kept: zone width and zone number are ints (UTMProjector.h:13-14); the zone number is fixed by the first
+ *               call (forward: floor(longitude / width); inverse: floor(x / 1000000) - 1 with the width hard-coded to 6) and sticks -- "unset"
+ *               is `zone < 0`, so a zone west of Greenwich is derived again by every call; width / 2 is an integer division;
+ *               f = 1 / 298.257222101; false easting 1000000 (zone + 1) + 500000; scale 0.9996 about 500000.  lio_utm_zone is the zone
+ *               number, -1 on a fresh handle; longitude0 of a fresh handle is -1 * width + width / 2 as in the reference (which warns).
+ *   lio_grid_convergence   get_grid_convergence (UP:119-122): atan(tan((lon - lon0) / 180 pi) sin(lat / 180 pi)) 180 / pi.
+ *   lio_transform_from_rpyt   getTransformFromRPYT (SU:88-96): translation * Rz(yaw) * Rx(pitch) * Ry(roll), degrees through the truncated
+ *               constant 0.01745329251994; row-major 4 x 4.
+ *   lio_quat_of_transform     Eigen's Quaterniond(Matrix3d) of the rotation block, (w, x, y, z).
+ *   lio_interpolate_transform interpolateTransform (SU:126-161) = the tail of RTKM::getInterpolatedTransform (RK:180-210): translation and
+ *               angle-axis of pre^-1 next scaled by `ratio`, kEpsilon 1e-8.
+ *   lio_rtk_transform_utm     computeRTKTransform(projector, data, zero_utm) (SU:112-124): UTM less zero_utm, altitude less zero_utm[2],
+ *               yaw = -(heading - grid convergence at the projector's longitude0), getTransformFromRPYT(x, y, z, yaw, pitch, roll).
+ *   lio_rtk_transform_origin  RTKM::computeRTKTransform(origin, data) (RK:125-139): the same with the origin fix projected again on every
+ *               call and its altitude subtracted.
+ *   lio_rtk_track   RTKM's mTimedInsData (RK:37-54, 91-95, 141-213): a map from stamp to fix (a fix with a stamp already held replaces it)
+ *               with a projector of its own.  set_origin: the first one wins (1 = taken, 0 = one was set), T = the origin's own pose
+ *               (mLastOdom).  feed: stored iff rtk_valid and the origin is set (1 / 0).  interpolate = getInterpolatedTransform, its
+ *               refusals in the reference's order: no origin; [an exact stamp answers here: LIO_RTK_EXACT]; fewer than two fixes; stamp before
+ *               the first; stamp after the last.  Otherwise the pair around the stamp with ratio = (t - pre) / (next - pre) (no + 1 here)
+ *               through lio_interpolate_transform.  T is written only when the track answers.
+ *   lio_gnss_queue  the graph's gps_queue (HG:141-156, 349-460, 653-660) up to the point where an edge is added.  set_origin: zero_utm =
+ *               (easting, northing, altitude [- z of the last key frame's estimate when there is one]); every call replaces it.  push =
+ *               gps_callback.  flush = flush_gps_queue over the key frames' stamps and has-fix flags (keyframe->utm_coord is set), in the
+ *               reference's order: nothing without key frames or fixes; the cursor walk (a key frame later than the last fix ends it, one
+ *               before the cursor's fix or with a fix is passed over); the bracket dt <= 0 && dt2 >= 0 && dt2 - dt < 2.0 (none found ends
+ *               the walk); unequal precisions pass the key frame over; ratio = (t - pre) / (next - pre + 1) (HG:654-655); both fixes through
+ *               lio_rtk_transform_utm and lio_interpolate_transform; z = 0 for dimension 2; the 10 / 20 / 50 m gate (precision < 100, < 1000,
+ *               else) against last_xyz, the last accepted fix (gps_last_update_pose: the caller's, read and written; all zero = none yet);
+ *               an accepted match sets the key frame's flag and last_xyz and is written to `out`; at the end every fix with a stamp <= the
+ *               last key frame's is erased (upper_bound).  The quaternion is Quaterniond(rotation).normalize() as (x, y, z, w).  The
+ *               reference flushes against `keyframes`, not `new_keyframes`: a key frame added in this pass is handed in at the next one.
+ *               Returns the matches, or -(matches) when cap is too small -- the queue and the flags have moved all the same: cap = n_kf
+ *               always suffices.  LIO_E_STATE without an origin.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_utm lio_utm;
+typedef struct lio_rtk_track lio_rtk_track;
+typedef struct lio_gnss_queue lio_gnss_queue;
+typedef struct lio_rtk_fix {  /* the fields of RTKType (slam/common/mapping_types.h:86-135) the GNSS side reads */
+    uint64_t stamp_us;
+    double latitude, longitude, altitude; /* degrees, degrees, metres */
+    double heading, pitch, roll;          /* degrees */
+    double precision;                     /* RTKType::precision (default 100) */
+    int32_t dimension;                    /* RTKType::dimension: 2, 3 or 6 (default 2) */
+    int32_t reserved;
+} lio_rtk_fix;
+typedef struct lio_gnss_match {
+    int32_t keyframe;  /* index into the arrays handed to flush */
+    int32_t dimension;
+    uint64_t first_stamp_us, second_stamp_us; /* the pair of fixes around the key frame */
+    double xyz[3];
+    double quat[4];    /* x, y, z, w */
+    double precision;
+} lio_gnss_match;
+#define LIO_RTK_INTERPOLATED 0
+#define LIO_RTK_EXACT 1
+#define LIO_RTK_NO_ORIGIN 2
+#define LIO_RTK_TOO_FEW 3
+#define LIO_RTK_EARLY 4
+#define LIO_RTK_LATE 5
+lio_utm* lio_utm_create(int zone_width);
+void lio_utm_destroy(lio_utm*);
+int lio_utm_zone(const lio_utm*);
+int lio_utm_forward(lio_utm*, double latitude, double longitude, double* x, double* y);
+int lio_utm_inverse(lio_utm*, double x, double y, double* latitude, double* longitude);
+double lio_utm_longitude0(const lio_utm*);
+double lio_grid_convergence(double longitude0, double lat, double lon);
+void lio_transform_from_rpyt(double x, double y, double z, double yaw, double pitch, double roll, double T[16]);
+void lio_quat_of_transform(const double T[16], double wxyz[4]);
+void lio_interpolate_transform(const double pre[16], const double next[16], double ratio, double out[16]);
+int lio_rtk_transform_utm(lio_utm*, const lio_rtk_fix* fix, const double zero_utm[3], double T[16]);
+int lio_rtk_transform_origin(lio_utm*, const lio_rtk_fix* origin, const lio_rtk_fix* fix, double T[16]);
+lio_rtk_track* lio_rtk_track_create(void);
+void lio_rtk_track_destroy(lio_rtk_track*);
+int lio_rtk_track_set_origin(lio_rtk_track*, const lio_rtk_fix* rtk, double T[16]);
+int lio_rtk_track_origin(const lio_rtk_track*, lio_rtk_fix* out);
+int lio_rtk_track_feed(lio_rtk_track*, int rtk_valid, const lio_rtk_fix* fix);
+int lio_rtk_track_size(const lio_rtk_track*);
+int lio_rtk_track_interpolate(const lio_rtk_track*, uint64_t stamp_us, double T[16]);
+lio_gnss_queue* lio_gnss_queue_create(void);
+void lio_gnss_queue_destroy(lio_gnss_queue*);
+int lio_gnss_queue_set_origin(lio_gnss_queue*, const lio_rtk_fix* rtk, int have_keyframe, double last_keyframe_z, double zero_utm[3]);
+int lio_gnss_queue_push(lio_gnss_queue*, const lio_rtk_fix* fix);
+int lio_gnss_queue_size(const lio_gnss_queue*);
+/* the stamps of the fixes held, in order: the count, or -(count) when cap is too small */
+int lio_gnss_queue_stamps(const lio_gnss_queue*, uint64_t* stamps, uint32_t cap);
+int lio_gnss_queue_flush(lio_gnss_queue*, const uint64_t* kf_stamps, uint8_t* kf_has_fix, uint32_t n_kf, double last_xyz[3], lio_gnss_match* out,
+                         uint32_t cap);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Several lidars into one frame on the device (csrc/scanmerge.hip): mergePoints (slam/common/slam_utils.cpp:249-273) followed by
+ * preprocessPoints (slam/common/slam_base.h:83-85) as RTKM::feedPointData calls them (slam/mapping/rtkm/src/rtkm.cpp:105-109), in one pass.
+ *   input    L clouds (1 <= L <= 16), cloud 0 the base; each n_l points (x, y, z, intensity) f32, a uint32 stamp per point (us since the
+ *            cloud's header) and a uint64 header stamp (us); scan_period_us (<= 2^32 - 1); the static transform (row-major 4 x 4 f64).
+ *   keep     the base's points all, ungated.  For every other cloud time_shift = double(header_l) - double(header_0); stamp =
+ *            double(stamp_i) + time_shift; kept iff stamp >= 0 && stamp <= double(scan_period_us) (slam_utils.cpp:261-264); the kept point's
+ *            stamp becomes uint32_t(stamp) (:265).  early = stamp < 0, late = stamp > scan_period: counted per cloud.
+ *   order    the base, then the clouds in the order given (the caller hands them in std::map order of their names), each in input order:
+ *            a stable compaction.
+ *   frame    every output point through pcl::transformPointCloud with a Matrix4d: the Matrix4d rule of lio_cloud_append_* (f64, terms left
+ *            to right, one cast to f32, no contraction), by the same device function.  Intensity passes through.  Non-finite points are
+ *            neither dropped nor counted: mergePoints has no such test.
+ *   not carried   the point attribute's `id` column (PointAttr::id): nothing downstream reads it.  The merged header stamp is the base's.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_scan_merge lio_scan_merge;
+lio_scan_merge* lio_scan_merge_create(int device, uint32_t max_clouds, uint64_t max_points);
+void lio_scan_merge_destroy(lio_scan_merge*);
+int lio_scan_merge_set_transform(lio_scan_merge*, const double T[16]);
+/* uploads the clouds, merges them; kept / early / late: n_clouds entries each or NULL (the base: kept = n_0, 0, 0); n_out: points of the frame */
+int lio_scan_merge_run_host(lio_scan_merge*, uint32_t n_clouds, const float* const* xyzi, const uint32_t* const* stamps, const uint32_t* n_points,
+                            const uint64_t* header_us, uint64_t scan_period_us, uint32_t* kept, uint32_t* early, uint32_t* late, uint64_t* n_out);
+/* the frame of the last run: n x 4 f32 and n stamps; returns n, or -n when cap (points) is too small */
+int64_t lio_scan_merge_download(lio_scan_merge*, float* xyzi, uint32_t* stamps, uint64_t cap);
+/* the same on the device (float4 per point), valid until the next run on this handle */
+const void* lio_scan_merge_device(lio_scan_merge*, const uint32_t** d_stamps, uint64_t* n);
+/* device time (HIP events) of the last run: the uploads, count + scan + write + the count's read-back */
+int lio_scan_merge_last_times(lio_scan_merge*, double* upload_us, double* merge_us);
 
 #ifdef __cplusplus
 }

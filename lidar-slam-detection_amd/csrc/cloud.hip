@@ -126,22 +126,7 @@ int exclusive_scan(hipStream_t st, uint32_t* data, uint64_t m, uint32_t* aux) {
 }
 
 // ---- append: transform, band, stable compaction --------------------------------------------------------------------------------------------
-struct XformArgs {
-    double m[12];  // rows 0..2 of the row-major 4 x 4
-    double zmin, zmax;
-    float scale;   // intensity factor (numpy_to_pointcloud(.., multiply)); 1 = left alone
-    int band;      // keep only zmin <= z <= zmax (compared in f64, as `p.z >= g_map_config.z_min` with double bounds)
-};
-
-__device__ __forceinline__ float4 xform(float4 p, const XformArgs& a) {
-    const double x = p.x, y = p.y, z = p.z;
-    float4 o;
-    o.x = (float)(((a.m[0] * x + a.m[1] * y) + a.m[2] * z) + a.m[3]);
-    o.y = (float)(((a.m[4] * x + a.m[5] * y) + a.m[6] * z) + a.m[7]);
-    o.z = (float)(((a.m[8] * x + a.m[9] * y) + a.m[10] * z) + a.m[11]);
-    o.w = (a.scale != 1.0f) ? p.w * a.scale : p.w;
-    return o;
-}
+// (XformArgs and xform, the Matrix4d rule of the append, live in device_prims.h: scanmerge.hip applies the same function)
 __device__ __forceinline__ bool keep(const float4& o, const XformArgs& a) { return !a.band || ((double)o.z >= a.zmin && (double)o.z <= a.zmax); }
 
 // kept points per tile (band only)

@@ -86,6 +86,26 @@ __device__ __forceinline__ void queue_long_run(bool is_long, uint32_t v, uint32_
     }
 }
 
+// ---- the Matrix4d rule ------------------------------------------------------------------------------------------------------------------------
+// pcl::transformPointCloud(in, out, Matrix4d) (PCL 1.9.1 transforms.hpp) as lio_cloud_append_* and lio_scan_merge_* apply it: per point in
+// f64, terms left to right, no contraction (-ffp-contract=off), one cast to f32; non-finite points are transformed too
+struct XformArgs {
+    double m[12];  // rows 0..2 of the row-major 4 x 4
+    double zmin, zmax;
+    float scale;   // intensity factor (numpy_to_pointcloud(.., multiply)); 1 = left alone
+    int band;      // keep only zmin <= z <= zmax (compared in f64, as `p.z >= g_map_config.z_min` with double bounds)
+};
+
+__device__ __forceinline__ float4 xform(float4 p, const XformArgs& a) {
+    const double x = p.x, y = p.y, z = p.z;
+    float4 o;
+    o.x = (float)(((a.m[0] * x + a.m[1] * y) + a.m[2] * z) + a.m[3]);
+    o.y = (float)(((a.m[4] * x + a.m[5] * y) + a.m[6] * z) + a.m[7]);
+    o.z = (float)(((a.m[8] * x + a.m[9] * y) + a.m[10] * z) + a.m[11]);
+    o.w = (a.scale != 1.0f) ? p.w * a.scale : p.w;
+    return o;
+}
+
 // ---- stable stream compaction ----------------------------------------------------------------------------------------------------------------
 // A workgroup of kThreads owns tile blockIdx.x; item r of thread tid is i = blockIdx.x * kTile + r * kThreads + tid.  The caller's count
 // kernel ends with compact_tile_count, the host calls compact_finish, the caller's write kernel hands its keep bits to compact_tile_write.

@@ -15,9 +15,11 @@
 // The dense-map export (set_export_map_config / export_points / dump_map_points, accumulate_cloud / save_accumulate_cloud,
 // save_undistortion_cloud: graph_utils.cpp:160-200, 384-446) runs on the device over lio_cloud_* (csrc/cloud.hip), texture_mesh
 // (graph_utils.cpp:449-501) over lio_knn_index_* (csrc/knn_index.hip).
-// Off the hot path (graph back end, GNSS, colouration: SURVEY.md section 2 OUT-OF-SCOPE, Appendix B): type-correct minimal
-// implementations -- empty dict / list, identity 4 x 4, stored-and-returned settings -- so that slam.py and map_manager.py run
-// unchanged.  They are listed in INTEGRATION.md.
+// The GNSS side of mapping mode (SLAM::run's GNSS lines, HDL_FastLIO::setOrigin / feedInsData, the method RTKM: slam.cpp:280-292,
+// fastlio.cpp:177-188, slam/mapping/rtkm/src/rtkm.cpp) runs over lio_utm_* / lio_rtk_track_* / lio_gnss_queue_* (csrc/geodesy.cpp, host) and
+// lio_scan_merge_* (csrc/scanmerge.hip): set_gnss, init_slam(method = "RTKM").
+// Off the hot path (what SURVEY.md section 2 and Appendix B leave out): type-correct minimal implementations -- empty dict / list,
+// identity 4 x 4, stored-and-returned settings -- so that slam.py and map_manager.py run unchanged.  They are listed in INTEGRATION.md.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -83,17 +85,11 @@ Mat4 rigid_inverse(const Mat4& a) {  // [R t; 0 1]^-1 = [R^T  -R^T t; 0 1]
     for (int i = 0; i < 3; i++) r(i, 3) = -(r(i, 0) * a(0, 3) + r(i, 1) * a(1, 3) + r(i, 2) * a(2, 3));
     return r;
 }
-// getTransformFromRPYT (slam_utils.cpp:89-96): translation * Rz(yaw) * Rx(pitch) * Ry(roll), angles in degrees
+// getTransformFromRPYT (slam_utils.cpp:89-96): translation * Rz(yaw) * Rx(pitch) * Ry(roll), angles in degrees (the library's: csrc/geodesy.cpp)
 Mat4 transform_from_rpyt(double x, double y, double z, double yaw, double pitch, double roll) {
-    const double cy = std::cos(yaw * kAng2Rad), sy = std::sin(yaw * kAng2Rad);
-    const double cp = std::cos(pitch * kAng2Rad), sp = std::sin(pitch * kAng2Rad);
-    const double cr = std::cos(roll * kAng2Rad), sr = std::sin(roll * kAng2Rad);
-    Mat4 Rz = Mat4::identity(), Rx = Mat4::identity(), Ry = Mat4::identity(), T = Mat4::identity();
-    Rz(0, 0) = cy; Rz(0, 1) = -sy; Rz(1, 0) = sy; Rz(1, 1) = cy;
-    Rx(1, 1) = cp; Rx(1, 2) = -sp; Rx(2, 1) = sp; Rx(2, 2) = cp;
-    Ry(0, 0) = cr; Ry(0, 2) = sr; Ry(2, 0) = -sr; Ry(2, 2) = cr;
-    T(0, 3) = x; T(1, 3) = y; T(2, 3) = z;
-    return mul(mul(mul(T, Rz), Rx), Ry);
+    Mat4 T;
+    lio_transform_from_rpyt(x, y, z, yaw, pitch, roll, T.m);
+    return T;
 }
 // getRPYTfromTransformFrom (slam_utils.cpp:98-110): Eigen's MatrixBase::eulerAngles(2, 0, 1) of the rotation block (Geometry/EulerAngles.h,
 // the Tait-Bryan branch with a0 = 2, a1 = 0, a2 = 1: even permutation, i = 2, j = 0, k = 1, result negated), in degrees
@@ -260,11 +256,116 @@ struct Slam {
     lio_render* painter = nullptr;
     bool painter_stale = true;            // the cameras or the static transform changed since the painter got them
     uint32_t colour_seed = 0;             // of the ground test's draws (lio_ground)
+    // the GNSS side of mapping mode (SLAM::run, slam.cpp:280-292; HDL_FastLIO::setOrigin / feedInsData, fastlio.cpp:177-188): off unless
+    // set_gnss(true) / LSD_AMD_GNSS=1.  On: the first valid fix sets the map origin, every valid fix goes to the graph's GNSS queue, and
+    // update_odom() flushes the queue against the graph's key frames into priors.  The queue is guarded by kf_mtx
+    bool gnss = false;
+    int ins_dim = 2;                      // SLAM::mInsDim (set_ins_config's ins_type)
+    lio_gnss_queue* gnss_queue = nullptr;
+    // method = "RTKM" (slam/mapping/rtkm/src/rtkm.cpp): poses straight from the RTK track, the lidars merged into one frame on the device;
+    // no FastLIO engine.  Guarded by mtx
+    bool rtkm = false, rtkm_ready = false;
+    lio_rtk_track* track = nullptr;
+    lio_scan_merge* merger = nullptr;
+    uint64_t merger_cap = 0;
+    Mat4 rtkm_last_odom = Mat4::identity();  // mLastOdom
+    std::vector<float> merged_pts;           // the last merged frame (INS frame) and its stamps
+    std::vector<uint32_t> merged_stamps;
+    // localisation mode: SLAM::mProjector and mZeroUtm (slam.cpp:159-166) of a loaded map that has an origin
+    lio_utm* utm = nullptr;
+    bool have_zero_utm = false;
+    double zero_utm[3] = {0, 0, 0};
 };
 std::unique_ptr<Slam> g;  // one global instance per process, like the reference's slam_ptr (slam_wrapper.cpp:4)
 
 void require(bool ok, const char* what) {
     if (!ok) throw std::runtime_error(std::string("slam_wrapper: ") + what + (lio_last_error()[0] ? std::string(": ") + lio_last_error() : std::string()));
+}
+
+// ---- the GNSS side shared by both mapping methods ---------------------------------------------------------------------------------------------
+// pydict_to_rtk (py_utils.cpp:214-242), as far as the GNSS side reads it; a missing key is 0 (the reference throws)
+struct Fix {
+    lio_rtk_fix f = lio_rtk_fix();
+    int status = 0;
+    bool has_stamp = false;
+    std::string sensor;
+};
+Fix fix_of(py::dict& rtk_dict) {
+    Fix x;
+    auto num = [&](const char* k) { return rtk_dict.contains(k) ? py::cast<double>(rtk_dict[k]) : 0.0; };
+    x.f.latitude = num("latitude"); x.f.longitude = num("longitude"); x.f.altitude = num("altitude");
+    x.f.heading = num("heading"); x.f.pitch = num("pitch"); x.f.roll = num("roll");
+    x.f.dimension = 2; x.f.precision = 100.0;  // RTKType's defaults (mapping_types.h:107-108)
+    if (rtk_dict.contains("Status")) x.status = py::cast<int>(rtk_dict["Status"]);
+    if (rtk_dict.contains("timestamp")) { x.f.stamp_us = py::cast<uint64_t>(rtk_dict["timestamp"]); x.has_stamp = true; }
+    if (rtk_dict.contains("Sensor")) x.sensor = py::cast<std::string>(rtk_dict["Sensor"]);
+    return x;
+}
+// SLAM::preprocessInsData (slam.cpp:194-271): the validity filter; a valid fix leaves with the configured dimension and its status' precision
+bool preprocess_ins(Slam* s, uint64_t timestamp, Fix& x) {
+    if (x.status == 0 && std::fabs(x.f.longitude) < 1e-4 && std::fabs(x.f.latitude) < 1e-4) {
+        const double lost = timestamp / 1000000.0 - s->last_ins_timestamp;
+        if (s->last_ins_priority != -1 && lost >= 1.0) s->last_ins_priority = -1;
+        return false;
+    }
+    if (s->rtkm) return true;  // "don't check the status when doing RTK Mapping"
+    const Slam::InsCfg* match = nullptr;
+    for (const auto& c : s->ins_cfg) if (c.status == x.status) { match = &c; break; }
+    if (!match) for (const auto& c : s->ins_cfg) if (c.status == -1) { match = &c; break; }
+    const int mp = match ? match->priority : -1;
+    const double now = x.f.stamp_us / 1000000.0;
+    int priority = -1;
+    if (mp == s->last_ins_priority) { priority = mp; s->last_ins_timestamp = now; }
+    else if (mp < s->last_ins_priority) { priority = mp; s->last_ins_priority = mp; s->last_ins_timestamp = now; }
+    else {
+        const double keep = now - s->last_ins_timestamp;
+        if (keep >= match->stable_time) { priority = mp; s->last_ins_priority = mp; s->last_ins_timestamp = now; }
+        else priority = s->last_ins_priority;
+    }
+    if (priority < 0) return false;
+    x.f.dimension = s->ins_dim;
+    for (const auto& c : s->ins_cfg) if (c.priority == priority) x.f.precision = c.precision;
+    return true;
+}
+// SLAM::setOrigin -> mSlam->setOrigin (HDL_FastLIO::setOrigin, fastlio.cpp:177-183: graph_set_origin; RTKM::setOrigin, rtkm.cpp:37-54): the
+// first one wins, whether it comes from a fix or from set_map_origin.  Called with the GIL held and no mutex
+void slam_set_origin(Slam* s, const lio_rtk_fix& f) {
+    if (s->origin_set) return;
+    const double v[6] = {f.latitude, f.longitude, f.altitude, f.heading, f.pitch, f.roll};
+    std::memcpy(s->origin, v, sizeof(v));
+    s->origin_set = true;
+    if (s->rtkm) {
+        std::lock_guard<std::mutex> lk(s->mtx);
+        if (!s->track) s->track = lio_rtk_track_create();
+        require(lio_rtk_track_set_origin(s->track, &f, s->rtkm_last_odom.m) >= 0, "set origin: lio_rtk_track_set_origin failed");
+    } else if (s->gnss && !s->loc) {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(s->kf_mtx);
+        if (!s->gnss_queue) s->gnss_queue = lio_gnss_queue_create();
+        // set_origin (hdl_graph_slam_nodelet.cpp:141-156): the altitude less the z of the last key frame's estimate
+        int last = (int)s->graph_pose.size() - 1;
+        while (last >= 0 && s->graph_gone[(size_t)last]) last--;
+        require(lio_gnss_queue_set_origin(s->gnss_queue, &f, last >= 0, last >= 0 ? s->graph_pose[(size_t)last](2, 3) : 0.0, nullptr) == LIO_OK,
+                "set origin: lio_gnss_queue_set_origin failed");
+    }
+}
+// SLAM::run's GNSS lines (slam.cpp:280-292) for one fix: the validity filter, the origin, feedInsData of the method.  With the switch off and
+// FastLIO only the filter runs (as before); its answer goes back to the caller for the velocity hand-over
+bool feed_gnss(Slam* s, uint64_t timestamp, Fix& x) {
+    const bool valid = preprocess_ins(s, timestamp, x);
+    if (!s->rtkm && !s->gnss) return valid;
+    if (valid && !s->origin_set) slam_set_origin(s, x.f);
+    if (s->rtkm) {  // RTKM::feedInsData (rtkm.cpp:91-95); nothing goes to the graph's queue
+        std::lock_guard<std::mutex> lk(s->mtx);
+        if (!s->track) s->track = lio_rtk_track_create();
+        require(lio_rtk_track_feed(s->track, valid ? 1 : 0, &x.f) >= 0, "lio_rtk_track_feed failed");
+    } else if (valid) {  // enqueue_graph_gps (hdl_graph_slam_nodelet.cpp:800-804)
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(s->kf_mtx);
+        if (!s->gnss_queue) s->gnss_queue = lio_gnss_queue_create();
+        require(lio_gnss_queue_push(s->gnss_queue, &x.f) == LIO_OK, "lio_gnss_queue_push failed");
+    }
+    return valid;
 }
 
 
@@ -771,9 +872,12 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
                    float dist_threshold, float degree_threshold, float frame_range) {
     // slam.py hands in method = "Localization" when the mode is not "mapping" (slam/slam.py:12); SLAM::SLAM then builds Locate::Localization
     const bool localization = mode == "localization" || method == "Localization";
-    if (!localization && method != "FastLIO")
-        throw std::runtime_error("slam_wrapper: only the FastLIO odometry path and the localisation mode are built on the device (method=" + method + ")");
+    if (!localization && method != "FastLIO" && method != "RTKM")
+        throw std::runtime_error("slam_wrapper: only the FastLIO and RTKM mapping methods and the localisation mode are built on the device (method=" + method + ")");
     g.reset(new Slam());
+    g->rtkm = !localization && method == "RTKM";
+    const char* gnss_env = std::getenv("LSD_AMD_GNSS");
+    g->gnss = gnss_env && gnss_env[0] == '1';
     g->mode = localization ? "localization" : mode;
     g->method = method;
     g->map_path = map_path;
@@ -807,6 +911,21 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
             else if (s.length() < 2 || s[1] != '-') cam = cam || true;
             else if (g->lidar.empty()) g->lidar = s;
         }
+        return py::cast(g->sensors);
+    }
+    if (g->rtkm) {
+        // RTKM::setSensors (rtkm.cpp:56-89): RTK and IMU first; without RTK nothing else (no lidar); camera names pass; the first "n-" name is
+        // the base lidar
+        for (auto& s : in) {
+            if (s == "RTK") { g->sensors.push_back(s); g->use_gps = true; }
+            else if (s == "IMU") { g->sensors.push_back(s); g->use_imu = true; }
+        }
+        if (g->use_gps)
+            for (auto& s : in) {
+                if (s == "RTK" || s == "IMU") continue;
+                g->sensors.push_back(s);
+                if (!(s.length() < 2 || s[1] != '-') && g->lidar.empty()) g->lidar = s;
+            }
         return py::cast(g->sensors);
     }
     // HDL_FastLIO::setSensors (fastlio.cpp:119-151): RTK and IMU first; without an IMU nothing else; the first "n-" name is the lidar
@@ -852,6 +971,21 @@ void read_odometrys(const std::string& map_path, std::vector<std::pair<uint64_t,
     }
 }
 
+namespace {
+struct MapInfo { double origin[6] = {0, 0, 0, 0, 0, 0}; int coordinate = 0; bool origin_set = false; };
+bool read_map_info(const std::string& map_path, MapInfo& mi) {  // MapLoader::loadMapOrigin (map_loader.cpp:180-221)
+    std::ifstream fs(map_path + "/graph/map_info.txt");
+    if (!fs) return false;
+    for (int i = 0; i < 6; i++) fs >> mi.origin[i];
+    double c = 0;
+    fs >> c;
+    mi.coordinate = (int)c;
+    mi.origin_set = false;
+    for (int i = 0; i < 6; i++) mi.origin_set = mi.origin_set || !(std::fabs(mi.origin[i]) < 1e-4);
+    return true;
+}
+}  // namespace
+
 bool setup_slam() {
     require((bool)g, "init_slam first");
     if (g->loc) load_keyframes(g->map_path, g->loc->frames);  // host side of MapLoader: get_graph_map serves the key frames whatever follows
@@ -861,7 +995,23 @@ bool setup_slam() {
         read_odometrys(g->map_path, g->odometrys);
     }
     if (lio_device_count() < 1) return false;  // the reference logs and returns false from setup() when the back end cannot start
-    if (g->loc) return loc_setup(g.get());
+    if (g->loc) {
+        // SLAM::setup (slam.cpp:159-166): the loaded map's origin, projected once, is mZeroUtm
+        MapInfo mi;
+        if (read_map_info(g->map_path, mi) && mi.origin_set) {
+            if (!g->utm) g->utm = lio_utm_create(6);
+            require(g->utm != nullptr && lio_utm_forward(g->utm, mi.origin[0], mi.origin[1], &g->zero_utm[0], &g->zero_utm[1]) == LIO_OK, "setup_slam: the map origin's projection failed");
+            g->zero_utm[2] = mi.origin[2];
+            g->have_zero_utm = true;
+        }
+        return loc_setup(g.get());
+    }
+    if (g->rtkm) {  // RTKM::init (rtkm.cpp:22-31): mLastOdom = identity; no FastLIO engine.  The merge handle is made at the first frame
+        std::lock_guard<std::mutex> lk(g->mtx);
+        if (!g->track) g->track = lio_rtk_track_create();
+        g->rtkm_ready = g->track != nullptr;
+        return g->rtkm_ready;
+    }
     // HDL_FastLIO::init (fastlio.cpp:153-171): T_imu_ins = T_imu * T_static^-1 is the (INS-frame cloud) -> IMU extrinsic
     g->T_imu_ins = mul(g->T_imu, rigid_inverse(g->T_static));
     g->T_imu_ins_inv = rigid_inverse(g->T_imu_ins);
@@ -886,6 +1036,10 @@ void deinit_slam() {
     if (g->graph) lio_graph_destroy(g->graph);
     if (g->floor_ground) lio_ground_destroy(g->floor_ground);
     if (g->painter) lio_render_destroy(g->painter);
+    if (g->gnss_queue) lio_gnss_queue_destroy(g->gnss_queue);
+    if (g->track) lio_rtk_track_destroy(g->track);
+    if (g->merger) lio_scan_merge_destroy(g->merger);
+    if (g->utm) lio_utm_destroy(g->utm);
     g->loc.reset(nullptr);
     g.reset(nullptr);
 }
@@ -1078,10 +1232,16 @@ py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, 
         heading = -heading;
     }
     if (heading < 0) heading += 360;
+    // slam.cpp:335-342: the inverse projection of zero_utm + odom once the localiser is inited and the map has an origin; zeros otherwise
+    double lat = 0.0, lon = 0.0, alt = 0.0;
+    if (inited && s->have_zero_utm) {
+        require(lio_utm_inverse(s->utm, s->zero_utm[0] + out_pose(0, 3), s->zero_utm[1] + out_pose(1, 3), &lat, &lon) == LIO_OK, "process: the inverse projection failed");
+        alt = s->zero_utm[2] + out_pose(2, 3);
+    }
     py::dict pose;
-    pose["latitude"] = 0.0;   // (no map origin / UTM projection without the GNSS side: slam.cpp:338-342)
-    pose["longitude"] = 0.0;
-    pose["altitude"] = 0.0;
+    pose["latitude"] = lat;
+    pose["longitude"] = lon;
+    pose["altitude"] = alt;
     pose["heading"] = heading;
     pose["pitch"] = pitch;
     pose["roll"] = roll;
@@ -1099,59 +1259,62 @@ py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, 
     return data;
 }
 
+// what process() does with a fix in mapping mode, and nothing else (_push_gnss calls it too).
+// SLAM::run (slam.cpp:283-296): preprocessInsData's validity test, the origin and the method's feedInsData (feed_gnss), then for FastLIO
+// fastlio_ins_enqueue (fastlio.cpp:185-187, laserMapping.cpp:417-441): the INS velocity, ENU -> ego -> IMU, third component zeroed -- IMU
+// initialisation seeds the state's velocity from it (IMU_Processing.hpp:201-204), the wheel-speed rows read it
+void feed_fix(Slam* s, py::dict& rtk_dict, Fix& fix, uint64_t timestamp) {
+    if (!s->use_gps || !fix.has_stamp) return;
+    const bool gnss_side = s->rtkm || s->gnss;
+    if (!rtk_dict.contains("Ve") && !gnss_side) return;
+    const bool valid = feed_gnss(s, timestamp, fix);
+    if (s->rtkm || !s->engine || !rtk_dict.contains("Ve")) return;
+    if (valid || fix.sensor.find("Wheel") != std::string::npos) {
+        const double hd = fix.f.heading, pt = fix.f.pitch, rl = fix.f.roll;
+        const double ve[3] = {py::cast<double>(rtk_dict["Ve"]), rtk_dict.contains("Vn") ? py::cast<double>(rtk_dict["Vn"]) : 0.0,
+                              rtk_dict.contains("Vu") ? py::cast<double>(rtk_dict["Vu"]) : 0.0};
+        const Mat4 Tve = rigid_inverse(transform_from_rpyt(0, 0, 0, -hd, pt, rl));
+        double ego[3], vi[3];
+        for (int r = 0; r < 3; r++) ego[r] = Tve(r, 0) * ve[0] + Tve(r, 1) * ve[1] + Tve(r, 2) * ve[2];
+        for (int r = 0; r < 3; r++) vi[r] = s->T_imu_ins(r, 0) * ego[0] + s->T_imu_ins(r, 1) * ego[1] + s->T_imu_ins(r, 2) * ego[2];
+        vi[2] = 0.0;  // "body up speed of INS is not accurate"
+        lio_fastlio_ins_enqueue(s->engine, fix.f.stamp_us / 1000000.0, vi);
+    }
+}
+
+// the frame of process() into the key-frame selector (SLAM::runMappingThread -> enqueue_graph -> cloud_callback, slam.cpp:398-411,
+// hdl_graph_slam_nodelet.cpp:163-246) with its odometry pose and its delta; no pose list (the delta branch).  kf_mtx is held
+void push_frame_locked(Slam* s, const float* pts, const uint32_t* stamps, uint32_t n, uint64_t header_stamp, const Mat4& pose, const Mat4& delta) {
+    if (!s->keyframer) {
+        lio_keyframer_params kp;
+        lio_keyframer_default_params(&kp);
+        kp.key_frame_distance = s->key_frame_distance;
+        kp.key_frame_degree = s->key_frame_degree;
+        kp.resolution = s->resolution;
+        kp.key_frame_range = s->key_frame_range;
+        kp.scan_period = s->scan_period;
+        s->keyframer = lio_keyframer_create(0, &kp);
+        require(s->keyframer != nullptr, "process: lio_keyframer_create failed");
+    }
+    require(lio_keyframer_push_host(s->keyframer, pts, stamps, n, header_stamp, pose.m, delta.m, nullptr, nullptr, 0, nullptr) == LIO_OK,
+            "process: key-frame push failed");
+}
+
+py::dict mapping_pose_dict(const Mat4& out_pose, double lat, double lon, double alt, int status, uint64_t header_stamp, uint64_t timestamp);
+py::dict process_rtkm(Slam* s, py::dict& points, py::dict& points_attr, py::dict& rtk_dict, uint64_t timestamp);
+
 py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, py::dict& image_stream_dict, py::dict& image_param,
                  py::dict& rtk_dict, py::array_t<double>& imu_list, uint64_t timestamp) {
     (void)image_stream_dict;
-    require(g && (g->engine || (g->loc && g->loc->scan)), "init_slam / setup_slam first");
+    require(g && (g->engine || g->rtkm_ready || (g->loc && g->loc->scan)), "init_slam / setup_slam first");
     Slam* s = g.get();
     if (s->loc) return process_localization(s, points, points_attr, image_dict, image_param, rtk_dict, imu_list, timestamp);
-    // pydict_to_rtk: only the fields SLAM::run copies into the pose in mapping mode (slam.cpp:344-348)
-    double lat = 0, lon = 0, alt = 0;
-    int status = 0;
-    if (rtk_dict.contains("latitude")) lat = py::cast<double>(rtk_dict["latitude"]);
-    if (rtk_dict.contains("longitude")) lon = py::cast<double>(rtk_dict["longitude"]);
-    if (rtk_dict.contains("altitude")) alt = py::cast<double>(rtk_dict["altitude"]);
-    if (rtk_dict.contains("Status")) status = py::cast<int>(rtk_dict["Status"]);
-    // SLAM::run (slam.cpp:283-296): preprocessInsData's validity test, then HDL_FastLIO::feedInsData -> fastlio_ins_enqueue (fastlio.cpp:185-187,
-    // laserMapping.cpp:417-441): the INS velocity, ENU -> ego -> IMU, third component zeroed -- IMU initialisation seeds the state's velocity
-    // from it (IMU_Processing.hpp:201-204), the wheel-speed rows read it
-    if (s->use_gps && rtk_dict.contains("Ve") && rtk_dict.contains("timestamp")) {
-        const uint64_t rtk_stamp = py::cast<uint64_t>(rtk_dict["timestamp"]);
-        const std::string sensor = rtk_dict.contains("Sensor") ? py::cast<std::string>(rtk_dict["Sensor"]) : std::string();
-        bool valid;
-        if (status == 0 && std::fabs(lon) < 1e-4 && std::fabs(lat) < 1e-4) {
-            const double lost = timestamp / 1000000.0 - s->last_ins_timestamp;
-            if (s->last_ins_priority != -1 && lost >= 1.0) s->last_ins_priority = -1;
-            valid = false;
-        } else {
-            const Slam::InsCfg* match = nullptr;
-            for (const auto& c : s->ins_cfg) if (c.status == status) { match = &c; break; }
-            if (!match) for (const auto& c : s->ins_cfg) if (c.status == -1) { match = &c; break; }
-            const int mp = match ? match->priority : -1;
-            int priority = -1;
-            if (mp == s->last_ins_priority) { priority = mp; s->last_ins_timestamp = rtk_stamp / 1000000.0; }
-            else if (mp < s->last_ins_priority) { priority = mp; s->last_ins_priority = mp; s->last_ins_timestamp = rtk_stamp / 1000000.0; }
-            else {
-                const double keep = rtk_stamp / 1000000.0 - s->last_ins_timestamp;
-                if (keep >= match->stable_time) { priority = mp; s->last_ins_priority = mp; s->last_ins_timestamp = rtk_stamp / 1000000.0; }
-                else priority = s->last_ins_priority;
-            }
-            valid = priority >= 0;
-        }
-        if (valid || sensor.find("Wheel") != std::string::npos) {
-            const double hd = rtk_dict.contains("heading") ? py::cast<double>(rtk_dict["heading"]) : 0.0;
-            const double pt = rtk_dict.contains("pitch") ? py::cast<double>(rtk_dict["pitch"]) : 0.0;
-            const double rl = rtk_dict.contains("roll") ? py::cast<double>(rtk_dict["roll"]) : 0.0;
-            const double ve[3] = {py::cast<double>(rtk_dict["Ve"]), rtk_dict.contains("Vn") ? py::cast<double>(rtk_dict["Vn"]) : 0.0,
-                                  rtk_dict.contains("Vu") ? py::cast<double>(rtk_dict["Vu"]) : 0.0};
-            const Mat4 Tve = rigid_inverse(transform_from_rpyt(0, 0, 0, -hd, pt, rl));
-            double ego[3], vi[3];
-            for (int r = 0; r < 3; r++) ego[r] = Tve(r, 0) * ve[0] + Tve(r, 1) * ve[1] + Tve(r, 2) * ve[2];
-            for (int r = 0; r < 3; r++) vi[r] = s->T_imu_ins(r, 0) * ego[0] + s->T_imu_ins(r, 1) * ego[1] + s->T_imu_ins(r, 2) * ego[2];
-            vi[2] = 0.0;  // "body up speed of INS is not accurate"
-            lio_fastlio_ins_enqueue(s->engine, rtk_stamp / 1000000.0, vi);
-        }
-    }
+    if (s->rtkm) return process_rtkm(s, points, points_attr, rtk_dict, timestamp);
+    // pydict_to_rtk; SLAM::run copies latitude / longitude / altitude / status into the pose in mapping mode (slam.cpp:344-348)
+    Fix fix = fix_of(rtk_dict);
+    const double lat = fix.f.latitude, lon = fix.f.longitude, alt = fix.f.altitude;
+    const int status = fix.status;
+    feed_fix(s, rtk_dict, fix, timestamp);
     // numpy_to_imu + HDL_FastLIO::feedImuData
     if (s->use_imu && imu_list.ndim() == 2 && imu_list.shape(1) >= 7) {
         auto ref = imu_list.unchecked<2>();
@@ -1220,27 +1383,19 @@ py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, 
         // odometry pose and delta = first^-1 * second; the IMU pose list of HDL_FastLIO::prediction is not fed (the delta branch)
         if (got && keyframes) {
             std::lock_guard<std::mutex> kl(s->kf_mtx);
-            if (!s->keyframer) {
-                lio_keyframer_params kp;
-                lio_keyframer_default_params(&kp);
-                kp.key_frame_distance = s->key_frame_distance;
-                kp.key_frame_degree = s->key_frame_degree;
-                kp.resolution = s->resolution;
-                kp.key_frame_range = s->key_frame_range;
-                kp.scan_period = s->scan_period;
-                s->keyframer = lio_keyframer_create(0, &kp);
-                require(s->keyframer != nullptr, "process: lio_keyframer_create failed");
-            }
             const Mat4 delta = mul(rigid_inverse(out_pose), odom_end);
-            require(lio_keyframer_push_host(s->keyframer, s->kf_points.data(), s->kf_stamps.data(), n, header_stamp, out_pose.m, delta.m, nullptr, nullptr, 0,
-                                            nullptr) == LIO_OK, "process: key-frame push failed");
+            push_frame_locked(s, s->kf_points.data(), s->kf_stamps.data(), n, header_stamp, out_pose, delta);
         }
         if (got && s->pose_graph) {  // HDL_FastLIO::getPose: get_odom2map() * odom.first (the key frame above carries the odometry itself)
             std::lock_guard<std::mutex> kl(s->kf_mtx);
             out_pose = mul(s->odom2map, out_pose);
         }
     }
-    // SLAM::run, mapping branch (slam.cpp:344-364)
+    return mapping_pose_dict(out_pose, lat, lon, alt, status, header_stamp, timestamp);
+}
+
+// SLAM::run, mapping branch (slam.cpp:344-364)
+py::dict mapping_pose_dict(const Mat4& out_pose, double lat, double lon, double alt, int status, uint64_t header_stamp, uint64_t timestamp) {
     double heading, pitch, roll;
     rpy_from_transform(out_pose, heading, pitch, roll);
     if (std::fabs(roll) >= 90.0 || std::fabs(pitch) >= 90.0) {
@@ -1272,6 +1427,98 @@ py::dict process(py::dict& points, py::dict& points_attr, py::dict& image_dict, 
     return data;
 }
 
+// SLAM::run over RTKM (rtkm.cpp): the fix to the track, the lidars merged into one frame on the device, the pose from the track at the merged
+// header stamp (mLastOdom when the track refuses), delta = mLastOdom^-1 * odom
+py::dict process_rtkm(Slam* s, py::dict& points, py::dict& points_attr, py::dict& rtk_dict, uint64_t timestamp) {
+    Fix fix = fix_of(rtk_dict);
+    feed_fix(s, rtk_dict, fix, timestamp);
+    // pydict_to_cloud into std::map order; mergePoints (slam_utils.cpp:249-273): without the base lidar the frame is empty
+    std::map<std::string, int> order;
+    std::vector<py::array_t<float, py::array::c_style | py::array::forcecast>> clouds, attrs;
+    std::vector<uint64_t> headers;
+    for (auto item : points) {
+        const std::string name = py::cast<std::string>(item.first);
+        py::dict attr = py::cast<py::dict>(points_attr[name.c_str()]);
+        order[name] = (int)clouds.size();
+        clouds.push_back(py::cast<py::array>(item.second));
+        attrs.push_back(py::cast<py::array>(attr["points_attr"]));
+        headers.push_back(py::cast<uint64_t>(attr["timestamp"]));
+        const auto& c = clouds.back();
+        const auto& a = attrs.back();
+        require(c.ndim() == 2 && c.shape(1) >= 4 && a.ndim() == 2 && a.shape(1) >= 1 && a.shape(0) == c.shape(0),
+                "process: points must be N x 4 float32 with an N x 2 attribute array");
+    }
+    std::vector<int> take;  // the base, then the others by name
+    if (order.count(s->lidar)) {
+        take.push_back(order[s->lidar]);
+        for (const auto& kv : order)
+            if (kv.first != s->lidar) take.push_back(kv.second);
+    }
+    require(take.size() <= 16, "process: RTKM merges at most 16 lidars");
+    std::vector<std::vector<float>> xyzi(take.size());
+    std::vector<std::vector<uint32_t>> stamps(take.size());
+    std::vector<const float*> pp(take.size());
+    std::vector<const uint32_t*> sp(take.size());
+    std::vector<uint32_t> np_(take.size());
+    std::vector<uint64_t> hd(take.size());
+    uint64_t total = 0;
+    for (size_t l = 0; l < take.size(); l++) {
+        const auto& c = clouds[(size_t)take[l]];
+        const auto& a = attrs[(size_t)take[l]];
+        const size_t n = (size_t)c.shape(0);
+        const py::ssize_t cs = c.shape(1), as = a.shape(1);
+        xyzi[l].resize(4 * n + 4);
+        stamps[l].resize(n + 1);
+        const float* src = c.data();
+        const float* asrc = a.data();
+        for (size_t i = 0; i < n; i++) {
+            for (int k = 0; k < 4; k++) xyzi[l][4 * i + k] = src[i * cs + k];
+            stamps[l][i] = (uint32_t)asrc[i * as];  // pointcloud_attr[i].stamp = ref_attr(i, 0): float -> uint32_t
+        }
+        pp[l] = xyzi[l].data(); sp[l] = stamps[l].data(); np_[l] = (uint32_t)n; hd[l] = headers[(size_t)take[l]];
+        total += n;
+    }
+    const uint64_t header_stamp = take.empty() ? 0 : hd[0];
+    Mat4 odom = Mat4::identity();
+    {
+        py::gil_scoped_release release;
+        std::unique_lock<std::mutex> lk(s->mtx);
+        uint64_t n_out = 0;
+        if (!take.empty()) {
+            if (!s->merger || total > s->merger_cap) {
+                if (s->merger) lio_scan_merge_destroy(s->merger);
+                s->merger_cap = std::max<uint64_t>(2 * total, 1ull << 20);
+                s->merger = lio_scan_merge_create(0, 16, s->merger_cap);
+                require(s->merger != nullptr, "process: lio_scan_merge_create failed");
+            }
+            require(lio_scan_merge_set_transform(s->merger, s->T_static.m) == LIO_OK, "process: lio_scan_merge_set_transform failed");
+            require(lio_scan_merge_run_host(s->merger, (uint32_t)take.size(), pp.data(), sp.data(), np_.data(), hd.data(),
+                                            uint64_t(s->scan_period * 1000000.0), nullptr, nullptr, nullptr, &n_out) == LIO_OK, "process: the merge failed");
+        }
+        s->merged_pts.resize(4 * (size_t)n_out + 4);
+        s->merged_stamps.resize((size_t)n_out + 1);
+        if (n_out)
+            require(lio_scan_merge_download(s->merger, s->merged_pts.data(), s->merged_stamps.data(), n_out) == (int64_t)n_out, "process: the merged frame's download failed");
+        s->merged_pts.resize(4 * (size_t)n_out);
+        s->merged_stamps.resize((size_t)n_out);
+        // RTKM::getPose (rtkm.cpp:111-123)
+        odom = s->rtkm_last_odom;
+        if (s->track) (void)lio_rtk_track_interpolate(s->track, header_stamp, odom.m);
+        const Mat4 delta = mul(rigid_inverse(s->rtkm_last_odom), odom);
+        s->last_odom_start = s->rtkm_last_odom;  // (_last_odometry: mLastOdom before and after this frame)
+        s->last_odom_end = odom;
+        s->rtkm_last_odom = odom;
+        const std::vector<float> pts = s->merged_pts;
+        const std::vector<uint32_t> st = s->merged_stamps;
+        lk.unlock();
+        if (s->keyframe_output && n_out > 0) {
+            std::lock_guard<std::mutex> kl(s->kf_mtx);
+            push_frame_locked(s, pts.data(), st.data(), (uint32_t)n_out, header_stamp, odom, delta);
+        }
+    }
+    return mapping_pose_dict(odom, fix.f.latitude, fix.f.longitude, fix.f.altitude, fix.status, header_stamp, timestamp);
+}
+
 // ---- off the hot path: type-correct minimal implementations -------------------------------------------
 // SLAM::setCameraParameter: kept for the colour map (the painter takes them with the static transform at its next frame)
 void set_camera_param(py::list& cameras) {
@@ -1284,6 +1531,10 @@ void set_camera_param(py::list& cameras) {
 // pydict_to_ins_config (py_utils.cpp:295-317): ins_normal / ins_float / ins_fix entries with use, status, stable_time, precision
 void set_ins_config(py::dict& dict) {
     if (!g) return;
+    if (dict.contains("ins_type")) {  // pydict_to_ins_dimension (py_utils.cpp:317-327)
+        const std::string dim = py::cast<std::string>(dict["ins_type"]);
+        g->ins_dim = dim == "2D" ? 2 : (dim == "3D" ? 3 : (dim == "6D" ? 6 : 0));
+    }
     g->ins_cfg.clear();
     int priority = 0;
     for (const char* name : {"ins_normal", "ins_float", "ins_fix"}) {
@@ -1381,6 +1632,71 @@ void release_first_node(Slam* s, const char* who) {
     s->fix_first_node = false;
     if (lio_graph_num_nodes(s->graph) > 0) require(lio_graph_set_fixed(s->graph, 0, 0) == LIO_OK, who);
 }
+// what flush_gps_queue (hdl_graph_slam_nodelet.cpp:398-455) does once a fix is matched to key frame `id`, for add_graph_gnss and for the flush of
+// the GNSS queue alike: the distance gate against the last accepted fix (10 / 20 / 50 m by precision), the information matrices, Huber 1.0, the
+// release of node 0.  `gated`: lio_gnss_queue_flush has applied the gate and marked the key frame already.  The ids of the edges added: [] when
+// the gate refuses the fix, the key frame has one already or is gone, or there is no graph.  kf_mtx is held
+std::vector<int> gnss_prior_locked(Slam* s, int id, const double xyz[3], const double quat[4], double precision, int dimension, bool gated, const char* who) {
+    std::vector<int> added;
+    if (!s->graph || id < 0 || (size_t)id >= s->graph_has_gnss.size() || s->graph_gone[(size_t)id]) return added;
+    if (!gated) {
+        if (s->graph_has_gnss[(size_t)id]) return added;
+        const double threshold = precision < 100.0 ? 10.0 : (precision < 1000.0 ? 20.0 : 50.0);
+        const double* last = s->gnss_last;
+        const double d[3] = {last[0] - xyz[0], last[1] - xyz[1], last[2] - xyz[2]};
+        if (std::sqrt(last[0] * last[0] + last[1] * last[1] + last[2] * last[2]) > 0 && std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) < threshold) return added;
+    }
+    const std::string failed = std::string(who) + ": lio_graph_add_prior failed";
+    double info[9] = {1.0 / precision, 0, 0, 0, 1.0 / precision, 0, 0, 0, 1.0 / precision};
+    if (dimension == 2) {
+        const double n2 = xyz[0] * xyz[0] + xyz[1] * xyz[1] + xyz[2] * xyz[2];
+        if (gated && !(n2 > 0)) {  // (the reference divides by zero here: the fix is left out and the key frame stays open for the next one)
+            s->graph_has_gnss[(size_t)id] = 0;
+            return added;
+        }
+        require(n2 > 0, "add_graph_gnss: a 2-D fix at the origin has no information for z");
+        info[8] = 1.0 / n2;  // 1 / (xyz.norm() * xyz.norm())
+    }
+    const double m[4] = {xyz[0], xyz[1], xyz[2], 0.0};
+    int e = lio_graph_add_prior(s->graph, id, LIO_GRAPH_PRIOR_XYZ, m, nullptr, info, LIO_GRAPH_KERNEL_HUBER, 1.0);
+    require(e >= 0, failed.c_str());
+    added.push_back(e);
+    if (dimension == 6) {
+        const double r = 1.0 / (precision * 10.0);  // gps_rot_stddev
+        const double rinfo[9] = {r, 0, 0, 0, r, 0, 0, 0, r};
+        e = lio_graph_add_prior(s->graph, id, LIO_GRAPH_PRIOR_QUAT, quat, nullptr, rinfo, LIO_GRAPH_KERNEL_HUBER, 1.0);
+        require(e >= 0, failed.c_str());
+        added.push_back(e);
+    }
+    s->graph_has_gnss[(size_t)id] = 1;
+    for (int k = 0; k < 3; k++) s->gnss_last[k] = xyz[k];
+    release_first_node(s, (std::string(who) + ": lio_graph_set_fixed failed").c_str());
+    return added;
+}
+// flush_gps_queue (hdl_graph_slam_nodelet.cpp:358-460) against the key frames the graph held BEFORE this pass (`keyframes`, not `new_keyframes`:
+// optimization_timer_callback appends the new ones after the flush, :604-624): the live key frames below n_before with their stamps and fix
+// flags go to lio_gnss_queue_flush, the matches become priors.  true: a prior was added.  kf_mtx is held
+bool gnss_flush_locked(Slam* s, size_t n_before) {
+    if (!s->gnss || !s->gnss_queue || !s->graph) return false;
+    std::vector<int> ids;
+    std::vector<uint64_t> stamps;
+    std::vector<uint8_t> has;
+    for (size_t k = 0; k < n_before && k < s->graph_gone.size(); k++)
+        if (!s->graph_gone[k]) { ids.push_back((int)k); stamps.push_back(s->bank_stamp[k]); has.push_back(s->graph_has_gnss[k]); }
+    if (ids.empty()) return false;
+    std::vector<lio_gnss_match> matches(ids.size());
+    const int n = lio_gnss_queue_flush(s->gnss_queue, stamps.data(), has.data(), (uint32_t)ids.size(), s->gnss_last, matches.data(), (uint32_t)matches.size());
+    if (n == LIO_E_STATE) return false;  // fixes without an origin cannot be (the first valid fix sets it): nothing to match against
+    require(n >= 0, "update_odom: lio_gnss_queue_flush failed");
+    bool updated = false;
+    for (int k = 0; k < n; k++) {
+        const lio_gnss_match& m = matches[(size_t)k];
+        const int id = ids[(size_t)m.keyframe];
+        s->graph_has_gnss[(size_t)id] = 1;
+        updated = !gnss_prior_locked(s, id, m.xyz, m.quat, m.precision, m.dimension, true, "update_odom").empty() || updated;
+    }
+    return updated;
+}
 // flush_floor_queue (hdl_graph_slam_nodelet.cpp:536-594) for one key frame that has just entered the graph.  The reference's floor detector is a
 // thread of its own that fills floor_coeffs_queue; here the key frame's cloud as popped goes through lio_ground_detect_host (preset 1: the floor
 // detector's parameters, the seed of set_ground_extraction) at this point.  The plane vertex is always fixed in the reference (:563), so the
@@ -1424,11 +1740,12 @@ py::dict update_odom() {
     };
     std::vector<Popped> popped;
     std::vector<std::pair<int, Mat4>> odoms;
-    if (g && (g->keyframer || !g->injected.empty())) {
+    if (g && (g->keyframer || !g->injected.empty() || g->gnss)) {
         py::gil_scoped_release rel;
         std::lock_guard<std::mutex> kl(g->kf_mtx);
         bool banked = false;
         const bool graph_on = g->pose_graph && g->loop_detection;
+        const size_t n_before = g->graph_odom.size();  // `keyframes` as the GNSS flush sees it
         while ((g->keyframer && lio_keyframer_pending(g->keyframer) > 0) || !g->injected.empty()) {
             popped.emplace_back();
             Popped& f = popped.back();
@@ -1490,6 +1807,9 @@ py::dict update_odom() {
                 if (id >= 0) { g->bank_stamp.push_back(f.stamp); g->bank_odom.push_back(f.pose); }
             }
         }
+        // flush_gps_queue after flush_keyframe_queue and the floor (optimization_timer_callback, hdl_graph_slam_nodelet.cpp:604-606)
+        const bool gnss_updated = graph_on && gnss_flush_locked(g.get(), n_before);
+        if (gnss_updated && !banked && graph_optimize_locked(g.get(), "update_odom")) g->graph_updated = true;
         if (banked) {  // LoopDetector::detect over the frames just queued (optimization_timer_callback, hdl_graph_slam_nodelet.cpp:588-623)
             lio_loop_edge found[8];  // (more than 8 loops in one call come back as -(count), below every error code)
             const int n_loops = lio_loop_detect(g->loop, found, 8);
@@ -1636,6 +1956,60 @@ void set_pose_graph(bool enable) {
     g->pose_graph = enable;
     if (enable) { g->loop_detection = true; g->keyframe_output = true; }
 }
+// not in the reference's module (whose GNSS side always runs): the GNSS side of FastLIO mapping -- the map origin from the first valid fix, the
+// fixes queued for the graph and flushed into priors by update_odom() -- off by default; LSD_AMD_GNSS=1 at init_slam switches it on for an
+// unchanged slam.py.  RTKM needs no switch
+void set_gnss(bool enable) {
+    require((bool)g, "init_slam first");
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    g->gnss = enable;
+}
+// test visibility: what process() does with a fix (the validity filter, the origin, the method's feedInsData, FastLIO's velocity hand-over when
+// there is an engine) and nothing else; the frame's timestamp is the fix's own
+void _push_gnss(py::dict rtk_dict) {
+    require((bool)g && !g->loc, "init_slam in mapping mode first");
+    Fix fix = fix_of(rtk_dict);
+    feed_fix(g.get(), rtk_dict, fix, fix.f.stamp_us);
+}
+// test visibility: the points (N x 4 f32, INS frame) and stamps (N u32) of the last RTKM frame
+py::tuple _last_merged() {
+    require((bool)g && g->rtkm, "init_slam with method RTKM first");
+    std::vector<float> pts;
+    std::vector<uint32_t> st;
+    {
+        std::lock_guard<std::mutex> lk(g->mtx);
+        pts = g->merged_pts;
+        st = g->merged_stamps;
+    }
+    py::array_t<float> a({(py::ssize_t)st.size(), (py::ssize_t)4});
+    py::array_t<uint32_t> b((py::ssize_t)st.size());
+    if (!st.empty()) {
+        std::memcpy(a.mutable_data(), pts.data(), pts.size() * sizeof(float));
+        std::memcpy(b.mutable_data(), st.data(), st.size() * sizeof(uint32_t));
+    }
+    return py::make_tuple(a, b);
+}
+// test visibility: the state of the GNSS side -- fixes queued for the graph, fixes on the RTK track
+py::dict _gnss_state() {
+    py::dict d;
+    if (!g) return d;
+    int queued = 0, tracked = 0;
+    {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        queued = g->gnss_queue ? lio_gnss_queue_size(g->gnss_queue) : 0;
+    }
+    {
+        std::lock_guard<std::mutex> lk(g->mtx);
+        tracked = g->track ? lio_rtk_track_size(g->track) : 0;
+    }
+    d["enabled"] = g->gnss;
+    d["origin_set"] = g->origin_set;
+    d["queued"] = queued;
+    d["tracked"] = tracked;
+    return d;
+}
 // test visibility: a key frame (points N x 4 f32, odometry pose 4 x 4 f64, stamp, accumulated distance) for the next update_odom(), as if the
 // front end had elected it
 void _push_keyframe(py::array_t<float, py::array::c_style | py::array::forcecast> points, py::array_t<double, py::array::c_style | py::array::forcecast> pose,
@@ -1722,10 +2096,11 @@ py::array_t<double> get_map_origin() {
     return a;
 }
 void set_map_origin(double lat, double lon, double alt, double heading, double pitch, double roll) {
-    if (g && !g->origin_set) {  // SLAM::setOrigin: first one wins
-        const double v[6] = {lat, lon, alt, heading, pitch, roll};
-        std::memcpy(g->origin, v, sizeof(v));
-        g->origin_set = true;
+    if (g && !g->origin_set) {  // SLAM::setOrigin: first one wins, against the fixes of process() as well
+        lio_rtk_fix f = lio_rtk_fix();
+        f.latitude = lat; f.longitude = lon; f.altitude = alt; f.heading = heading; f.pitch = pitch; f.roll = roll;
+        f.dimension = 2; f.precision = 100.0;
+        slam_set_origin(g.get(), f);
     }
 }
 // ---- merge_map (slam_wrapper.cpp:174-178 -> SLAM::mergeMap -> MapLoader::mergeMapSLAM, map_loader.cpp:82-169) ----------------------------------
@@ -1844,18 +2219,6 @@ py::dict _read_g2o(std::string path) {
 }
 
 namespace {
-struct MapInfo { double origin[6] = {0, 0, 0, 0, 0, 0}; int coordinate = 0; bool origin_set = false; };
-bool read_map_info(const std::string& map_path, MapInfo& mi) {  // MapLoader::loadMapOrigin (map_loader.cpp:180-221)
-    std::ifstream fs(map_path + "/graph/map_info.txt");
-    if (!fs) return false;
-    for (int i = 0; i < 6; i++) fs >> mi.origin[i];
-    double c = 0;
-    fs >> c;
-    mi.coordinate = (int)c;
-    mi.origin_set = false;
-    for (int i = 0; i < 6; i++) mi.origin_set = mi.origin_set || !(std::fabs(mi.origin[i]) < 1e-4);
-    return true;
-}
 void to_map_frame(KeyFrameDisk& kf) {  // KeyFrame::transformPoints at the frame's pose (load_keyframes' loop)
     kf.xyzi = kf.local;
     const size_t n = kf.xyzi.size() / 4;
@@ -2387,8 +2750,9 @@ py::dict run_robust_graph_optimization(std::string mode) {
 // not in the reference's module: one GNSS fix for key frame `id`, what flush_gps_queue (hdl_graph_slam_nodelet.cpp:398-455) does once it has
 // matched a fix to a key frame -- xyz (metres, already in the map's projection; z ignored for dimension 2), the fix's precision and dimension
 // (2, 3 or 6), for dimension 6 the orientation as a quaternion (x, y, z, w).  The distance gate against the last accepted fix (10 / 20 / 50 m by
-// precision), the information matrices, Huber 1.0, the release of node 0.  The UTM projection, the RTK queue and the interpolation between two
-// fixes in time stay out of scope.  The ids of the edges added: [] when the gate refuses the fix, the key frame has one already, or there is no graph
+// precision), the information matrices, Huber 1.0, the release of node 0: gnss_prior_locked, which the flush of the GNSS queue calls as well
+// (set_gnss: the UTM projection, the queue and the interpolation between two fixes in time, lio_gnss_queue_*).  The ids of the edges added: []
+// when the gate refuses the fix, the key frame has one already, or there is no graph
 std::vector<int> add_graph_gnss(int id, py::array_t<double, py::array::c_style | py::array::forcecast> xyz_in, double precision, int dimension, py::object orientation) {
     std::vector<int> added;
     if (!g) return added;
@@ -2405,32 +2769,7 @@ std::vector<int> add_graph_gnss(int id, py::array_t<double, py::array::c_style |
     }
     py::gil_scoped_release rel;
     std::lock_guard<std::mutex> kl(g->kf_mtx);
-    if (!g->graph || id < 0 || (size_t)id >= g->graph_has_gnss.size() || g->graph_has_gnss[(size_t)id] || g->graph_gone[(size_t)id]) return added;
-    const double threshold = precision < 100.0 ? 10.0 : (precision < 1000.0 ? 20.0 : 50.0);
-    const double* last = g->gnss_last;
-    const double d[3] = {last[0] - xyz[0], last[1] - xyz[1], last[2] - xyz[2]};
-    if (std::sqrt(last[0] * last[0] + last[1] * last[1] + last[2] * last[2]) > 0 && std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) < threshold) return added;
-    double info[9] = {1.0 / precision, 0, 0, 0, 1.0 / precision, 0, 0, 0, 1.0 / precision};
-    if (dimension == 2) {
-        const double n2 = xyz[0] * xyz[0] + xyz[1] * xyz[1] + xyz[2] * xyz[2];
-        require(n2 > 0, "add_graph_gnss: a 2-D fix at the origin has no information for z");
-        info[8] = 1.0 / n2;  // 1 / (xyz.norm() * xyz.norm())
-    }
-    const double m[4] = {xyz[0], xyz[1], xyz[2], 0.0};
-    int e = lio_graph_add_prior(g->graph, id, LIO_GRAPH_PRIOR_XYZ, m, nullptr, info, LIO_GRAPH_KERNEL_HUBER, 1.0);
-    require(e >= 0, "add_graph_gnss: lio_graph_add_prior failed");
-    added.push_back(e);
-    if (dimension == 6) {
-        const double r = 1.0 / (precision * 10.0);  // gps_rot_stddev
-        const double rinfo[9] = {r, 0, 0, 0, r, 0, 0, 0, r};
-        e = lio_graph_add_prior(g->graph, id, LIO_GRAPH_PRIOR_QUAT, quat, nullptr, rinfo, LIO_GRAPH_KERNEL_HUBER, 1.0);
-        require(e >= 0, "add_graph_gnss: lio_graph_add_prior failed");
-        added.push_back(e);
-    }
-    g->graph_has_gnss[(size_t)id] = 1;
-    for (int k = 0; k < 3; k++) g->gnss_last[k] = xyz[k];
-    release_first_node(g.get(), "add_graph_gnss: lio_graph_set_fixed failed");
-    return added;
+    return gnss_prior_locked(g.get(), id, xyz, quat, precision, dimension, false, "add_graph_gnss");
 }
 // test visibility: the graph's live priors as lio_graph_priors returns them
 py::list _graph_priors() {
@@ -2998,73 +3337,12 @@ struct Colouration {
 };
 Colouration g_col;
 
-// Eigen's Quaterniond(Matrix3d) (w, x, y, z), q * v, q1 * q2 and toRotationMatrix
-void quat_of(const Mat4& T, double q[4]) {
-    const double t = T(0, 0) + T(1, 1) + T(2, 2);
-    if (t > 0) {
-        const double r = std::sqrt(t + 1.0), k = 0.5 / r;
-        q[0] = 0.5 * r; q[1] = (T(2, 1) - T(1, 2)) * k; q[2] = (T(0, 2) - T(2, 0)) * k; q[3] = (T(1, 0) - T(0, 1)) * k;
-        return;
-    }
-    int i = 0;
-    if (T(1, 1) > T(0, 0)) i = 1;
-    if (T(2, 2) > T(i, i)) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    const double r = std::sqrt(T(i, i) - T(j, j) - T(k, k) + 1.0), kk = 0.5 / r;
-    q[1 + i] = 0.5 * r;
-    q[0] = (T(k, j) - T(j, k)) * kk; q[1 + j] = (T(j, i) + T(i, j)) * kk; q[1 + k] = (T(k, i) + T(i, k)) * kk;
-}
-void quat_rotate(const double q[4], const double v[3], double o[3]) {
-    const double uv[3] = {2 * (q[2] * v[2] - q[3] * v[1]), 2 * (q[3] * v[0] - q[1] * v[2]), 2 * (q[1] * v[1] - q[2] * v[0])};
-    o[0] = v[0] + q[0] * uv[0] + (q[2] * uv[2] - q[3] * uv[1]);
-    o[1] = v[1] + q[0] * uv[1] + (q[3] * uv[0] - q[1] * uv[2]);
-    o[2] = v[2] + q[0] * uv[2] + (q[1] * uv[1] - q[2] * uv[0]);
-}
-void quat_mul(const double a[4], const double b[4], double o[4]) {
-    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-    o[2] = a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3];
-    o[3] = a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1];
-}
-// interpolateTransform (slam_utils.cpp:126-161): the pose a fraction `ratio` of the way from pre to next, along the translation and the
-// angle-axis of pre^-1 next
+// Eigen's Quaterniond(Matrix3d) (w, x, y, z) and interpolateTransform (slam_utils.cpp:126-161): the library's (csrc/geodesy.cpp), which the RTK
+// track and the graph's GNSS queue use as well
+void quat_of(const Mat4& T, double q[4]) { lio_quat_of_transform(T.m, q); }
 Mat4 interpolate_transform(const Mat4& pre, const Mat4& next, double ratio) {
-    double q[4], qi[4], qn[4], dq[4];
-    quat_of(pre, q);
-    qi[0] = q[0]; qi[1] = -q[1]; qi[2] = -q[2]; qi[3] = -q[3];
-    quat_of(next, qn);
-    const double t[3] = {pre(0, 3), pre(1, 3), pre(2, 3)}, tn[3] = {next(0, 3), next(1, 3), next(2, 3)};
-    double a[3], b[3];
-    quat_rotate(qi, t, a);
-    quat_rotate(qi, tn, b);
-    const double dt[3] = {-a[0] + b[0], -a[1] + b[1], -a[2] + b[2]};
-    quat_mul(qi, qn, dq);
-    // Eigen::AngleAxisd(q): angle = 2 atan2(|vec|, |w|), the axis vec / |vec| with the sign of w; no rotation: angle 0 about x
-    double n = std::sqrt(dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]), angle = 0, axis[3] = {1, 0, 0};
-    if (n != 0.0) {
-        angle = 2.0 * std::atan2(n, std::fabs(dq[0]));
-        if (dq[0] < 0) n = -n;
-        for (int i = 0; i < 3; i++) axis[i] = dq[1 + i] / n;
-    }
-    const double lt[3] = {ratio * dt[0], ratio * dt[1], ratio * dt[2]};
-    const double lr[3] = {ratio * (angle * axis[0]), ratio * (angle * axis[1]), ratio * (angle * axis[2])};
-    const double norm = std::sqrt(lr[0] * lr[0] + lr[1] * lr[1] + lr[2] * lr[2]);
-    double tq[4] = {1, 0, 0, 0};
-    if (!(norm < 1e-8)) {
-        const double sh = std::sin(0.5 * norm), ch = std::cos(0.5 * norm);
-        tq[0] = ch; tq[1] = sh * (lr[0] / norm); tq[2] = sh * (lr[1] / norm); tq[3] = sh * (lr[2] / norm);
-    }
-    double rt[3], nq[4];
-    quat_rotate(q, lt, rt);
-    quat_mul(q, tq, nq);
-    Mat4 R = Mat4::identity();
-    const double w = nq[0], x = nq[1], y = nq[2], z = nq[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R(0, 0) = 1 - (tyy + tzz); R(0, 1) = txy - twz; R(0, 2) = txz + twy;
-    R(1, 0) = txy + twz; R(1, 1) = 1 - (txx + tzz); R(1, 2) = tyz - twx;
-    R(2, 0) = txz - twy; R(2, 1) = tyz + twx; R(2, 2) = 1 - (txx + tyy);
-    for (int i = 0; i < 3; i++) R(i, 3) = t[i] + rt[i];
+    Mat4 R;
+    lio_interpolate_transform(pre.m, next.m, ratio, R.m);
     return R;
 }
 
@@ -3635,6 +3913,10 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("_last_estimate_pose", &_last_estimate_pose);
     m.def("set_pose_graph", &set_pose_graph, "the pose graph over the key frames and the loops", py::arg("enable"));
     m.def("_push_keyframe", &_push_keyframe, "test hook: a key frame for the next update_odom()", py::arg("points"), py::arg("pose"), py::arg("stamp"), py::arg("accum_distance"));
+    m.def("set_gnss", &set_gnss, "the GNSS side of FastLIO mapping: origin from the first valid fix, GNSS priors in the pose graph", py::arg("enable"));
+    m.def("_push_gnss", &_push_gnss, "test hook: what process() does with a fix", py::arg("rtk_dict"));
+    m.def("_last_merged", &_last_merged, "test hook: points and stamps of the last RTKM frame");
+    m.def("_gnss_state", &_gnss_state, "test hook: the state of the GNSS side");
     m.def("set_loop_config", &set_loop_config, "LoopDetector thresholds", py::arg("dict"));
     m.def("get_loop_edges", &get_loop_edges, "loop edges found so far");
     m.def("_last_odometry", &_last_odometry);

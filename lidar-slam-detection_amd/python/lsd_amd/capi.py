@@ -72,7 +72,17 @@ SYMBOLS = [
     "lio_graph_remove_node", "lio_graph_node_live", "lio_graph_edge_records", "lio_loop_retire",
     "lio_render_create", "lio_render_destroy", "lio_render_clear", "lio_render_set_cameras", "lio_render_set_active", "lio_render_frame", "lio_render_size",
     "lio_render_download", "lio_render_download_voxels", "lio_render_download_points", "lio_render_download_last_image", "lio_render_last_times",
+    "lio_utm_create", "lio_utm_destroy", "lio_utm_zone", "lio_utm_forward", "lio_utm_inverse", "lio_utm_longitude0", "lio_grid_convergence",
+    "lio_transform_from_rpyt", "lio_quat_of_transform", "lio_interpolate_transform", "lio_rtk_transform_utm", "lio_rtk_transform_origin",
+    "lio_rtk_track_create", "lio_rtk_track_destroy", "lio_rtk_track_set_origin", "lio_rtk_track_origin", "lio_rtk_track_feed", "lio_rtk_track_size",
+    "lio_rtk_track_interpolate",
+    "lio_gnss_queue_create", "lio_gnss_queue_destroy", "lio_gnss_queue_set_origin", "lio_gnss_queue_push", "lio_gnss_queue_size", "lio_gnss_queue_stamps",
+    "lio_gnss_queue_flush",
+    "lio_scan_merge_create", "lio_scan_merge_destroy", "lio_scan_merge_set_transform", "lio_scan_merge_run_host", "lio_scan_merge_download",
+    "lio_scan_merge_device", "lio_scan_merge_last_times",
 ]
+ABI_VERSION = 22  # the revision of include/lio_hip.h this binding was written against
+RTK_INTERPOLATED, RTK_EXACT, RTK_NO_ORIGIN, RTK_TOO_FEW, RTK_EARLY, RTK_LATE = 0, 1, 2, 3, 4, 5  # lio_rtk_track_interpolate
 
 
 class NormalEq(C.Structure):
@@ -229,6 +239,16 @@ class EstimateReport(C.Structure):  # lio_estimate_report
 
 class NdtTimes(C.Structure):  # lio_ndt_times
     _fields_ = [("cost_us", C.c_double), ("launches", C.c_uint64), ("update_launches", C.c_uint64), ("pairs", C.c_uint64), ("source_points", C.c_uint64)]
+
+
+class RtkFix(C.Structure):  # lio_rtk_fix
+    _fields_ = [("stamp_us", C.c_uint64), ("latitude", C.c_double), ("longitude", C.c_double), ("altitude", C.c_double), ("heading", C.c_double),
+                ("pitch", C.c_double), ("roll", C.c_double), ("precision", C.c_double), ("dimension", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GnssMatch(C.Structure):  # lio_gnss_match
+    _fields_ = [("keyframe", C.c_int32), ("dimension", C.c_int32), ("first_stamp_us", C.c_uint64), ("second_stamp_us", C.c_uint64),
+                ("xyz", C.c_double * 3), ("quat", C.c_double * 4), ("precision", C.c_double)]
 
 
 class KernelTimes(C.Structure):
@@ -577,6 +597,41 @@ def lib():
     sig("lio_render_download_points", C.c_int64, vp, f32p, u32p, f32p, f32p, f32p, u64)
     sig("lio_render_download_last_image", C.c_int64, vp, f32p, i32p, u8p, u64, C.POINTER(cint), C.POINTER(cint))
     sig("lio_render_last_times", cint, vp, f64p, f64p, f64p)
+    fixp, u64p = C.POINTER(RtkFix), C.POINTER(u64)
+    sig("lio_utm_create", vp, cint)
+    sig("lio_utm_destroy", None, vp)
+    sig("lio_utm_zone", cint, vp)
+    sig("lio_utm_forward", cint, vp, dbl, dbl, f64p, f64p)
+    sig("lio_utm_inverse", cint, vp, dbl, dbl, f64p, f64p)
+    sig("lio_utm_longitude0", dbl, vp)
+    sig("lio_grid_convergence", dbl, dbl, dbl, dbl)
+    sig("lio_transform_from_rpyt", None, dbl, dbl, dbl, dbl, dbl, dbl, f64p)
+    sig("lio_quat_of_transform", None, f64p, f64p)
+    sig("lio_interpolate_transform", None, f64p, f64p, dbl, f64p)
+    sig("lio_rtk_transform_utm", cint, vp, fixp, f64p, f64p)
+    sig("lio_rtk_transform_origin", cint, vp, fixp, fixp, f64p)
+    sig("lio_rtk_track_create", vp)
+    sig("lio_rtk_track_destroy", None, vp)
+    sig("lio_rtk_track_set_origin", cint, vp, fixp, f64p)
+    sig("lio_rtk_track_origin", cint, vp, fixp)
+    sig("lio_rtk_track_feed", cint, vp, cint, fixp)
+    sig("lio_rtk_track_size", cint, vp)
+    sig("lio_rtk_track_interpolate", cint, vp, u64, f64p)
+    sig("lio_gnss_queue_create", vp)
+    sig("lio_gnss_queue_destroy", None, vp)
+    sig("lio_gnss_queue_set_origin", cint, vp, fixp, cint, dbl, f64p)
+    sig("lio_gnss_queue_push", cint, vp, fixp)
+    sig("lio_gnss_queue_size", cint, vp)
+    sig("lio_gnss_queue_stamps", cint, vp, u64p, u32)
+    sig("lio_gnss_queue_flush", cint, vp, u64p, u8p, u32, f64p, C.POINTER(GnssMatch), u32)
+    sig("lio_scan_merge_create", vp, cint, u32, u64)
+    sig("lio_scan_merge_destroy", None, vp)
+    sig("lio_scan_merge_set_transform", cint, vp, f64p)
+    sig("lio_scan_merge_run_host", cint, vp, u32, C.POINTER(f32p), C.POINTER(C.POINTER(u32)), C.POINTER(u32), u64p, u64, C.POINTER(u32), C.POINTER(u32),
+        C.POINTER(u32), u64p)
+    sig("lio_scan_merge_download", C.c_int64, vp, f32p, C.POINTER(u32), u64)
+    sig("lio_scan_merge_device", vp, vp, C.POINTER(C.POINTER(u32)), u64p)
+    sig("lio_scan_merge_last_times", cint, vp, f64p, f64p)
     sig("lio_state_boxplus", None, f64p, f64p, f64p)
     sig("lio_state_boxminus", None, f64p, f64p, f64p)
     _lib = L

@@ -2489,3 +2489,213 @@ class ColourMap:
         v = [C.c_double(0) for _ in range(3)]
         check(lib().lio_render_last_times(self.h, *[C.byref(x) for x in v]), "render times")
         return dict(insert_us=v[0].value, image_us=v[1].value, finish_us=v[2].value)
+
+
+def rtk_fix(stamp_us=0, latitude=0.0, longitude=0.0, altitude=0.0, heading=0.0, pitch=0.0, roll=0.0, precision=100.0, dimension=2):
+    """a lio_rtk_fix (degrees, metres; the defaults of the reference's RTKType)"""
+    return capi.RtkFix(int(stamp_us), float(latitude), float(longitude), float(altitude), float(heading), float(pitch), float(roll), float(precision),
+                       int(dimension), 0)
+
+
+def _fix(f):
+    return f if isinstance(f, capi.RtkFix) else rtk_fix(**f)
+
+
+def grid_convergence(longitude0, lat, lon):
+    return lib().lio_grid_convergence(float(longitude0), float(lat), float(lon))
+
+
+def transform_from_rpyt(x, y, z, yaw, pitch, roll):
+    T = np.zeros((4, 4))
+    lib().lio_transform_from_rpyt(float(x), float(y), float(z), float(yaw), float(pitch), float(roll), ptr(T, C.c_double))
+    return T
+
+
+def interpolate_transform(pre, nxt, ratio):
+    a, b, T = f64(pre).reshape(4, 4), f64(nxt).reshape(4, 4), np.zeros((4, 4))
+    lib().lio_interpolate_transform(ptr(a, C.c_double), ptr(b, C.c_double), float(ratio), ptr(T, C.c_double))
+    return T
+
+
+class Utm:
+    """lio_utm: the reference's UTMProjector, host only.  The zone is fixed by the first call (zone is -1 until then)."""
+
+    def __init__(self, zone_width=6):
+        self.h = lib().lio_utm_create(int(zone_width))
+        if not self.h:
+            raise capi.LioError("lio_utm_create failed")
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_utm_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @property
+    def zone(self):
+        return lib().lio_utm_zone(self.h)
+
+    def forward(self, lat, lon):
+        x, y = C.c_double(0), C.c_double(0)
+        check(lib().lio_utm_forward(self.h, float(lat), float(lon), C.byref(x), C.byref(y)), "utm forward")
+        return x.value, y.value
+
+    def inverse(self, x, y):
+        lat, lon = C.c_double(0), C.c_double(0)
+        check(lib().lio_utm_inverse(self.h, float(x), float(y), C.byref(lat), C.byref(lon)), "utm inverse")
+        return lat.value, lon.value
+
+    def longitude0(self):
+        return lib().lio_utm_longitude0(self.h)
+
+    def rtk_transform_utm(self, fix, zero_utm):
+        """computeRTKTransform(projector, data, zero_utm)"""
+        z, T = f64(zero_utm).reshape(3), np.zeros((4, 4))
+        check(lib().lio_rtk_transform_utm(self.h, C.byref(_fix(fix)), ptr(z, C.c_double), ptr(T, C.c_double)), "rtk transform")
+        return T
+
+    def rtk_transform_origin(self, origin, fix):
+        """RTKM::computeRTKTransform(origin, data)"""
+        T = np.zeros((4, 4))
+        check(lib().lio_rtk_transform_origin(self.h, C.byref(_fix(origin)), C.byref(_fix(fix)), ptr(T, C.c_double)), "rtk transform")
+        return T
+
+
+class RtkTrack:
+    """lio_rtk_track: RTKM's stamp -> fix map with its interpolation, host only."""
+
+    def __init__(self):
+        self.h = lib().lio_rtk_track_create()
+        if not self.h:
+            raise capi.LioError("lio_rtk_track_create failed")
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_rtk_track_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def set_origin(self, fix):
+        """(taken, T): the first origin wins; T is the origin's own pose"""
+        T = np.zeros((4, 4))
+        rc = check(lib().lio_rtk_track_set_origin(self.h, C.byref(_fix(fix)), ptr(T, C.c_double)), "track set_origin")
+        return bool(rc), (T if rc else None)
+
+    def feed(self, fix, valid=True):
+        return bool(check(lib().lio_rtk_track_feed(self.h, int(bool(valid)), C.byref(_fix(fix))), "track feed"))
+
+    def __len__(self):
+        return check(lib().lio_rtk_track_size(self.h), "track size")
+
+    def interpolate(self, stamp_us):
+        """(code, T): code is one of capi.RTK_*; T is None when the track refuses"""
+        T = np.zeros((4, 4))
+        rc = check(lib().lio_rtk_track_interpolate(self.h, int(stamp_us), ptr(T, C.c_double)), "track interpolate")
+        return rc, (T if rc in (capi.RTK_INTERPOLATED, capi.RTK_EXACT) else None)
+
+
+class GnssQueue:
+    """lio_gnss_queue: the pose graph's queue of fixes and its flush against the key frames, host only."""
+
+    def __init__(self):
+        self.h = lib().lio_gnss_queue_create()
+        if not self.h:
+            raise capi.LioError("lio_gnss_queue_create failed")
+        self.last_xyz = np.zeros(3)  # gps_last_update_pose
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_gnss_queue_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def set_origin(self, fix, last_keyframe_z=None):
+        z = np.zeros(3)
+        check(lib().lio_gnss_queue_set_origin(self.h, C.byref(_fix(fix)), int(last_keyframe_z is not None), float(last_keyframe_z or 0.0), ptr(z, C.c_double)),
+              "gnss set_origin")
+        return z
+
+    def push(self, fix):
+        check(lib().lio_gnss_queue_push(self.h, C.byref(_fix(fix))), "gnss push")
+
+    def __len__(self):
+        return check(lib().lio_gnss_queue_size(self.h), "gnss size")
+
+    def stamps(self):
+        out = np.zeros(max(len(self), 1), np.uint64)
+        n = check(lib().lio_gnss_queue_stamps(self.h, ptr(out, C.c_uint64), len(out)), "gnss stamps")
+        return out[:n]
+
+    def flush(self, kf_stamps, kf_has_fix):
+        """the matches as dicts; kf_has_fix (uint8 array) is updated in place, self.last_xyz as well"""
+        st = np.ascontiguousarray(kf_stamps, np.uint64)
+        assert kf_has_fix.dtype == np.uint8 and kf_has_fix.flags.c_contiguous and len(kf_has_fix) == len(st)
+        out = (capi.GnssMatch * max(len(st), 1))()
+        n = check(lib().lio_gnss_queue_flush(self.h, ptr(st, C.c_uint64), ptr(kf_has_fix, C.c_uint8), len(st), ptr(self.last_xyz, C.c_double), out, len(st)),
+                  "gnss flush")
+        return [dict(keyframe=m.keyframe, dimension=m.dimension, first=m.first_stamp_us, second=m.second_stamp_us, xyz=np.array(m.xyz), quat=np.array(m.quat),
+                     precision=m.precision) for m in out[:n]]
+
+
+class ScanMerge:
+    """lio_scan_merge: several lidars into one frame on the device (mergePoints + preprocessPoints of the RTKM method).  Cloud 0 is the base."""
+
+    def __init__(self, max_clouds=16, max_points=1 << 20, device=0):
+        self.h = lib().lio_scan_merge_create(device, int(max_clouds), int(max_points))
+        if not self.h:
+            raise capi.LioError("lio_scan_merge_create failed: " + lib().lio_last_error().decode())
+        self.n = 0
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_scan_merge_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def set_transform(self, T):
+        M = f64(T).reshape(4, 4)
+        check(lib().lio_scan_merge_set_transform(self.h, ptr(M, C.c_double)), "scan merge set_transform")
+
+    def run(self, clouds, stamps, headers, scan_period_us):
+        """clouds: list of N_l x 4 f32; stamps: list of N_l u32; headers: u64 per cloud.  Returns (n, kept, early, late) with per-cloud counts."""
+        L = len(clouds)
+        pts = [f32(c).reshape(-1, 4) for c in clouds]
+        sts = [np.ascontiguousarray(s, np.uint32).reshape(-1) for s in stamps]
+        assert len(sts) == L and len(headers) == L and all(len(p) == len(s) for p, s in zip(pts, sts))
+        pp = (C.POINTER(C.c_float) * L)(*[ptr(p, C.c_float) for p in pts])
+        sp = (C.POINTER(C.c_uint32) * L)(*[ptr(s, C.c_uint32) for s in sts])
+        n_l = np.array([len(p) for p in pts], np.uint32)
+        hd = np.array([int(h) for h in headers], np.uint64)
+        kept, early, late = np.zeros(L, np.uint32), np.zeros(L, np.uint32), np.zeros(L, np.uint32)
+        n = C.c_uint64(0)
+        check(lib().lio_scan_merge_run_host(self.h, L, pp, sp, ptr(n_l, C.c_uint32), ptr(hd, C.c_uint64), int(scan_period_us), ptr(kept, C.c_uint32),
+                                            ptr(early, C.c_uint32), ptr(late, C.c_uint32), C.byref(n)), "scan merge run")
+        self.n = int(n.value)
+        return self.n, kept, early, late
+
+    def download(self, cap=None):
+        """(points, stamps) of the last run; with a cap that is too small the call's own answer -(count)"""
+        cap = self.n if cap is None else int(cap)
+        pts, st = np.zeros((max(cap, 1), 4), np.float32), np.zeros(max(cap, 1), np.uint32)
+        m = lib().lio_scan_merge_download(self.h, ptr(pts, C.c_float), ptr(st, C.c_uint32), cap)
+        if m < 0:
+            if m == -self.n and self.n > cap:
+                return int(m)
+            check(int(m), "scan merge download")
+        return pts[:m], st[:m]
+
+    def device_view(self):
+        """(points address, stamps address, n) of the last frame on the device"""
+        st, n = C.POINTER(C.c_uint32)(), C.c_uint64(0)
+        p = lib().lio_scan_merge_device(self.h, C.byref(st), C.byref(n))
+        return p, C.cast(st, C.c_void_p).value, int(n.value)
+
+    def last_times(self):
+        """(upload_us, merge_us): device time of the last run"""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib().lio_scan_merge_last_times(self.h, C.byref(a), C.byref(b)), "scan merge times")
+        return a.value, b.value
