@@ -86,8 +86,10 @@ int lio_device_count(void);
  *      the graph hands back its edges as they were added: graph_save).  A removed node's id, and a retired frame's, is refused as unknown.
  * 22 = lio_utm_* / lio_grid_convergence / lio_transform_from_rpyt / lio_quat_of_transform / lio_interpolate_transform / lio_rtk_transform_* /
  *      lio_rtk_track_* / lio_gnss_queue_* (the GNSS side of mapping mode on the host: UTM projection, the RTK track of RTKM, the graph's GNSS
- *      queue) and lio_scan_merge_* (several lidars into one frame on the device: mergePoints + preprocessPoints). */
-#define LIO_ABI_VERSION 22
+ *      queue) and lio_scan_merge_* (several lidars into one frame on the device: mergePoints + preprocessPoints).
+ * 23 = lio_sc_set_positions / lio_sc_local_search (the INS-aided start of the relocalisation: GlobalLocalization::localSearch over the key
+ *      frames' positions resident beside the descriptors) and lio_update_origin (a map's poses and GNSS priors under another origin). */
+#define LIO_ABI_VERSION 23
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1453,6 +1455,26 @@ int lio_sc_search(lio_sc*, const double* desc, const float* ringkey, uint32_t n_
 /* globalSearch of a cloud: the matched frame's id (-1: the best score is not below dist_thres; 0.30 with point clouds alone), the yaw, the
  * score and the column shift behind the yaw (any may be NULL) */
 int lio_sc_global_search_host(lio_sc*, const float* xyzi, uint32_t n, double dist_thres, int32_t* match_id, float* yaw, double* score, int32_t* shift);
+/* the key frames' positions (n_frames x 3 f32: the translations of their poses rounded to f32), row k = bank id k, resident beside the
+ * descriptors; what localSearch's kd-tree (mGraphKDTree) holds.  n_frames must be the bank's number of frames when a local search runs */
+int lio_sc_set_positions(lio_sc*, const float* xyz, uint32_t n_frames);
+/* GlobalLocalization::localSearch (global_localization.cpp:350-385), the INS-aided start.  The cloud is described once under the shift (0, 0).
+ *   nearest     the min(10, F) frames nearest to (f32(ins_x), f32(ins_y), 0) among ALL F frames of the bank (the active set is not read: the
+ *               reference's kd-tree holds every key frame).  The query's z is 0 while a frame keeps its own z: the reference's quirk, kept.
+ *               f32 with d = frame - query: d2 = ((dx*dx) + dy*dy) + dz*dz.  In rising (d2, id): equal distances go to the SMALLER ID.  (PCL's
+ *               kd-tree leaves the order of ties undefined; this is the project's rule.)  A d2 that is not a number sorts after every number.
+ *   distances   distanceBtnScanContext of the cloud's descriptor to each of those frames, the bank's rows read by id on the device
+ *   walk        on the host, in that order, from match = -1 and min_dist = 1.0: without a match yet, f64(d2) > precision^2 ends the search
+ *               with -1 ("far from the map"); with one, f64(d2) > precision^2 / 10 ends the walk; otherwise the frame's distance is read and
+ *               wins by strict <.  No dist_thres applies.  n_examined = the distances the walk read.  An empty bank answers -1, 0 read.
+ * match_id -1 comes with yaw 0 and score 1.0.  ins_xyz[2] is not read.  LIO_E_STATE when the positions do not cover the bank;
+ * LIO_E_INVALID when ins_xyz[0], ins_xyz[1] or the precision is not finite (both gates would be false for them).
+ * Any output may be NULL */
+int lio_sc_local_search(lio_sc*, const float* xyzi, uint32_t n, const double ins_xyz[3], double precision, int32_t* match_id, float* yaw, double* score,
+                        int32_t* n_examined);
+/* what the last local search walked over: the nearest frames in rising (d2, id) with d2, Scan Context distance and column shift of each (10
+ * entries each, any may be NULL; places past the returned count min(10, F) hold -1, inf, NaN, -1), and the shift of the match (0 without one) */
+int lio_sc_last_local(lio_sc*, int32_t* ids, float* d2, double* dist, int32_t* shift, int32_t* match_shift);
 /* host only: the yaw of a column shift */
 float lio_sc_shift_to_yaw(int32_t shift);
 /* points the last add_frames / describe / global_search call dropped because a coordinate was not finite */
@@ -1795,6 +1817,13 @@ int lio_gnss_queue_size(const lio_gnss_queue*);
 int lio_gnss_queue_stamps(const lio_gnss_queue*, uint64_t* stamps, uint32_t cap);
 int lio_gnss_queue_flush(lio_gnss_queue*, const uint64_t* kf_stamps, uint8_t* kf_has_fix, uint32_t n_kf, double last_xyz[3], lio_gnss_match* out,
                          uint32_t cap);
+/* graph_update_origin's coordinate change (HG:1396-1449), in place: a map recorded under the origin `from` expressed under the origin `to`.  Two
+ * projectors made fresh as the reference makes them, each fixed to its zone by projecting its own origin (zero_utm_from, zero_utm_to).  Per
+ * translation -- of each of the n_poses row-major 4 x 4 poses and of each of the n_xyz points (a GNSS prior's measurement): (lat, lon) =
+ * inverse_from(x + zero_utm_from.x, y + zero_utm_from.y); (x, y) = forward_to(lat, lon) - zero_utm_to; z = z + from.altitude - to.altitude.
+ * Rotations are not touched (the reference does not turn them by the difference in grid convergence).  Only latitude, longitude and altitude
+ * of the two fixes are read.  Either array may be NULL with its count 0. */
+int lio_update_origin(const lio_rtk_fix* from, const lio_rtk_fix* to, double* poses16, uint32_t n_poses, double* xyz, uint32_t n_xyz);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Several lidars into one frame on the device (csrc/scanmerge.hip): mergePoints (slam/common/slam_utils.cpp:249-273) followed by

@@ -6,6 +6,7 @@
 //   lio_interpolate_transform  interpolateTransform (slam_utils.cpp:126-161) = the tail of RTKM::getInterpolatedTransform (rtkm.cpp:180-210)
 //   lio_rtk_transform_*      computeRTKTransform, the zero_utm form (slam_utils.cpp:112-124) and RTKM's origin form (rtkm.cpp:125-139)
 //   lio_rtk_track_*          RTKM's mTimedInsData: setOrigin / feedInsData / getInterpolatedTransform (rtkm.cpp:37-54, 91-95, 141-213)
+//   lio_update_origin        graph_update_origin's coordinate change (hdl_graph_slam_nodelet.cpp:1396-1449): a map under another origin
 //   lio_gnss_queue_*         the graph's gps_queue: set_origin / gps_callback / flush_gps_queue / interpolated_transform
 //                            (hdl_graph_slam_nodelet.cpp:141-156, 349-460, 653-660) up to the point where an edge is added
 //
@@ -311,6 +312,28 @@ int lio_rtk_transform_origin(lio_utm* u, const lio_rtk_fix* origin, const lio_rt
     dataY -= originY;
     dataZ = fix->altitude - origin->altitude;
     rtk_pose(u, fix, dataX, dataY, dataZ, T);
+    return LIO_OK;
+}
+
+// graph_update_origin (hdl_graph_slam_nodelet.cpp:1396-1449) without its graph: two projectors made fresh, each fixed to its zone by its own
+// origin; a translation goes back to latitude / longitude by the `from` projector and forward again by the `to` projector
+int lio_update_origin(const lio_rtk_fix* from, const lio_rtk_fix* to, double* poses16, uint32_t n_poses, double* xyz, uint32_t n_xyz) {
+    if (!from || !to || (n_poses && !poses16) || (n_xyz && !xyz)) return LIO_E_INVALID;
+    lio_utm projector_from{6, -1}, projector_to{6, -1};
+    double zero_utm_from[2], zero_utm_to[2];
+    lio_utm_forward(&projector_from, from->latitude, from->longitude, &zero_utm_from[0], &zero_utm_from[1]);
+    lio_utm_forward(&projector_to, to->latitude, to->longitude, &zero_utm_to[0], &zero_utm_to[1]);
+    auto move = [&](double* x, double* y, double* z) {
+        double lat, lon;
+        lio_utm_inverse(&projector_from, *x + zero_utm_from[0], *y + zero_utm_from[1], &lat, &lon);
+        double new_local_x, new_local_y;
+        lio_utm_forward(&projector_to, lat, lon, &new_local_x, &new_local_y);
+        *x = new_local_x - zero_utm_to[0];
+        *y = new_local_y - zero_utm_to[1];
+        *z = *z + from->altitude - to->altitude;
+    };
+    for (uint32_t k = 0; k < n_xyz; k++) move(xyz + 3 * (size_t)k, xyz + 3 * (size_t)k + 1, xyz + 3 * (size_t)k + 2);
+    for (uint32_t k = 0; k < n_poses; k++) move(poses16 + 16 * (size_t)k + 3, poses16 + 16 * (size_t)k + 7, poses16 + 16 * (size_t)k + 11);
     return LIO_OK;
 }
 

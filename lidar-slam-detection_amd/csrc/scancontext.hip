@@ -14,6 +14,9 @@
 //              difference under shift s (60 terms in column order); lane j the column cosine of column j under each of the seven shifts (20
 //              terms in row order); lanes 0..6 add a shift's 60 cosines in column order.  Every sum is sequential: with -ffp-contract=off the
 //              result is the restatement's to the last bit
+//   local      GlobalLocalization::localSearch (global_localization.cpp:350-385): the key frames' positions lie beside the descriptors; a key per
+//              frame (f32 squared distance to the INS position << 32 | id), the same selection, the same distance kernel over the bank's rows
+//              by id, and the walk over at most ten rows on the host
 // No floating-point atomics; no workgroup waits for another.
 #include <cfloat>
 #include <cmath>
@@ -164,6 +167,16 @@ __global__ void __launch_bounds__(kThreads) sc_ring_keys(const float* __restrict
     keys[(size_t)blockIdx.y * n_active + i] = ((unsigned long long)__float_as_uint(d) << 32) | id;
 }
 
+// localSearch's kd-tree query: keys[i] = f32 squared distance bits << 32 | i of frame i's position (pos: n x 3) to (qx, qy, 0) -- the query's z is
+// 0, the frame keeps its own.  A squared distance is never negative, so its bits order as the floats do (what is not a number: after all)
+__global__ void __launch_bounds__(kThreads) sc_pos_keys(const float* __restrict__ pos, uint32_t n, float qx, float qy, unsigned long long* __restrict__ keys) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float dx = pos[3 * (size_t)i] - qx, dy = pos[3 * (size_t)i + 1] - qy, dz = pos[3 * (size_t)i + 2];
+    const float d2 = ((dx * dx) + dy * dy) + dz * dz;
+    keys[i] = ((unsigned long long)(__float_as_uint(d2) & 0x7FFFFFFFu) << 32) | i;
+}
+
 // the kCand smallest keys of query blockIdx.x in rising order; cand[q][k] = id or -1, cand_d[q][k] = the f32 distance
 __global__ void __launch_bounds__(kThreads) sc_ring_select(const unsigned long long* __restrict__ keys, uint32_t n_active, int32_t* __restrict__ cand,
                                                            float* __restrict__ cand_d) {
@@ -306,6 +319,8 @@ struct lio_sc {
     // the bank
     double *desc = nullptr, *sector = nullptr, *norm = nullptr;
     float* ring = nullptr;
+    float* pos = nullptr;  // the key frames' positions, n_pos rows
+    uint32_t n_pos = 0;
     int32_t* d_active = nullptr;
     std::vector<int32_t> active;
     bool all_active = true;
@@ -328,6 +343,10 @@ struct lio_sc {
     double* cand_dist = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     double t_describe = 0, t_ring = 0, t_dist = 0;
+    // the last local search
+    int32_t loc_n = 0, loc_ids[kCand], loc_shift[kCand], loc_match_shift = 0;
+    float loc_d2[kCand];
+    double loc_dist[kCand];
 };
 
 namespace {
@@ -482,7 +501,7 @@ lio_sc* lio_sc_create(int device, uint32_t max_frames, uint32_t max_points_per_c
     h->max_points = max_points_per_call;
     bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&h->ev[0]) == hipSuccess && hipEventCreate(&h->ev[1]) == hipSuccess;
     ok = ok && regrow(&h->desc, (uint64_t)max_frames * kBins) == LIO_OK && regrow(&h->sector, (uint64_t)max_frames * kSectors) == LIO_OK &&
-         regrow(&h->norm, (uint64_t)max_frames * kSectors) == LIO_OK && regrow(&h->ring, (uint64_t)max_frames * kRings) == LIO_OK &&
+         regrow(&h->norm, (uint64_t)max_frames * kSectors) == LIO_OK && regrow(&h->ring, (uint64_t)max_frames * kRings) == LIO_OK && regrow(&h->pos, (uint64_t)max_frames * 3) == LIO_OK &&
          regrow(&h->d_active, (uint64_t)max_frames) == LIO_OK && regrow(&h->pts, (uint64_t)max_points_per_call) == LIO_OK && regrow(&h->d_bad, 1) == LIO_OK &&
          regrow(&h->keys, 1) == LIO_OK;
     if (!ok) {
@@ -499,7 +518,7 @@ void lio_sc_destroy(lio_sc* h) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->st) hipStreamSynchronize(h->st);
-    hipFree(h->desc); hipFree(h->sector); hipFree(h->norm); hipFree(h->ring); hipFree(h->d_active); hipFree(h->pts); hipFree(h->d_tab); hipFree(h->bins); hipFree(h->d_bad);
+    hipFree(h->desc); hipFree(h->sector); hipFree(h->norm); hipFree(h->ring); hipFree(h->pos); hipFree(h->d_active); hipFree(h->pts); hipFree(h->d_tab); hipFree(h->bins); hipFree(h->d_bad);
     for (int s = 0; s < 2; s++) { hipFree(h->q_desc[s]); hipFree(h->q_sector[s]); hipFree(h->q_norm[s]); }
     hipFree(h->q_ring); hipFree(h->keys); hipFree(h->cand); hipFree(h->cand_q); hipFree(h->cand_shift); hipFree(h->cand_rd); hipFree(h->cand_dist);
     if (h->h_tab) hipHostFree(h->h_tab);
@@ -512,6 +531,7 @@ void lio_sc_destroy(lio_sc* h) {
 int lio_sc_reset(lio_sc* h) {
     if (!h) return LIO_E_INVALID;
     h->n_frames = 0;
+    h->n_pos = 0;
     h->active.clear();
     h->all_active = true;
     return LIO_OK;
@@ -698,6 +718,89 @@ int lio_sc_global_search_host(lio_sc* h, const float* xyzi, uint32_t n, double d
     if (score) *score = min_dist;
     if (shift) *shift = best_shift;
     return LIO_OK;
+}
+
+int lio_sc_set_positions(lio_sc* h, const float* xyz, uint32_t n_frames) {
+    if (!h || (n_frames && !xyz)) return LIO_E_INVALID;
+    if (n_frames > h->max_frames) { set_error("lio_sc_set_positions: %u positions exceed max_frames %u", n_frames, h->max_frames); return LIO_E_CAPACITY; }
+    hipSetDevice(h->device);
+    LIO_HIP_TRY(hipStreamSynchronize(h->st));
+    if (n_frames) LIO_HIP_TRY(hipMemcpy(h->pos, xyz, (size_t)n_frames * 3 * sizeof(float), hipMemcpyHostToDevice));
+    h->n_pos = n_frames;
+    return LIO_OK;
+}
+
+int lio_sc_local_search(lio_sc* h, const float* xyzi, uint32_t n, const double ins_xyz[3], double precision, int32_t* match_id, float* yaw, double* score,
+                        int32_t* n_examined) {
+    if (!h || (n && !xyzi) || !ins_xyz) return LIO_E_INVALID;
+    if (!(ins_xyz[0] - ins_xyz[0] == 0.0 && ins_xyz[1] - ins_xyz[1] == 0.0 && precision - precision == 0.0)) {  // (both gates are false for what is not a number)
+        set_error("lio_sc_local_search: the INS position or the precision is not finite");
+        return LIO_E_INVALID;
+    }
+    if (h->n_pos != h->n_frames) { set_error("lio_sc_local_search: %u positions for a bank of %u frames (lio_sc_set_positions)", h->n_pos, h->n_frames); return LIO_E_STATE; }
+    hipSetDevice(h->device);
+    h->t_describe = h->t_ring = h->t_dist = 0;
+    const uint32_t F = h->n_frames;
+    const int nc = (int)(F < (uint32_t)kCand ? F : (uint32_t)kCand);
+    h->loc_n = nc;
+    h->loc_match_shift = 0;
+    for (int k = 0; k < kCand; k++) { h->loc_ids[k] = -1; h->loc_shift[k] = -1; h->loc_d2[k] = INFINITY; h->loc_dist[k] = (double)NAN; }
+    int32_t best_id = -1, best_shift = 0, examined = 0;
+    double min_dist = 1.0;
+    if (nc > 0) {  // (an empty tree: nearestKSearch answers 0 and localSearch returns before it describes the cloud)
+        static const double kHere[2] = {0, 0};
+        int rc = describe_query(h, "lio_sc_local_search", xyzi, n, kHere, 1);
+        if (rc != LIO_OK) return rc;
+        {
+            Span sp(h, &h->t_ring);
+            if (F > h->keys_cap) {
+                LIO_HIP_TRY(hipStreamSynchronize(h->st));
+                h->keys_cap = 0;
+                rc = regrow(&h->keys, F);
+                if (rc != LIO_OK) return rc;
+                h->keys_cap = F;
+            }
+            hipLaunchKernelGGL(sc_pos_keys, (F + kThreads - 1) / kThreads, kThreads, 0, h->st, h->pos, F, (float)ins_xyz[0], (float)ins_xyz[1], h->keys);
+            hipLaunchKernelGGL(sc_ring_select, 1, kThreads, 0, h->st, h->keys, F, h->cand, h->cand_rd);
+            LIO_HIP_TRY(hipGetLastError());
+        }
+        {
+            Span sp(h, &h->t_dist);
+            LIO_HIP_TRY(hipMemsetAsync(h->cand_q, 0, nc * sizeof(int32_t), h->st));  // every pair takes query 0
+            const DescSet A{h->q_desc[0], h->q_sector[0], h->q_norm[0]}, B{h->desc, h->sector, h->norm};
+            hipLaunchKernelGGL(sc_distance, nc, 64, 0, h->st, A, B, h->cand_q, h->cand, h->cand_dist, h->cand_shift);
+            LIO_HIP_TRY(hipGetLastError());
+        }
+        LIO_HIP_TRY(hipMemcpyAsync(h->loc_d2, h->cand_rd, kCand * sizeof(float), hipMemcpyDeviceToHost, h->st));
+        rc = download_candidates(h, 1, h->loc_ids, h->loc_dist, h->loc_shift, nullptr);  // ends with the stream's synchronisation: loc_d2 is in too
+        if (rc != LIO_OK) return rc;
+        for (int k = nc; k < kCand; k++) { h->loc_dist[k] = (double)NAN; h->loc_shift[k] = -1; }  // places no pair was launched for
+        // the walk of global_localization.cpp:366-381
+        const double p2 = precision * precision;
+        for (int i = 0; i < nc; i++) {
+            const double d2 = (double)h->loc_d2[i];
+            if (best_id == -1 && d2 > p2) break;  // far away from the map (best_id is -1: the answer)
+            if (best_id != -1 && d2 > p2 / 10.0) break;
+            examined++;
+            if (h->loc_dist[i] < min_dist) { min_dist = h->loc_dist[i]; best_id = h->loc_ids[i]; best_shift = h->loc_shift[i]; }
+        }
+    }
+    h->loc_match_shift = best_shift;
+    if (match_id) *match_id = best_id;
+    if (yaw) *yaw = lio_sc_shift_to_yaw(best_shift);
+    if (score) *score = min_dist;
+    if (n_examined) *n_examined = examined;
+    return LIO_OK;
+}
+
+int lio_sc_last_local(lio_sc* h, int32_t* ids, float* d2, double* dist, int32_t* shift, int32_t* match_shift) {
+    if (!h) return LIO_E_INVALID;
+    if (ids) memcpy(ids, h->loc_ids, sizeof(h->loc_ids));
+    if (d2) memcpy(d2, h->loc_d2, sizeof(h->loc_d2));
+    if (dist) memcpy(dist, h->loc_dist, sizeof(h->loc_dist));
+    if (shift) memcpy(shift, h->loc_shift, sizeof(h->loc_shift));
+    if (match_shift) *match_shift = h->loc_match_shift;
+    return h->loc_n;
 }
 
 int lio_sc_last_dropped(lio_sc* h, uint64_t* n_nonfinite) {

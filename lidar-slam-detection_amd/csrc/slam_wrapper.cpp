@@ -141,21 +141,36 @@ struct Loc {
     // detector over it; key-frame id -> bank frame
     struct MergeEdge { int a, b, kernel; double M[16], info[36]; };
     std::vector<MergeEdge> medges;
+    // under set_gnss the GNSS priors of both maps' graph.g2o (EDGE_SE3_PRIORXYZ / _PRIORQUAT with their kernels) belong to the record too
+    struct MergePrior { int kf, type, kernel; double m[4], info[9], delta; };
+    std::vector<MergePrior> mpriors;
     std::set<int> mfixed;
     bool have_mgraph = false;
     lio_loop* mbank = nullptr;
     lio_overlap* moverlap = nullptr;
     std::map<int, int> bank_of_kf;
     uint32_t bank_max_points = 0, ndt_biggest = 0;
-    struct MergeReport { std::vector<std::array<int, 2>> overlaps; std::vector<double> scores; std::vector<int> reasons, new_ids; int fragments = 0, skipped_tags = 0; } merge_report;
+    struct MergeReport { std::vector<std::array<int, 2>> overlaps; std::vector<double> scores; std::vector<int> reasons, new_ids; int fragments = 0, skipped_tags = 0, priors = 0;
+                         bool origin_updated = false; } merge_report;
     // global relocalisation (GlobalLocalization::globalSearch + registrationAlign, global_localization.cpp:387-413, 456-482): off unless
     // set_global_localization(true) / LSD_AMD_RELOC=1.  The bank holds the descriptors of the key frames' local clouds, frame k = key frame k
     bool reloc = false;
     lio_sc* sc = nullptr;
     lio_gicp* reloc_gicp = nullptr;
     std::vector<float> reloc_ds;
-    struct Reloc { bool searched = false, accepted = false; int match_id = -1, converged = 0; double score = 0, fitness = 0, dx = 0, da = 0; float yaw = 0; } last_reloc;
+    struct Reloc { bool searched = false, accepted = false, local = false; int match_id = -1, converged = 0, n_examined = 0; double score = 0, fitness = 0, dx = 0, da = 0;
+                   float yaw = 0; Mat4 guess = Mat4::identity(); } last_reloc;
     int reloc_searches = 0;  // searches run since init_slam
+    // GNSS in localisation mode (set_gnss; Localization::feedInsData, localization.cpp:199-209): a valid fix of a map with an origin, with its pose
+    // T = computeRTKTransform(projector, fix, zero_utm).  Not initialised: the latest one, which the next search consumes (runSearchPose drains its
+    // queue and keeps the newest, global_localization.cpp:288-296).  Initialised: the localiser's ins_data (ins_callback: at most 10, the oldest
+    // leaves first) and what the bracket rule made of it for the last located frame
+    struct Ins { lio_rtk_fix f = lio_rtk_fix(); Mat4 T = Mat4::identity(); };
+    bool have_latest_ins = false;
+    Ins latest_ins;
+    std::deque<Ins> ins_data;
+    struct GpsUse { bool used = false; Mat4 T = Mat4::identity(); double precision = 0, ratio = 0; int dimension = 0; } last_gps;
+    double sc_dist_thres = 0.30;  // 0.25 under set_gnss (the sensor-fusion configuration, global_localization.cpp:25-35)
     // the operator's hint (GlobalLocalization::getEstimatePose / setInitPose's mLastFrame / initializePose's pose * delta).  The last frame is
     // the downsampled cloud in `scan` (have_last_frame: the scan holds the reduced cloud of the most recent non-empty frame); an accepted hint
     // keeps its pose and a device copy of that frame (slot 1 of the local map) until the next non-empty frame hands over to the filter
@@ -503,7 +518,10 @@ bool loc_fill_sc(Loc& L) {
         }
         if (lio_sc_add_frames_host(L.sc, buf.data(), off.data(), (uint32_t)(k1 - k0)) != (int)k0) return false;
     }
-    return true;
+    // mGraphKDTree (feedInitData): every key frame's position, for the INS-aided search
+    std::vector<float> pos;
+    for (const KeyFrameDisk& kf : L.frames) for (int a = 0; a < 3; a++) pos.push_back((float)kf.odom(a, 3));
+    return lio_sc_set_positions(L.sc, pos.data(), (uint32_t)L.frames.size()) == LIO_OK;
 }
 
 // yaw2matrix (Scancontext.cpp:68-75): cos / sin of the f32 angle
@@ -528,7 +546,7 @@ bool loc_reduce_staged(Loc& L, uint32_t n, uint32_t& n_ds) {
 
 // GlobalLocalization::globalSearch + registrationAlign with the cloud in L.staged: true when an initial pose was accepted into L.init_pose.
 // DEVIATION: synchronous, on every uninitialised frame (the reference's search thread drops the frames that arrive while it is busy and
-// registers the next one against the frame it searched with); localSearch (INS-aided) and the image search are not built
+// registers the next one against the frame it searched with); the image search is not built.  With a fix held (set_gnss) localSearch runs instead
 bool loc_relocalize(Loc& L, uint32_t n) {
     Loc::Reloc& r = L.last_reloc;
     r = Loc::Reloc();
@@ -544,7 +562,18 @@ bool loc_relocalize(Loc& L, uint32_t n) {
     r.searched = true;
     L.reloc_searches++;
     int32_t id = -1;
-    if (lio_sc_global_search_host(L.sc, L.reloc_ds.data(), n_ds, 0.30, &id, &r.yaw, &r.score, nullptr) != LIO_OK) return false;
+    // runSearchPose (global_localization.cpp:311-323): with an INS fix held the local search runs INSTEAD of the global one -- no fallback on this
+    // frame -- and the fix is consumed
+    const bool local = L.have_latest_ins;
+    const Loc::Ins ins = L.latest_ins;
+    L.have_latest_ins = false;
+    r.local = local;
+    if (local) {
+        const double xyz[3] = {ins.T(0, 3), ins.T(1, 3), ins.T(2, 3)};
+        int32_t ne = 0;
+        if (lio_sc_local_search(L.sc, L.reloc_ds.data(), n_ds, xyz, ins.f.precision, &id, &r.yaw, &r.score, &ne) != LIO_OK) return false;
+        r.n_examined = ne;
+    } else if (lio_sc_global_search_host(L.sc, L.reloc_ds.data(), n_ds, L.sc_dist_thres, &id, &r.yaw, &r.score, nullptr) != LIO_OK) return false;
     r.match_id = id;
     if (id < 0 || (size_t)id >= L.frames.size()) return false;
     // select_registration_method("FAST_VGICP"): the loop detector's coarse configuration
@@ -560,7 +589,23 @@ bool loc_relocalize(Loc& L, uint32_t n) {
         if (!L.reloc_gicp || lio_gicp_set_voxel_mode(L.reloc_gicp, lp.voxel_resolution, 1) != LIO_OK) return false;
     }
     if (lio_gicp_set_target(L.reloc_gicp, kf.local.data(), nt) != LIO_OK || lio_gicp_set_source(L.reloc_gicp, L.reloc_ds.data(), n_ds) != LIO_OK) return false;
-    const Mat4 guess = yaw_matrix_f32(-r.yaw);
+    Mat4 guess = yaw_matrix_f32(-r.yaw);
+    if (local && ins.f.dimension == 6) {
+        // :313-315: kf.odom.cast<float>().inverse() * ins.T.cast<float>() in f32 (the inverse taken as a rigid one), the height set to 0
+        float K[16], I[16], G[16];
+        for (int i = 0; i < 16; i++) { K[i] = (float)kf.odom.m[i]; I[i] = (float)ins.T.m[i]; }
+        float Ki[16] = {K[0], K[4], K[8], 0.f, K[1], K[5], K[9], 0.f, K[2], K[6], K[10], 0.f, 0.f, 0.f, 0.f, 1.f};
+        for (int a = 0; a < 3; a++) Ki[4 * a + 3] = -(Ki[4 * a] * K[3] + Ki[4 * a + 1] * K[7] + Ki[4 * a + 2] * K[11]);
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) {
+                float v = 0.f;
+                for (int c = 0; c < 4; c++) v += Ki[4 * a + c] * I[4 * c + b];
+                G[4 * a + b] = v;
+            }
+        for (int i = 0; i < 16; i++) guess.m[i] = (double)G[i];
+        guess(2, 3) = 0.0;
+    }
+    r.guess = guess;
     lio_ndt_params p;
     lio_ndt_default_params(&p);
     p.rotation_epsilon_deg = lp.coarse_rotation_epsilon_deg;
@@ -753,6 +798,8 @@ bool loc_localize(Slam* s, uint32_t n, uint64_t stamp, Mat4& pose_out) {
         L.init_stamp = stamp;
         L.pose_data.clear();
         L.imu_data.clear();
+        L.ins_data.clear();  // a fresh localiser
+        L.last_gps = Loc::GpsUse();
         L.last_odom = T;
         L.initialized = true;
         L.age = 0;
@@ -791,13 +838,44 @@ bool loc_localize(Slam* s, uint32_t n, uint64_t stamp, Mat4& pose_out) {
     if (L.resolution >= 0.1) { if (lio_scan_voxel_downsample(L.scan, (float)L.resolution, 1, &n_ds) != LIO_OK) return false; }
     else { std::vector<float> raw(4 * (size_t)n); lio_scan_download_raw(L.scan, raw.data(), n); lio_scan_set_ds(L.scan, raw.data(), n); n_ds = n; }
     L.have_last_frame = n_ds > 0;  // DEVIATION: mLastFrame is refreshed while localising too (the reference matches a hint against a stale scan)
+    // ins process (hdl_localization_nodelet.cpp:231-261), statement for statement: the pair of fixes around the scan's stamp
+    lio_gps_observation gps_obs;
+    const lio_gps_observation* gps = nullptr;
+    L.last_gps = Loc::GpsUse();
+    if (!L.ins_data.empty()) {
+        if (stamp > L.ins_data.back().f.stamp_us) {
+            L.ins_data.clear();
+        } else if (stamp >= L.ins_data.front().f.stamp_us) {
+            bool gps_data_valid = false;
+            size_t first_ins = 0, second_ins = 0;
+            for (; second_ins != L.ins_data.size(); second_ins++) {
+                const double dt = (L.ins_data[first_ins].f.stamp_us - double(stamp)) / 1000000.0;
+                const double dt2 = (L.ins_data[second_ins].f.stamp_us - double(stamp)) / 1000000.0;
+                if (dt <= 0 && dt2 >= 0 && (dt2 - dt) < 0.2) { gps_data_valid = true; break; }
+                first_ins = second_ins;
+            }
+            if (gps_data_valid) {
+                const Loc::Ins &a1 = L.ins_data[first_ins], &a2 = L.ins_data[second_ins];
+                const double t_diff_ratio = static_cast<double>(stamp - a1.f.stamp_us) / static_cast<double>(a2.f.stamp_us - a1.f.stamp_us + 1);
+                L.last_gps.used = true;
+                L.last_gps.precision = a1.f.precision;
+                L.last_gps.dimension = a1.f.dimension;
+                L.last_gps.ratio = t_diff_ratio;
+                lio_interpolate_transform(a1.T.m, a2.T.m, t_diff_ratio, L.last_gps.T.m);
+                std::memcpy(gps_obs.T, L.last_gps.T.m, sizeof(gps_obs.T));
+                gps_obs.precision = a1.f.precision;
+                gps_obs.dimension = a1.f.dimension;
+                gps = &gps_obs;
+            }
+        }
+    }
     // correct
     float obs[7], cov[49];
     bool result = false;
     double fitness = 0.0;
     if (L.have_map) {
         int it = 0;
-        const int rc = lio_pose_estimator_match_gps(L.pe, L.ndt, L.scan, &L.par, nullptr, obs, cov, &it);
+        const int rc = lio_pose_estimator_match_gps(L.pe, L.ndt, L.scan, &L.par, gps, obs, cov, &it);
         result = rc == 1;
         if (stamp - L.init_stamp < 10000000) {  // WARM_UP_TIME: getFitnessScore(25) of the alignment (pose_estimator.cpp:254-264)
             double T[16] = {0, 0, 0, obs[0], 0, 0, 0, obs[1], 0, 0, 0, obs[2], 0, 0, 0, 1};
@@ -809,7 +887,7 @@ bool loc_localize(Slam* s, uint32_t n, uint64_t stamp, Mat4& pose_out) {
             lio_ndt_fitness_score(L.ndt, L.scan, T, 25.0, &fitness, &n_in);
         }
     } else {
-        result = lio_pose_estimator_match_gps_only(L.pe, nullptr, obs, cov) == 1;
+        result = lio_pose_estimator_match_gps_only(L.pe, gps, obs, cov) == 1;
     }
     lio_pose_estimator_correct(L.pe, stamp, obs);
     float M[16];
@@ -1155,6 +1233,26 @@ lio_render* live_painter(Slam* s) {
     return s->painter;
 }
 
+// what process() does with a fix in localisation mode under set_gnss (_push_gnss calls it too): preprocessInsData's validity test, then
+// Localization::feedInsData (localization.cpp:199-209) -- dropped unless valid and the map has an origin; T = computeRTKTransform(projector, fix,
+// zero_utm); the global locator keeps the newest, the localiser a list of ten (ins_callback).  Returns rtk_valid
+bool loc_feed_fix(Slam* s, py::dict& rtk_dict, uint64_t timestamp) {
+    Fix fix = fix_of(rtk_dict);
+    const bool rtk_valid = fix.has_stamp && preprocess_ins(s, timestamp, fix);
+    if (!rtk_valid || !s->have_zero_utm) return rtk_valid;
+    Loc& L = *s->loc;
+    Loc::Ins ins;
+    ins.f = fix.f;
+    std::lock_guard<std::mutex> lk(s->mtx);
+    require(lio_rtk_transform_utm(s->utm, &fix.f, s->zero_utm, ins.T.m) == LIO_OK, "process: the fix's projection failed");
+    if (!L.initialized) { L.latest_ins = ins; L.have_latest_ins = true; }
+    else {
+        if (L.ins_data.size() >= 10) L.ins_data.pop_front();
+        L.ins_data.push_back(ins);
+    }
+    return rtk_valid;
+}
+
 // SLAM::run, localisation branch (slam.cpp:273-367) over Localization::feedImuData / feedPointData / getPose
 py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, py::dict& image_dict, py::dict& image_param, py::dict& rtk_dict,
                               py::array_t<double>& imu_list, uint64_t timestamp) {
@@ -1189,11 +1287,16 @@ py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, 
             imu_in.push_back(m);
         }
     }
+    // SLAM::run's GNSS lines (slam.cpp:280-292) in localisation mode, behind set_gnss: the validity filter mapping mode uses; with the switch off
+    // the fix is not looked at
+    const bool gnss_side = s->gnss && s->use_gps;
+    const bool rtk_valid = gnss_side && loc_feed_fix(s, rtk_dict, timestamp);
     Mat4 out_pose = Mat4::identity();
     bool located = false, inited = false;
     {
         py::gil_scoped_release release;
         std::lock_guard<std::mutex> lk(s->mtx);
+        L.sc_dist_thres = gnss_side ? 0.25 : 0.30;  // like everything of the switch here: only with RTK among the sensors
         if (L.initialized) L.imu_data.insert(L.imu_data.end(), imu_in.begin(), imu_in.end());  // Localization::feedImuData: dropped while not initialised
         // preprocessPoints (slam_base.h:83-85) straight into the staging vector
         L.staged.resize(4 * (size_t)n + 4);
@@ -1249,7 +1352,7 @@ py::dict process_localization(Slam* s, py::dict& points, py::dict& points_attr, 
     pose["Vn"] = 0;
     pose["Vu"] = 0;
     pose["Status"] = status;
-    pose["state"] = inited ? "Localizing(L)" : "Initializing";
+    pose["state"] = inited ? ((gnss_side && rtk_valid) ? "Localizing(L+G)" : "Localizing(L)") : "Initializing";  // slam.cpp:324-332
     pose["timestamp"] = header_stamp;
     pose["odom_matrix"] = mat4_to_numpy_f32(out_pose);
     py::dict data;
@@ -1902,6 +2005,11 @@ py::dict _last_relocalization() {
     d["da"] = r.da;
     d["accepted"] = r.accepted;
     d["searches"] = g->loc->reloc_searches;
+    d["kind"] = r.local ? "local" : "global";
+    d["n_examined"] = r.n_examined;
+    py::array_t<double> guess({(py::ssize_t)4, (py::ssize_t)4});
+    std::memcpy(guess.mutable_data(), r.guess.m, sizeof(r.guess.m));
+    d["guess"] = guess;  // what registrationAlign started from
     return d;
 }
 // test visibility: the report of the last get_estimate_pose call, and the delta of the hand-over once it has happened
@@ -1958,7 +2066,9 @@ void set_pose_graph(bool enable) {
 }
 // not in the reference's module (whose GNSS side always runs): the GNSS side of FastLIO mapping -- the map origin from the first valid fix, the
 // fixes queued for the graph and flushed into priors by update_odom() -- off by default; LSD_AMD_GNSS=1 at init_slam switches it on for an
-// unchanged slam.py.  RTKM needs no switch
+// unchanged slam.py.  RTKM needs no switch.  In localisation mode (with "RTK" among the sensors and a map that has an origin) the same switch
+// lets the fix in: a valid fix starts the relocalisation near the INS position (localSearch instead of the nine-shift global search, whose
+// threshold is 0.25 under the switch), the fixes around a scan's stamp are fused by the pose filter, and the state reads "Localizing(L+G)"
 void set_gnss(bool enable) {
     require((bool)g, "init_slam first");
     py::gil_scoped_release rel;
@@ -1968,7 +2078,11 @@ void set_gnss(bool enable) {
 // test visibility: what process() does with a fix (the validity filter, the origin, the method's feedInsData, FastLIO's velocity hand-over when
 // there is an engine) and nothing else; the frame's timestamp is the fix's own
 void _push_gnss(py::dict rtk_dict) {
-    require((bool)g && !g->loc, "init_slam in mapping mode first");
+    require((bool)g, "init_slam first");
+    if (g->loc) {  // localisation mode: the fix's way into the localiser, when the switch is on and RTK is a sensor
+        if (g->gnss && g->use_gps) (void)loc_feed_fix(g.get(), rtk_dict, rtk_dict.contains("timestamp") ? py::cast<uint64_t>(rtk_dict["timestamp"]) : 0);
+        return;
+    }
     Fix fix = fix_of(rtk_dict);
     feed_fix(g.get(), rtk_dict, fix, fix.f.stamp_us);
 }
@@ -2008,6 +2122,23 @@ py::dict _gnss_state() {
     d["origin_set"] = g->origin_set;
     d["queued"] = queued;
     d["tracked"] = tracked;
+    if (g->loc) {  // localisation mode: the localiser's list of fixes, the fix held for the next search, the observation of the last located frame
+        std::lock_guard<std::mutex> lk(g->mtx);
+        const Loc& L = *g->loc;
+        std::vector<uint64_t> stamps;
+        for (const Loc::Ins& i : L.ins_data) stamps.push_back(i.f.stamp_us);
+        d["stamps"] = stamps;
+        d["latest_held"] = L.have_latest_ins;
+        py::dict o;
+        o["used"] = L.last_gps.used;
+        py::array_t<double> T({(py::ssize_t)4, (py::ssize_t)4});
+        std::memcpy(T.mutable_data(), L.last_gps.T.m, sizeof(L.last_gps.T.m));
+        o["T"] = T;
+        o["precision"] = L.last_gps.precision;
+        o["dimension"] = L.last_gps.dimension;
+        o["ratio"] = L.last_gps.ratio;
+        d["observation"] = o;
+    }
     return d;
 }
 // test visibility: a key frame (points N x 4 f32, odometry pose 4 x 4 f64, stamp, accumulated distance) for the next update_odom(), as if the
@@ -2265,6 +2396,38 @@ void record_take_file(std::vector<Loc::MergeEdge>& edges, std::set<int>& fixed, 
         edges.push_back(me);
     }
 }
+// the GNSS priors of one map's file into the record (set_gnss): EDGE_SE3_PRIORXYZ = x y z + the information's upper triangle, EDGE_SE3_PRIORQUAT =
+// w x y z + the same; a line of <file>.kernels that names the prior's vertex alone gives its kernel (one such line serves every prior of that
+// vertex: the mapping side puts Huber 1.0 on both).  A prior on a vertex without a key frame, or one that is not complete, is passed over.
+// Returns the number taken
+int record_take_priors(std::vector<Loc::MergePrior>& priors, const G2oFile& gf, const std::map<int, int>& id_of) {
+    int taken = 0;
+    for (const auto& p : gf.priors) {
+        auto it = id_of.find(p.node);
+        const bool xyz = p.tag == "EDGE_SE3_PRIORXYZ";
+        if (it == id_of.end() || p.values.size() != (xyz ? 9u : 10u)) continue;
+        Loc::MergePrior mp;
+        mp.kf = it->second;
+        mp.type = xyz ? LIO_GRAPH_PRIOR_XYZ : LIO_GRAPH_PRIOR_QUAT;
+        if (xyz) { mp.m[0] = p.values[0]; mp.m[1] = p.values[1]; mp.m[2] = p.values[2]; mp.m[3] = 0.0; }
+        else { mp.m[0] = p.values[1]; mp.m[1] = p.values[2]; mp.m[2] = p.values[3]; mp.m[3] = p.values[0]; }
+        const double* u = p.values.data() + (xyz ? 3 : 4);
+        int at = 0;
+        for (int r = 0; r < 3; r++)
+            for (int c = r; c < 3; c++) { mp.info[r * 3 + c] = u[at]; mp.info[c * 3 + r] = u[at]; at++; }
+        mp.kernel = LIO_GRAPH_KERNEL_NONE;
+        mp.delta = 1.0;
+        for (const auto& k : gf.kernels)
+            if (k.vertices.size() == 1 && k.vertices[0] == p.node && k.delta > 0) {
+                mp.kernel = k.type == "Huber" ? LIO_GRAPH_KERNEL_HUBER : k.type == "DCS2" ? LIO_GRAPH_KERNEL_DCS2 : LIO_GRAPH_KERNEL_NONE;
+                mp.delta = k.delta;
+                break;
+            }
+        priors.push_back(mp);
+        taken++;
+    }
+    return taken;
+}
 void graph_add(lio_graph* gr, const std::map<int, int>& node_of_kf, const Loc::MergeEdge& e) {
     require(lio_graph_add_edge(gr, node_of_kf.at(e.a), node_of_kf.at(e.b), e.M, e.info, e.kernel, 1.0) >= 0, "merge_map: lio_graph_add_edge failed");
 }
@@ -2298,10 +2461,15 @@ void optimize_and_sync(Loc& L, lio_graph* gr, const std::map<int, int>& node_of_
             if (b != L.bank_of_kf.end()) require(lio_loop_set_pose(L.mbank, b->second, kf.odom.m) == LIO_OK, "merge_map: lio_loop_set_pose failed");
         }
 }
-struct MergeInput { std::vector<KeyFrameDisk> fresh; G2oFile ref_g2o, new_g2o; };
+struct MergeInput {
+    std::vector<KeyFrameDisk> fresh;
+    G2oFile ref_g2o, new_g2o;
+    bool reanchor = false;  // set_gnss and origins that differ: the new map goes under the loaded map's origin (`from` -> `to`)
+    lio_rtk_fix from = lio_rtk_fix(), to = lio_rtk_fix();
+};
 // the merge itself, under the lock of process() and without the GIL.  It works on its own copies -- the record of the graph, a device graph of
 // its own, the report -- and changes the key-frame list's poses and the bank as it goes; the caller undoes those when it throws
-void merge_locked(Slam* s, MergeInput& in, std::vector<Loc::MergeEdge>& edges, std::set<int>& fixed, Loc::MergeReport& report) {
+void merge_locked(Slam* s, MergeInput& in, std::vector<Loc::MergeEdge>& edges, std::vector<Loc::MergePrior>& priors, std::set<int>& fixed, Loc::MergeReport& report) {
     Loc& L = *s->loc;
     std::vector<KeyFrameDisk>& fresh = in.fresh;
     uint32_t biggest = 1024;
@@ -2313,6 +2481,7 @@ void merge_locked(Slam* s, MergeInput& in, std::vector<Loc::MergeEdge>& edges, s
         for (const KeyFrameDisk& kf : L.frames) same[kf.id] = kf.id;
         record_take_file(edges, fixed, in.ref_g2o, same);
         report.skipped_tags = in.ref_g2o.skipped;
+        if (s->gnss) report.skipped_tags -= record_take_priors(priors, in.ref_g2o, same);  // (taken, not passed over)
     }
     // graph_merge (hdl_graph_slam_nodelet.cpp:1222-1336): new vertex ids max + 1 ... in key-frame order, the new edges behind the graph's
     int max_id = 0;
@@ -2321,6 +2490,23 @@ void merge_locked(Slam* s, MergeInput& in, std::vector<Loc::MergeEdge>& edges, s
     for (KeyFrameDisk& kf : fresh) { renamed[kf.id] = ++max_id; kf.id = max_id; }
     record_take_file(edges, fixed, in.new_g2o, renamed);
     report.skipped_tags += in.new_g2o.skipped;
+    const size_t first_new_prior = priors.size();
+    if (s->gnss) report.skipped_tags -= record_take_priors(priors, in.new_g2o, renamed);
+    if (in.reanchor) {
+        // graph_update_origin (hdl_graph_slam_nodelet.cpp:1396-1449, map_loader.cpp:104-112): the new map's poses (its vertex estimates: a node's
+        // estimate is its key frame's pose) and the measurements of its EDGE_SE3_PRIORXYZ edges go under the loaded map's origin
+        std::vector<double> poses(16 * fresh.size()), xyz;
+        for (size_t k = 0; k < fresh.size(); k++) std::memcpy(&poses[16 * k], fresh[k].odom.m, 16 * sizeof(double));
+        for (size_t k = first_new_prior; k < priors.size(); k++)
+            if (priors[k].type == LIO_GRAPH_PRIOR_XYZ) xyz.insert(xyz.end(), priors[k].m, priors[k].m + 3);
+        require(lio_update_origin(&in.from, &in.to, poses.data(), (uint32_t)fresh.size(), xyz.data(), (uint32_t)(xyz.size() / 3)) == LIO_OK, "merge_map: lio_update_origin failed");
+        for (size_t k = 0; k < fresh.size(); k++) std::memcpy(fresh[k].odom.m, &poses[16 * k], 16 * sizeof(double));
+        size_t at = 0;
+        for (size_t k = first_new_prior; k < priors.size(); k++)
+            if (priors[k].type == LIO_GRAPH_PRIOR_XYZ) { std::memcpy(priors[k].m, &xyz[at], 3 * sizeof(double)); at += 3; }
+        report.origin_updated = true;
+    }
+    report.priors = (int)priors.size();
     // the device graph of this call: node estimates are the key frames' odom
     struct Graph { lio_graph* h = nullptr; ~Graph() { if (h) lio_graph_destroy(h); } } gr;
     gr.h = lio_graph_create(0, nullptr);
@@ -2334,6 +2520,9 @@ void merge_locked(Slam* s, MergeInput& in, std::vector<Loc::MergeEdge>& edges, s
         }
     for (int id : fixed) require(lio_graph_set_fixed(gr.h, node_of_kf.at(id), 1) == LIO_OK, "merge_map: lio_graph_set_fixed failed");
     for (const Loc::MergeEdge& e : edges) graph_add(gr.h, node_of_kf, e);
+    for (const Loc::MergePrior& p : priors)
+        require(lio_graph_add_prior(gr.h, node_of_kf.at(p.kf), p.type, p.m, nullptr, p.info, p.kernel, p.delta) >= 0, "merge_map: lio_graph_add_prior failed");
+    if (in.reanchor) optimize_and_sync(L, gr.h, node_of_kf, {&L.frames, &fresh});  // the graph_optimize at the end of graph_update_origin + the sync (map_loader.cpp:111)
     if (!L.mbank) {
         lio_loop_params lp;
         lio_loop_default_params(&lp);
@@ -2424,8 +2613,15 @@ py::dict merge_map(const std::string& directory) {
     if (!read_g2o(directory + "/graph/graph.g2o", in.new_g2o, err)) return merge_refused(err.c_str());
     if (ref_info.coordinate != new_info.coordinate) return merge_refused("coordinate system is not consistent");
     if (!ref_info.origin_set || !new_info.origin_set) return merge_refused("a map without an origin needs global_alignment, which is not built");
+    // map_loader.cpp:104-112: origins that differ (any of latitude, longitude, altitude by more than 1e-6) put the new map under the loaded map's
+    // origin first -- behind set_gnss; without the switch such a pair is refused as it always was
     for (int i = 0; i < 3; i++)
-        if (std::fabs(ref_info.origin[i] - new_info.origin[i]) > 1e-6) return merge_refused("the origins differ: graph_update_origin is not built");
+        if (std::fabs(ref_info.origin[i] - new_info.origin[i]) > 1e-6) in.reanchor = true;
+    if (in.reanchor && !s->gnss) return merge_refused("the origins differ: set_gnss(True) puts the new map under the loaded map's origin");
+    if (in.reanchor) {
+        in.from.latitude = new_info.origin[0]; in.from.longitude = new_info.origin[1]; in.from.altitude = new_info.origin[2];
+        in.to.latitude = ref_info.origin[0]; in.to.longitude = ref_info.origin[1]; in.to.altitude = ref_info.origin[2];
+    }
     auto vertex_ids = [](const G2oFile& gf) { std::set<int> v; for (const auto& x : gf.vertices) v.insert(x.id); return v; };
     const std::set<int> new_vertices = vertex_ids(in.new_g2o);
     for (const KeyFrameDisk& kf : in.fresh)
@@ -2439,6 +2635,7 @@ py::dict merge_map(const std::string& directory) {
     // the work: on copies of the graph's record and of the report; what it changes in place (the poses of the list, the bank) is undone if it fails
     std::vector<Loc::MergeEdge> edges = L.medges;
     std::set<int> fixed = L.mfixed;
+    std::vector<Loc::MergePrior> priors = L.mpriors;
     Loc::MergeReport report;
     std::vector<Mat4> saved;
     for (const KeyFrameDisk& kf : L.frames) saved.push_back(kf.odom);
@@ -2447,9 +2644,10 @@ py::dict merge_map(const std::string& directory) {
     {
         py::gil_scoped_release release;
         try {
-            merge_locked(s, in, edges, fixed, report);
+            merge_locked(s, in, edges, priors, fixed, report);
             // commit: the record, the key frames (map_loader.cpp:140), their map-frame clouds, the resident map
             L.medges.swap(edges);
+            L.mpriors.swap(priors);
             L.mfixed.swap(fixed);
             L.have_mgraph = true;
             L.merge_report = report;
@@ -2483,6 +2681,8 @@ py::dict _last_merge() {
     d["reasons"] = reasons;
     d["fragments"] = r.fragments;
     d["skipped_tags"] = r.skipped_tags;
+    d["origin_updated"] = r.origin_updated;
+    d["priors"] = r.priors;
     return d;
 }
 // get_graph_map (slam_wrapper.cpp:180-184 -> keyframe_to_pydict, py_utils.cpp:272-293): the key frames of the loaded map in localisation mode
@@ -3563,6 +3763,16 @@ py::list dump_graph(const std::string& directory) {
                     gf.edges.push_back(e);
                     if (me.kernel != LIO_GRAPH_KERNEL_NONE) gf.kernels.push_back({{me.a, me.b}, kernel_name(me.kernel), 1.0});
                 }
+                for (const Loc::MergePrior& mp : L.mpriors) {  // (none unless the merge ran under set_gnss)
+                    G2oFile::Prior p;
+                    p.node = mp.kf;
+                    if (mp.type == LIO_GRAPH_PRIOR_XYZ) { p.tag = "EDGE_SE3_PRIORXYZ"; p.values = {mp.m[0], mp.m[1], mp.m[2]}; }
+                    else { p.tag = "EDGE_SE3_PRIORQUAT"; p.values = {mp.m[3], mp.m[0], mp.m[1], mp.m[2]}; }
+                    for (int r = 0; r < 3; r++)
+                        for (int c = r; c < 3; c++) p.values.push_back(mp.info[r * 3 + c]);
+                    gf.priors.push_back(p);
+                    if (mp.kernel != LIO_GRAPH_KERNEL_NONE) gf.kernels.push_back({{mp.kf}, kernel_name(mp.kernel), mp.delta});
+                }
             }
         } else {
             std::lock_guard<std::mutex> kl(g->kf_mtx);
@@ -3913,7 +4123,11 @@ PYBIND11_MODULE(slam_wrapper, m) {
     m.def("_last_estimate_pose", &_last_estimate_pose);
     m.def("set_pose_graph", &set_pose_graph, "the pose graph over the key frames and the loops", py::arg("enable"));
     m.def("_push_keyframe", &_push_keyframe, "test hook: a key frame for the next update_odom()", py::arg("points"), py::arg("pose"), py::arg("stamp"), py::arg("accum_distance"));
-    m.def("set_gnss", &set_gnss, "the GNSS side of FastLIO mapping: origin from the first valid fix, GNSS priors in the pose graph", py::arg("enable"));
+    m.def("set_gnss", &set_gnss, "the GNSS side (off by default).  FastLIO mapping: origin from the first valid fix, GNSS priors in the pose graph.  Localisation mode: an INS-aided "
+          "initial pose (local Scan Context search), fixes fused by the pose filter, state Localizing(L+G) and a global-search threshold of 0.25, all "
+          "four only with RTK among the sensors; merge_map takes a map recorded under another origin (re-anchored to the loaded map's) and carries "
+          "both maps' GNSS priors",
+          py::arg("enable"));
     m.def("_push_gnss", &_push_gnss, "test hook: what process() does with a fix", py::arg("rtk_dict"));
     m.def("_last_merged", &_last_merged, "test hook: points and stamps of the last RTKM frame");
     m.def("_gnss_state", &_gnss_state, "test hook: the state of the GNSS side");

@@ -65,6 +65,7 @@ SYMBOLS = [
     "lio_overlap_last_report", "lio_overlap_last_times",
     "lio_sc_create", "lio_sc_destroy", "lio_sc_reset", "lio_sc_num_frames", "lio_sc_add_frames_host", "lio_sc_download_frame", "lio_sc_describe_host", "lio_sc_set_active",
     "lio_sc_distance", "lio_sc_search", "lio_sc_global_search_host", "lio_sc_shift_to_yaw", "lio_sc_last_dropped", "lio_sc_last_times",
+    "lio_sc_set_positions", "lio_sc_local_search", "lio_sc_last_local", "lio_update_origin",
     "lio_graph_default_params", "lio_graph_create", "lio_graph_destroy", "lio_graph_reset", "lio_graph_add_node", "lio_graph_set_fixed", "lio_graph_set_estimate",
     "lio_graph_num_nodes", "lio_graph_get_fixed", "lio_graph_add_edge", "lio_graph_remove_edge", "lio_graph_optimize", "lio_graph_estimates", "lio_graph_edges",
     "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
@@ -81,7 +82,8 @@ SYMBOLS = [
     "lio_scan_merge_create", "lio_scan_merge_destroy", "lio_scan_merge_set_transform", "lio_scan_merge_run_host", "lio_scan_merge_download",
     "lio_scan_merge_device", "lio_scan_merge_last_times",
 ]
-ABI_VERSION = 22  # the revision of include/lio_hip.h this binding was written against
+ABI_VERSION = 22  # kept at 22 for callers that compare against it; the revision the binding needs is ABI_REQUIRED
+ABI_REQUIRED = 23  # the oldest library revision that has every symbol above; lib() refuses an older one
 RTK_INTERPOLATED, RTK_EXACT, RTK_NO_ORIGIN, RTK_TOO_FEW, RTK_EARLY, RTK_LATE = 0, 1, 2, 3, 4, 5  # lio_rtk_track_interpolate
 
 
@@ -282,6 +284,8 @@ def lib():
     sig("lio_last_warning", C.c_char_p)
     sig("lio_device_count", cint)
     sig("lio_abi_version", cint)
+    if L.lio_abi_version() < ABI_REQUIRED:
+        raise RuntimeError(f"{LIB_PATH} is at ABI revision {L.lio_abi_version()}, this binding needs {ABI_REQUIRED}: build it again")
     sig("lio_pinned_alloc", vp, u64)
     sig("lio_pinned_free", None, vp)
     sig("lio_map_bytes", u64, vp)
@@ -624,6 +628,10 @@ def lib():
     sig("lio_gnss_queue_size", cint, vp)
     sig("lio_gnss_queue_stamps", cint, vp, u64p, u32)
     sig("lio_gnss_queue_flush", cint, vp, u64p, u8p, u32, f64p, C.POINTER(GnssMatch), u32)
+    sig("lio_update_origin", cint, fixp, fixp, f64p, u32, f64p, u32)
+    sig("lio_sc_set_positions", cint, vp, f32p, u32)
+    sig("lio_sc_local_search", cint, vp, f32p, u32, f64p, dbl, i32p, f32p, f64p, i32p)
+    sig("lio_sc_last_local", cint, vp, i32p, f32p, f64p, i32p, i32p)
     sig("lio_scan_merge_create", vp, cint, u32, u64)
     sig("lio_scan_merge_destroy", None, vp)
     sig("lio_scan_merge_set_transform", cint, vp, f64p)

@@ -771,6 +771,23 @@ class ScanContext:
         check(lib().lio_sc_global_search_host(self.h, ptr(p, C.c_float), len(p), float(dist_thres), C.byref(mid), C.byref(yaw), C.byref(sc), C.byref(sh)), "sc global_search")
         return dict(match_id=mid.value, yaw=np.float32(yaw.value), score=sc.value, shift=sh.value)
 
+    def set_positions(self, xyz):
+        """the key frames' positions ((F, 3), rounded to f32), row k = bank id k: what local_search measures the INS position against"""
+        p = f32(xyz).reshape(-1, 3)
+        check(lib().lio_sc_set_positions(self.h, ptr(p, C.c_float), len(p)), "sc set_positions")
+
+    def local_search(self, cloud, ins_xyz, precision):
+        """localSearch, the INS-aided start -> dict(match_id (-1: none), yaw (f32), score, shift, n_examined, ids, d2, dist, shifts): the last
+        four are the min(10, F) frames nearest to (x, y, 0) in rising (d2, id) with the Scan Context distance and shift of each"""
+        p, q = f32(cloud).reshape(-1, 4), f64(ins_xyz).reshape(3)
+        mid, yaw, sc, ne, ms = C.c_int32(0), C.c_float(0), C.c_double(0), C.c_int32(0), C.c_int32(0)
+        check(lib().lio_sc_local_search(self.h, ptr(p, C.c_float), len(p), ptr(q, C.c_double), float(precision), C.byref(mid), C.byref(yaw), C.byref(sc), C.byref(ne)),
+              "sc local_search")
+        ids, d2, dist, sh = np.zeros(10, np.int32), np.zeros(10, np.float32), np.zeros(10), np.zeros(10, np.int32)
+        n = check(lib().lio_sc_last_local(self.h, ptr(ids, C.c_int32), ptr(d2, C.c_float), ptr(dist, C.c_double), ptr(sh, C.c_int32), C.byref(ms)), "sc last_local")
+        return dict(match_id=mid.value, yaw=np.float32(yaw.value), score=sc.value, shift=ms.value, n_examined=ne.value, ids=ids[:n], d2=d2[:n], dist=dist[:n],
+                    shifts=sh[:n])
+
     @staticmethod
     def shift_to_yaw(shift):
         return np.float32(lib().lio_sc_shift_to_yaw(int(shift)))
@@ -2515,6 +2532,16 @@ def interpolate_transform(pre, nxt, ratio):
     a, b, T = f64(pre).reshape(4, 4), f64(nxt).reshape(4, 4), np.zeros((4, 4))
     lib().lio_interpolate_transform(ptr(a, C.c_double), ptr(b, C.c_double), float(ratio), ptr(T, C.c_double))
     return T
+
+
+def update_origin(origin_from, origin_to, poses=None, xyz=None):
+    """graph_update_origin's coordinate change: poses ((n, 4, 4)) and points ((m, 3)) of a map recorded under origin_from, expressed under
+    origin_to -> (poses, xyz), f64 copies; rotations are not touched.  An origin is a fix, or (latitude, longitude, altitude)"""
+    a, b = [o if isinstance(o, (capi.RtkFix, dict)) else dict(latitude=o[0], longitude=o[1], altitude=o[2]) for o in (origin_from, origin_to)]
+    P = np.array(poses if poses is not None else np.zeros((0, 4, 4)), np.float64).reshape(-1, 4, 4)
+    X = np.array(xyz if xyz is not None else np.zeros((0, 3)), np.float64).reshape(-1, 3)
+    check(lib().lio_update_origin(C.byref(_fix(a)), C.byref(_fix(b)), ptr(P, C.c_double), len(P), ptr(X, C.c_double), len(X)), "update_origin")
+    return P, X
 
 
 class Utm:
