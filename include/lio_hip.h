@@ -88,8 +88,10 @@ int lio_device_count(void);
  *      lio_rtk_track_* / lio_gnss_queue_* (the GNSS side of mapping mode on the host: UTM projection, the RTK track of RTKM, the graph's GNSS
  *      queue) and lio_scan_merge_* (several lidars into one frame on the device: mergePoints + preprocessPoints).
  * 23 = lio_sc_set_positions / lio_sc_local_search (the INS-aided start of the relocalisation: GlobalLocalization::localSearch over the key
- *      frames' positions resident beside the descriptors) and lio_update_origin (a map's poses and GNSS priors under another origin). */
-#define LIO_ABI_VERSION 23
+ *      frames' positions resident beside the descriptors) and lio_update_origin (a map's poses and GNSS priors under another origin).
+ * 24 = lio_calib_* / lio_se3f_* / lio_dfo_* (the lidar-INS calibration: Scan's subsampling, the f32 Transform, the odometry interpolation and
+ *      two derivative-free minimisers on the host; the capped k-NN cost of all key scans and Aligner::lidarOdomTransform on the device). */
+#define LIO_ABI_VERSION 24
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1853,6 +1855,116 @@ int64_t lio_scan_merge_download(lio_scan_merge*, float* xyzi, uint32_t* stamps, 
 const void* lio_scan_merge_device(lio_scan_merge*, const uint32_t** d_stamps, uint64_t* n);
 /* device time (HIP events) of the last run: the uploads, count + scan + write + the count's read-back */
 int lio_scan_merge_last_times(lio_scan_merge*, double* upload_us, double* merge_us);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Lidar-INS calibration (csrc/calib_host.cpp, csrc/calib.hip; ABI 24): the reference's calib_ins_* chain -- the pybind module
+ * sensor_driver/calibration/calib_wrapper.cpp:41-115 over lidar_ins/src/aligner.cpp and lidar_ins/src/sensor.cpp.
+ *   cost      every key scan moved into the odometry frame by M_s = matrix(T_o0_ot_s * T_o_l) (f32; x' = ((m00 x + m01 y) + m02 z) + m03,
+ *             separately rounded: the project's statement of pcl::transformPoint, which cannot be pinned without PCL), one exact k-NN index
+ *             over the combined cloud, every point's K = k + 1 nearest in it (the point itself included, aligner.cpp:47-51), and
+ *             sum over points and neighbours of min(d2, cap) with the cap compared with the SQUARED distance (aligner.cpp:25-28).
+ *             metric 0 = global: k = 3, cap 10.0; metric 1 = local: k = 1, cap 1.0 (aligner.h:19-23).
+ *   sum       DEVIATION: the reference adds the terms in f32 per batch of 1000 points and then over batches (aligner.cpp:22-72); this library
+ *             returns the f64 sum in a fixed order (per point ascending, then a fixed tree), bit-identical from run to run.
+ *   optimiser DEVIATION: nlopt's GN_DIRECT_L and LN_BOBYQA are replaced by lio_dfo_direct_l and lio_dfo_nelder_mead (below), restated from
+ *             the published algorithms; the calling protocol of Aligner::lidarOdomTransform (aligner.cpp:82-190) is kept.
+ *   a 7-float transform is tx, ty, tz, qw, qx, qy, qz; a 16-float one a row-major 4 x 4.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* Scan::Scan (sensor.cpp:48-65): keep[i] = 1 iff the i-th draw of std::uniform_real_distribution<float>(0, 1) over
+ * std::default_random_engine(stamp_us) is < min(1, 6000 / (n + 1)); the number kept */
+int lio_calib_subsample(uint64_t n, int64_t stamp_us, uint8_t* keep);
+/* Transform (transform.h:23-65) in f32 */
+void lio_se3f_exp(const float v[6], float T[7]);
+void lio_se3f_log(const float T[7], float v[6]);
+void lio_se3f_mul(const float a[7], const float b[7], float out[7]);
+void lio_se3f_inverse(const float a[7], float out[7]);
+void lio_se3f_matrix(const float T[7], float M[16]);
+void lio_se3f_from_matrix(const float M[16], float T[7]);
+/* Odom::getOdomTransform (sensor.cpp:14-44) over m entries (stamps in us, T m x 7): the search runs forward from start_idx only, the ratio is
+ * not clamped.  LIO_E_STATE for m < 2 (the reference reads past its vector) */
+int lio_calib_interpolate(const int64_t* stamps, const float* T, uint32_t m, int64_t stamp, uint32_t start_idx, float T_out[7], uint32_t* match_idx);
+
+/* derivative-free minimisers over a box (1 <= n <= LIO_DFO_MAX_DIM).  The hook runs after every evaluation; a non-zero return stops the
+ * method.  Neither evaluates outside [lb, ub] or more than max_evals times.  x_best / report: the best point evaluated. */
+#define LIO_DFO_MAX_DIM 8
+#define LIO_DFO_STOP_EVALS 0
+#define LIO_DFO_STOP_XTOL 1
+#define LIO_DFO_STOP_HOOK 2
+typedef double (*lio_dfo_fn)(const double* x, int n, void* user);
+typedef int (*lio_dfo_hook)(int evals, const double* x, int n, double f, void* user);
+typedef struct lio_dfo_params {
+    int32_t max_evals; /* 500 */
+    int32_t reserved;
+    double xtol_abs;   /* 1e-4: DIRECT-L stops dividing a rectangle whose sides are all at most this, Nelder-Mead stops at such a simplex */
+    double epsilon;    /* 1e-4: DIRECT-L's epsilon */
+    double step[LIO_DFO_MAX_DIM]; /* Nelder-Mead: the initial simplex is x0 and x0 + step[i] e_i (- when + leaves the box); 0 = side / 20 */
+} lio_dfo_params;
+typedef struct lio_dfo_report {
+    int32_t evals;
+    int32_t stop;
+    double f_best;
+} lio_dfo_report;
+void lio_dfo_default_params(lio_dfo_params*);
+/* DIRECT (Jones, Perttunen & Stuckman 1993) with Gablonsky & Kelley's locally biased selection: first evaluation at the centre, no start point */
+int lio_dfo_direct_l(lio_dfo_fn f, void* user, int n, const double* lb, const double* ub, const lio_dfo_params* p, lio_dfo_hook hook, void* hook_user,
+                     double* x_best, lio_dfo_report* report);
+/* Nelder-Mead (1965), coefficients 1, 2, 1/2, 1/2, every point projected onto the box */
+int lio_dfo_nelder_mead(lio_dfo_fn f, void* user, int n, const double* x0, const double* lb, const double* ub, const lio_dfo_params* p,
+                        lio_dfo_hook hook, void* hook_user, double* x_best, lio_dfo_report* report);
+
+#define LIO_CALIB_MAX_SCANS 64
+#define LIO_CALIB_GLOBAL 0
+#define LIO_CALIB_LOCAL 1
+#define LIO_CALIB_UNCAPPED 2 /* added to the metric: the walk starts from +inf instead of the cap (same terms; measurement only) */
+typedef struct lio_calib_params { /* Aligner::Config (aligner.h:12-25) and the optimisers' own fields */
+    int32_t local_only;       /* Config::local: skip the global stage */
+    int32_t time_cal;         /* 1 */
+    double max_time_offset;   /* 0.2 s */
+    int32_t max_evals;        /* 500 per stage */
+    int32_t knn_batch_size;   /* 1000: carried; the f64 sum has no batches */
+    double xtol;              /* 1e-4 */
+    int32_t local_knn_k;      /* 1 */
+    int32_t global_knn_k;     /* 3 */
+    float local_knn_max_dist; /* 1.0, compared with the squared distance */
+    float global_knn_max_dist; /* 10.0 */
+    double direct_epsilon;    /* 1e-4 */
+    double nm_step[7];        /* Nelder-Mead's initial steps of the local stage: x, y, z (m), rotation vector (rad), time offset (s) */
+} lio_calib_params;
+typedef struct lio_calib_ins lio_calib_ins;
+void lio_calib_default_params(lio_calib_params*);
+/* NULL without a usable device */
+lio_calib_ins* lio_calib_ins_create(int device);
+void lio_calib_ins_destroy(lio_calib_ins*);
+/* calib_ins_reset (calib_wrapper.cpp:41-54): no scans, no odometry, current = best = Transform(init) */
+int lio_calib_ins_reset(lio_calib_ins*, const float init[16]);
+/* Lidar::addPointcloud + Scan::Scan (sensor.cpp:102-114, 48-65): n points, `stride` floats apart (>= 3); every point is drawn for, a kept
+ * point with a non-finite coordinate is dropped (the reference would trip FLANN's assertion); the points kept.  An empty scan is a scan.
+ * LIO_E_CAPACITY beyond LIO_CALIB_MAX_SCANS (the limit of 20 is the wrapper's, calib_wrapper.cpp:61-65) */
+int lio_calib_ins_add_scan(lio_calib_ins*, const float* xyz, uint64_t n, uint32_t stride, int64_t stamp_us);
+/* Odom::addTransformData (sensor.cpp:10-12) */
+int lio_calib_ins_add_odom(lio_calib_ins*, const float T[16], int64_t stamp_us);
+int lio_calib_ins_counts(lio_calib_ins*, uint32_t* n_scans, uint32_t* n_odoms, uint64_t* n_points);
+/* Lidar::setOdomLidarTransform(exp(x)) (aligner.cpp:97) */
+int lio_calib_ins_set_transform(lio_calib_ins*, const double x[6]);
+/* Lidar::setOdomOdomTransforms (sensor.cpp:122-127) at time_offset, then the S x 16 f32 matrices an evaluation at the current transform uses.
+ * LIO_E_STATE with fewer than two odometry entries; LIO_E_INVALID when a pose is not finite (two entries with one stamp) */
+int lio_calib_ins_scan_matrices(lio_calib_ins*, double time_offset, float* out);
+/* Lidar::getCombinedPointcloud (sensor.cpp:116-120) at exp(x[0..6)), with nx == 7 at the time offset x[6] (nx == 6: the scan poses as they
+ * were last set): n x 3 f32 in scan-major input order; the number of points */
+int64_t lio_calib_ins_combined(lio_calib_ins*, const double* x, int nx, float* xyz_out, uint64_t cap);
+/* Aligner::lidarOdomKNNError (aligner.cpp:33-80) as LidarOdomMinimizer calls it (:82-98), without the best-transform bookkeeping.
+ * LIO_E_STATE with fewer than K points */
+int lio_calib_ins_error(lio_calib_ins*, const double* x, int nx, int metric, double* err);
+/* the n x K terms min(d2, cap) of that evaluation in combined-cloud index order, each row ascending: the test door */
+int64_t lio_calib_ins_error_terms(lio_calib_ins*, const double* x, int nx, int metric, float* terms, uint64_t cap);
+/* Aligner::lidarOdomTransform (aligner.cpp:137-190); blocks until done.  params NULL = the defaults */
+int lio_calib_ins_calibrate(lio_calib_ins*, const lio_calib_params* params);
+/* Aligner::getOptimizationStatus's inputs (aligner.cpp:192-199); may be called from another thread while _calibrate runs */
+int lio_calib_ins_progress(lio_calib_ins*, int32_t* evals, double* best_err, int32_t* finished);
+/* Lidar::getBestOdomLidarTransform().matrix() */
+int lio_calib_ins_result(lio_calib_ins*, float T[16]);
+/* device time (HIP events) of the last evaluation */
+int lio_calib_ins_last_times(lio_calib_ins*, double* assemble_us, double* build_us, double* terms_us);
 
 #ifdef __cplusplus
 }

@@ -81,6 +81,11 @@ SYMBOLS = [
     "lio_gnss_queue_flush",
     "lio_scan_merge_create", "lio_scan_merge_destroy", "lio_scan_merge_set_transform", "lio_scan_merge_run_host", "lio_scan_merge_download",
     "lio_scan_merge_device", "lio_scan_merge_last_times",
+    "lio_calib_subsample", "lio_se3f_exp", "lio_se3f_log", "lio_se3f_mul", "lio_se3f_inverse", "lio_se3f_matrix", "lio_se3f_from_matrix",
+    "lio_calib_interpolate", "lio_dfo_default_params", "lio_dfo_direct_l", "lio_dfo_nelder_mead", "lio_calib_default_params",
+    "lio_calib_ins_create", "lio_calib_ins_destroy", "lio_calib_ins_reset", "lio_calib_ins_add_scan", "lio_calib_ins_add_odom", "lio_calib_ins_counts",
+    "lio_calib_ins_set_transform", "lio_calib_ins_scan_matrices", "lio_calib_ins_combined", "lio_calib_ins_error", "lio_calib_ins_error_terms",
+    "lio_calib_ins_calibrate", "lio_calib_ins_progress", "lio_calib_ins_result", "lio_calib_ins_last_times",
 ]
 ABI_VERSION = 22  # kept at 22 for callers that compare against it; the revision the binding needs is ABI_REQUIRED
 ABI_REQUIRED = 23  # the oldest library revision that has every symbol above; lib() refuses an older one
@@ -258,6 +263,27 @@ class KernelTimes(C.Structure):
                 ("linearize_launches", C.c_uint32), ("finalize_launches", C.c_uint32), ("pad", C.c_uint32)]
 
 
+DFO_MAX_DIM = 8  # LIO_DFO_MAX_DIM
+DFO_STOP_EVALS, DFO_STOP_XTOL, DFO_STOP_HOOK = 0, 1, 2
+CALIB_MAX_SCANS, CALIB_GLOBAL, CALIB_LOCAL, CALIB_UNCAPPED = 64, 0, 1, 2
+
+
+class DfoParams(C.Structure):  # lio_dfo_params
+    _fields_ = [("max_evals", C.c_int32), ("reserved", C.c_int32), ("xtol_abs", C.c_double), ("epsilon", C.c_double), ("step", C.c_double * DFO_MAX_DIM)]
+
+
+class DfoReport(C.Structure):  # lio_dfo_report
+    _fields_ = [("evals", C.c_int32), ("stop", C.c_int32), ("f_best", C.c_double)]
+
+
+class CalibParams(C.Structure):  # lio_calib_params
+    _fields_ = [("local_only", C.c_int32), ("time_cal", C.c_int32), ("max_time_offset", C.c_double), ("max_evals", C.c_int32),
+                ("knn_batch_size", C.c_int32), ("xtol", C.c_double), ("local_knn_k", C.c_int32), ("global_knn_k", C.c_int32),
+                ("local_knn_max_dist", C.c_float), ("global_knn_max_dist", C.c_float), ("direct_epsilon", C.c_double), ("nm_step", C.c_double * 7)]
+
+
+DFO_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_int, C.c_void_p)  # lio_dfo_fn
+DFO_HOOK = C.CFUNCTYPE(C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_void_p)  # lio_dfo_hook
 REDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p)  # lio_gather_fn: (ctx, d_local, d_gathered, n_records, stream)
 
@@ -642,6 +668,35 @@ def lib():
     sig("lio_scan_merge_last_times", cint, vp, f64p, f64p)
     sig("lio_state_boxplus", None, f64p, f64p, f64p)
     sig("lio_state_boxminus", None, f64p, f64p, f64p)
+    i64, i64p = C.c_int64, C.POINTER(C.c_int64)
+    dpp, drp, cpp = C.POINTER(DfoParams), C.POINTER(DfoReport), C.POINTER(CalibParams)
+    sig("lio_calib_subsample", cint, u64, i64, u8p)
+    sig("lio_se3f_exp", None, f32p, f32p)
+    sig("lio_se3f_log", None, f32p, f32p)
+    sig("lio_se3f_mul", None, f32p, f32p, f32p)
+    sig("lio_se3f_inverse", None, f32p, f32p)
+    sig("lio_se3f_matrix", None, f32p, f32p)
+    sig("lio_se3f_from_matrix", None, f32p, f32p)
+    sig("lio_calib_interpolate", cint, i64p, f32p, u32, i64, u32, f32p, u32p)
+    sig("lio_dfo_default_params", None, dpp)
+    sig("lio_dfo_direct_l", cint, DFO_FN, vp, cint, f64p, f64p, dpp, DFO_HOOK, vp, f64p, drp)
+    sig("lio_dfo_nelder_mead", cint, DFO_FN, vp, cint, f64p, f64p, f64p, dpp, DFO_HOOK, vp, f64p, drp)
+    sig("lio_calib_default_params", None, cpp)
+    sig("lio_calib_ins_create", vp, cint)
+    sig("lio_calib_ins_destroy", None, vp)
+    sig("lio_calib_ins_reset", cint, vp, f32p)
+    sig("lio_calib_ins_add_scan", cint, vp, f32p, u64, u32, i64)
+    sig("lio_calib_ins_add_odom", cint, vp, f32p, i64)
+    sig("lio_calib_ins_counts", cint, vp, u32p, u32p, u64p)
+    sig("lio_calib_ins_set_transform", cint, vp, f64p)
+    sig("lio_calib_ins_scan_matrices", cint, vp, dbl, f32p)
+    sig("lio_calib_ins_combined", i64, vp, f64p, cint, f32p, u64)
+    sig("lio_calib_ins_error", cint, vp, f64p, cint, cint, f64p)
+    sig("lio_calib_ins_error_terms", i64, vp, f64p, cint, cint, f32p, u64)
+    sig("lio_calib_ins_calibrate", cint, vp, cpp)
+    sig("lio_calib_ins_progress", cint, vp, i32p, f64p, i32p)
+    sig("lio_calib_ins_result", cint, vp, f32p)
+    sig("lio_calib_ins_last_times", cint, vp, f64p, f64p, f64p)
     _lib = L
     return L
 

@@ -2726,3 +2726,100 @@ class ScanMerge:
         a, b = C.c_double(0), C.c_double(0)
         check(lib().lio_scan_merge_last_times(self.h, C.byref(a), C.byref(b)), "scan merge times")
         return a.value, b.value
+
+
+class InsCalib:
+    """lio_calib_ins: the lidar-INS calibration (the reference's calib_ins_* chain): key scans and an odometry track in, the lidar-to-INS
+    transform out.  x is the 6-vector (translation, rotation vector) of a candidate, with the time offset (s) as an optional seventh entry;
+    metric 0 = global (k = 3, cap 10), 1 = local (k = 1, cap 1)."""
+
+    GLOBAL, LOCAL, UNCAPPED = capi.CALIB_GLOBAL, capi.CALIB_LOCAL, capi.CALIB_UNCAPPED
+
+    def __init__(self, init=None, device=0):
+        self.h = lib().lio_calib_ins_create(device)
+        if not self.h:
+            raise capi.LioError("lio_calib_ins_create failed: " + lib().lio_last_error().decode())
+        self.reset(np.eye(4) if init is None else init)
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_calib_ins_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def default_params():
+        p = capi.CalibParams()
+        lib().lio_calib_default_params(C.byref(p))
+        return p
+
+    def reset(self, init):
+        M = f32(init).reshape(4, 4)
+        check(lib().lio_calib_ins_reset(self.h, ptr(M, C.c_float)), "calib reset")
+
+    def add_scan(self, points, stamp_us):
+        """points N x (>= 3) f32; the number of points kept (about 6000 of a large scan)"""
+        p = f32(points)
+        p = p.reshape(-1, p.shape[-1] if p.ndim == 2 else 3)
+        return check(lib().lio_calib_ins_add_scan(self.h, ptr(p, C.c_float), len(p), p.shape[1], int(stamp_us)), "calib add_scan")
+
+    def add_odom(self, T, stamp_us):
+        M = f32(T).reshape(4, 4)
+        check(lib().lio_calib_ins_add_odom(self.h, ptr(M, C.c_float), int(stamp_us)), "calib add_odom")
+
+    def counts(self):
+        """(scans, odometry entries, points held)"""
+        s, o, n = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        check(lib().lio_calib_ins_counts(self.h, C.byref(s), C.byref(o), C.byref(n)), "calib counts")
+        return s.value, o.value, int(n.value)
+
+    def set_transform(self, x):
+        check(lib().lio_calib_ins_set_transform(self.h, ptr(f64(x).reshape(6), C.c_double)), "calib set_transform")
+
+    def scan_matrices(self, time_offset=0.0):
+        """sets the scan poses at the offset; the S x 4 x 4 f32 matrices an evaluation at the current transform uses"""
+        out = np.zeros((max(self.counts()[0], 1), 4, 4), np.float32)
+        check(lib().lio_calib_ins_scan_matrices(self.h, float(time_offset), ptr(out, C.c_float)), "calib scan_matrices")
+        return out[: self.counts()[0]]
+
+    def combined(self, x):
+        x = f64(x).reshape(-1)
+        n = self.counts()[2]
+        out = np.zeros((max(n, 1), 3), np.float32)
+        m = check(int(lib().lio_calib_ins_combined(self.h, ptr(x, C.c_double), len(x), ptr(out, C.c_float), n)), "calib combined")
+        return out[:m]
+
+    def error(self, x, metric):
+        x, e = f64(x).reshape(-1), C.c_double(0)
+        check(lib().lio_calib_ins_error(self.h, ptr(x, C.c_double), len(x), int(metric), C.byref(e)), "calib error")
+        return e.value
+
+    def error_terms(self, x, metric):
+        """n x K f32: min(d2, cap) of every point's K nearest in the combined cloud, rows in combined-cloud order, ascending"""
+        x = f64(x).reshape(-1)
+        n, K = self.counts()[2], 2 if (int(metric) & 1) else 4
+        out = np.zeros((max(n, 1), K), np.float32)
+        m = check(int(lib().lio_calib_ins_error_terms(self.h, ptr(x, C.c_double), len(x), int(metric), ptr(out, C.c_float), n)), "calib error_terms")
+        return out[:m]
+
+    def calibrate(self, params=None):
+        check(lib().lio_calib_ins_calibrate(self.h, C.byref(params) if params is not None else None), "calib calibrate")
+        return self.result()
+
+    def progress(self):
+        """(evaluations so far, smallest cost so far, finished)"""
+        n, e, f = C.c_int32(0), C.c_double(0), C.c_int32(0)
+        check(lib().lio_calib_ins_progress(self.h, C.byref(n), C.byref(e), C.byref(f)), "calib progress")
+        return n.value, e.value, bool(f.value)
+
+    def result(self):
+        M = np.zeros((4, 4), np.float32)
+        check(lib().lio_calib_ins_result(self.h, ptr(M, C.c_float)), "calib result")
+        return M
+
+    def last_times(self):
+        """(assemble_us, build_us, terms_us): device time of the last evaluation"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        check(lib().lio_calib_ins_last_times(self.h, C.byref(a), C.byref(b), C.byref(c)), "calib times")
+        return a.value, b.value, c.value
