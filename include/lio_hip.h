@@ -90,8 +90,10 @@ int lio_device_count(void);
  * 23 = lio_sc_set_positions / lio_sc_local_search (the INS-aided start of the relocalisation: GlobalLocalization::localSearch over the key
  *      frames' positions resident beside the descriptors) and lio_update_origin (a map's poses and GNSS priors under another origin).
  * 24 = lio_calib_* / lio_se3f_* / lio_dfo_* (the lidar-INS calibration: Scan's subsampling, the f32 Transform, the odometry interpolation and
- *      two derivative-free minimisers on the host; the capped k-NN cost of all key scans and Aligner::lidarOdomTransform on the device). */
-#define LIO_ABI_VERSION 24
+ *      two derivative-free minimisers on the host; the capped k-NN cost of all key scans and Aligner::lidarOdomTransform on the device).
+ * 25 = lio_graph_estimate_gnss_moment / lio_graph_moment_begin / _end / _get / _linearize (the GNSS moment stage of robust_graph_optimize's mode
+ *      `mapping`: one shared 3-DoF vertex, the offset between the antenna and the lidar frame, bordered onto the pose graph's system). */
+#define LIO_ABI_VERSION 25
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -1488,10 +1490,9 @@ int lio_sc_last_times(lio_sc*, double* describe_us, double* ringkey_us, double* 
  * The pose graph on the device (csrc/graph.hip): what hdl_graph_slam's GraphSLAM does with g2o for SE3 pose nodes and EdgeSE3 edges
  * (graph_slam.cpp:344-375, solver "lm_var").  g2o is not in the reference tree: THE RULES BELOW ARE RESTATED FROM g2o'S PUBLISHED SOURCE
  * (types/slam3d/isometry3d_mappings, edge_se3, core/robust_kernel_impl, core/optimization_algorithm_levenberg) and are pinned to an f64 numpy
- * restatement (tests/graph_cases.py, tests/graph_prior_cases.py), not to a compiled reference.  Out of scope: the reference's
- * EdgeSE3PriorVec (its only producer, imu_callback, returns at once: hdl_graph_slam_nodelet.cpp:462-463) and the "GNSS moment" stage of
- * robust_graph_optimize's mode `mapping` (:1039-1081), which needs a 3-DoF point vertex.  NULL from lio_graph_create without a device: there is
- * no CPU fallback.
+ * restatement (tests/graph_cases.py, tests/graph_prior_cases.py, tests/graph_moment_cases.py), not to a compiled reference.  Out of scope: the
+ * reference's EdgeSE3PriorVec (its only producer, imu_callback, returns at once: hdl_graph_slam_nodelet.cpp:462-463).  NULL from
+ * lio_graph_create without a device: there is no CPU fallback.
  *   state       a node is an f64 translation, a unit quaternion and a fixed flag; an edge is from, to, a measurement M (given as a row-major
  *               4 x 4, kept as translation + quaternion), an f64 6 x 6 information matrix, a kernel and its delta.  Ids count from 0 in creation
  *               order and are never reused; a removed edge takes no part.
@@ -1525,6 +1526,28 @@ int lio_sc_last_times(lio_sc*, double* describe_us, double* ringkey_us, double* 
  *   outliers    THE PROJECT'S NAME for the first stage of robust_graph_optimize (:1004-1038), lio_graph_remove_gnss_outliers: every live XYZ prior
  *               gets DCS2 with delta = max_err^2 Omega(0,0); optimise; every XYZ prior with 2 phi / (phi + chi2_e) < 0.1 (the unrobustified
  *               chi2_e) is removed; optimise again.  The priors that stay keep DCS2.
+ *   moment      THE PROJECT'S NAME for the second stage of robust_graph_optimize in mode `mapping` (:1037-1081), lio_graph_estimate_gnss_moment: the
+ *               constant offset m between the GNSS antenna and the lidar frame, one shared VertexPointXYZ (3 DoF, updated additively: m <- m + d_m).
+ *               While the stage is open every live XYZ prior is an EdgeSE3GNSS (edge_se3_gnss.hpp:39-45) on its node (t, R) and m:
+ *                 e = t - (z + R m);  d e / d d = [R | 2 R [m]x] (3 x 6, under X <- X fromVectorMQT(d));  d e / d m = -R
+ *               (ANALYTIC, THE PROJECT'S RULE: g2o differentiates this edge numerically).  SIGN: with fixes z = t + R l, l the antenna's place in
+ *               the lidar frame, the stage finds m = -l, not l; the moved measurements z' = z + R m = t are the lidar's own positions.  This is
+ *               the reference's convention and is not a mistake to be mended.  The stage, statement for statement: (1) m = 0 with an EdgeXYZPrior
+ *               at 0 of information diag(1/2000, 1/2000, 1/200), e_m = m, no kernel; (2) every live XYZ prior becomes a moment edge with the same
+ *               node, measurement and information and DCS2 with phi = max_err^2 Omega(0,0), max_err = 1.0; (3) optimize(1024); (4) every moment
+ *               edge becomes an XYZ prior again with z' = z + R_node m, the same information and DCS2; (5) the moment and its prior are removed.
+ *               THE PROJECT'S RULE: the reference deletes and re-creates the edges, so every GNSS prior gets a new id and the counter advances by
+ *               2 n; here a prior keeps its id and changes its measurement in place (ids stay stable for a caller that shows them, as for
+ *               lio_graph_remove_node, and no dead placeholder is left).  The moment vertex's id (1000000) is never visible.
+ *               The system with the moment present has 6 Na + 3 unknowns: per moment edge on an active node a 6 x 3 coupling block
+ *               J^T (rho' Omega) J_m, and J_m^T (rho' Omega) J_m and -J_m^T (rho' Omega) e into the border's 3 x 3 and b_m, to which the moment's
+ *               prior adds Omega_m and -Omega_m m.  A moment edge on a fixed node contributes to the 3 x 3, b_m and chi2 only.  LM: lambda_0 takes
+ *               the largest |diag H| over the border's three entries too, d^T (lambda d + b) covers them, a rejected trial restores m with the
+ *               poses, the moment's prior is one live edge for min_edges and its m^T Omega_m m is part of chi2 (added after the per-256 records).
+ *               The solve's preconditioner has the damped 3 x 3's inverse as one more block; with no active node the cap on its iterations is 3
+ *               (THE PROJECT'S RULE, as the solve is).
+ *               Sums: a node's coupling block, the 3 x 3 and b_m are summed in rising edge id; the border rows' sum over the nodes is folded
+ *               in the solve's fixed order.
  *   active set  a fixed node contributes no unknowns; a node with no live edge is left out of the solve and keeps its estimate.
  *   LM          OptimizationAlgorithmLevenberg: lambda_0 = 1e-5 max diag(H), nu = 2.  A trial solves (H + lambda I) d = b, applies the update and
  *               re-evaluates chi2; rho = (chi2_old - chi2_new) / (d^T (lambda d + b) + 1e-3).  Accepted (rho > 0, chi2_new finite): lambda *=
@@ -1613,6 +1636,23 @@ int lio_graph_priors(lio_graph*, int32_t* id, int32_t* node, int32_t* type, doub
 /* the GNSS outlier stage (the rules above, "outliers"): the number of priors removed, their ids into removed_ids (the first cap of them; may be
  * NULL); -1 with nothing touched when fewer than min_edges live edges exist.  report (may be NULL) is of the second optimisation */
 int lio_graph_remove_gnss_outliers(lio_graph*, double max_distance_error, int max_iterations, int32_t* removed_ids, uint32_t cap, lio_graph_report* report);
+/* the GNSS moment stage (the rules above, "moment"): the number of XYZ priors re-anchored, the moment into moment3 (may be NULL).  prior_info9 =
+ * the information of the moment's prior at 0 (NULL: the reference's diag(1/2000, 1/2000, 1/200)).  0 with nothing touched when no live XYZ prior
+ * exists; LIO_E_STATE with nothing touched when fewer than min_edges live edges exist (the moment's prior counted as one), or between
+ * lio_graph_moment_begin and _end.  report (may be NULL) is of the stage's optimisation */
+int lio_graph_estimate_gnss_moment(lio_graph*, double max_distance_error, int max_iterations, const double* prior_info9, double moment3[3], lio_graph_report* report);
+/* stage doors of the moment stage.  _begin opens it at the moment m0 (NULL: 0) with the prior information info9 (NULL: the reference's) and
+ * changes no kernel; until _end, lio_graph_optimize, lio_graph_chi2 and lio_graph_linearize run over the bordered system (every live XYZ prior a
+ * moment edge), and lio_graph_add_node / _add_edge / _add_prior / _remove_edge / _remove_node / _reset / _remove_gnss_outliers /
+ * _estimate_gnss_moment and a second _begin answer LIO_E_STATE.  _end with apply != 0 moves every live XYZ prior's measurement to z + R_node m
+ * and returns their number; with apply == 0 it drops the moment and leaves every prior as it was (0).  _get: the current moment.  _linearize: one
+ * linearisation as lio_graph_linearize, and from it b_m, the border's 3 x 3 (row-major) and per node id the 6 x 3 coupling block (row-major, 18
+ * per node; zeros for a node that is fixed or carries no moment edge; node_cap in nodes); the number of moment edges.  _get, _end and _linearize
+ * answer LIO_E_STATE when no stage is open */
+int lio_graph_moment_begin(lio_graph*, const double* m0, const double* info9);
+int lio_graph_moment_end(lio_graph*, int apply);
+int lio_graph_moment_get(lio_graph*, double m3[3]);
+int lio_graph_moment_linearize(lio_graph*, double bm3[3], double Hmm9[9], double* Hpm, uint32_t node_cap);
 /* the iterations run; -1 with nothing touched when fewer than min_edges live edges exist (GraphSLAM::optimize); other negative values are
  * LIO_E_* (a NULL handle is LIO_E_INVALID = -1 as well).  report may be NULL */
 int lio_graph_optimize(lio_graph*, int max_iterations, lio_graph_report* report);

@@ -15,6 +15,13 @@
 //              that id.  graph_linearize_prior (one lane per prior) writes e, chi2, rho', J^T W J and -J^T W e into the id's Hii / bi slots, so
 //              graph_assemble and the node -> edges lists take both kinds in rising id as they are; graph_chi2<true> follows the placeholder,
 //              so a prior's rho joins the partial of its 256 ids.  Without priors neither the extra launch nor graph_chi2<true> is used.
+//   moment     between lio_graph_moment_begin and _end every live XYZ prior is an EdgeSE3GNSS to one shared 3-DoF vertex m, a dense border of three
+//              unknowns on the system.  graph_linearize_moment (after graph_linearize_prior) takes those priors' slots again and leaves the 6 x 3
+//              coupling block, the 3 x 3 and the 3 of b per prior; graph_assemble_border sums them per active node and over all, in rising id,
+//              and adds the moment's own prior; graph_solve_border is graph_solve's text with the border compiled in (three more rows, the
+//              damped 3 x 3's inverse in the preconditioner, three more block sums per product); graph_update_moment, graph_chi2_moment and
+//              graph_decide_moment carry m through the trial.  With no stage open none of these is launched and the kernels above take the
+//              arguments they always took.
 // The host enqueues, per LM iteration, linearise + assemble + kMaxTrials trials; a kernel whose trial is not wanted (the iteration was decided, or
 // the optimisation stopped) leaves at once.  The host reads one LmState per iteration.
 #include <cfloat>
@@ -208,6 +215,32 @@ HD double prior_rho(const PriorDev& pr, const double* __restrict__ nt, const dou
     prior_eval(pr.type, t, q, m, pl, e, A, nl, u, &sgn);
     robustify(prior_chi2(e, pr.info, We), pr.kernel, pr.delta, &rho, &rho1);
     return rho;
+}
+// the moment stage's state on the device: the moment m, its backup, the information of its prior at 0
+constexpr int kMomM = 0, kMomBak = 3, kMomInfo = 6, kMomDoubles = 15;
+// what graph_linearize_moment leaves per prior (by its index, not its id): the 6 x 3 coupling block, the border's 3 x 3 and its 3 of b
+constexpr int kMlinHpm = 0, kMlinHmm = 18, kMlinBm = 27, kMlinDoubles = 30;
+// EdgeSE3GNSS: e = t - (z + R m) for the node (t, R), the measurement z and the moment m
+HD void moment_eval(const double t[3], const double R[9], const double z[3], const double m[3], double e[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) e[r] = t[r] - (z[r] + ((R[r * 3] * m[0] + R[r * 3 + 1] * m[1]) + R[r * 3 + 2] * m[2]));
+}
+// rho of a live XYZ prior taken as a moment edge
+HD double moment_rho(const PriorDev& pr, const double* __restrict__ nt, const double* __restrict__ nq, const double* __restrict__ mom) {
+    double t[3], q[4], z[3], m[3], R[9], e[3], We[3], rho, rho1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { t[k] = nt[pr.node * 3ull + k]; z[k] = pr.m[k]; m[k] = mom[kMomM + k]; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) q[k] = nq[pr.node * 4ull + k];
+    q_to_R(q, R);
+    moment_eval(t, R, z, m, e);
+    robustify(prior_chi2(e, pr.info, We), pr.kernel, pr.delta, &rho, &rho1);
+    return rho;
+}
+// m^T Omega m of the moment's own prior (EdgeXYZPrior at 0, no kernel)
+HD double moment_prior_chi2(const double m[3], const double* __restrict__ info) {
+    double We[3];
+    return prior_chi2(m, info, We);
 }
 // X <- X fromVectorMQT(d), the quaternion renormalised
 HD void apply_delta(double t[3], double q[4], const double d[6]) {
@@ -422,6 +455,103 @@ __global__ void __launch_bounds__(kEdgeThreads) graph_linearize_prior(const Prio
     }
 }
 
+// the moment stage (include/lio_hip.h, "moment"): one lane per prior (grid-stride), after graph_linearize_prior on the same stream.  A live XYZ
+// prior is an EdgeSE3GNSS on its node and the shared moment m: e = t - (z + R m), J = [R | 2 R [m]x], J_m = -R.  The node's 6 x 6 and b overwrite
+// what graph_linearize_prior left in the id's Hii / bi slots; the coupling block J^T (rho' Omega) J_m, J_m^T (rho' Omega) J_m and
+// -J_m^T (rho' Omega) e go to the prior's record in mlin.  Priors of the other types, and dead ones, are left as they are
+__global__ void __launch_bounds__(kEdgeThreads) graph_linearize_moment(const PriorDev* __restrict__ priors, uint32_t n, const double* __restrict__ nt,
+                                                                       const double* __restrict__ nq, const LmState* __restrict__ st, int tag, LinBuf L,
+                                                                       const double* __restrict__ mom, double* __restrict__ mlin) {
+    if (!wanted(st, tag)) return;
+    for (uint32_t k0 = blockIdx.x * kEdgeThreads + threadIdx.x; k0 < n; k0 += gridDim.x * kEdgeThreads) {
+        const PriorDev& pr = priors[k0];
+        if (!pr.live || pr.type != LIO_GRAPH_PRIOR_XYZ) continue;
+        const uint64_t id = (uint64_t)pr.id;
+        double t[3], q[4], z[3], m[3], e[3], We[3], Jt[9], Jr[9], Jm[9];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { t[k] = nt[pr.node * 3ull + k]; z[k] = pr.m[k]; m[k] = mom[kMomM + k]; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) q[k] = nq[pr.node * 4ull + k];
+        q_to_R(q, Jt);
+        moment_eval(t, Jt, z, m, e);
+        const double chi2 = prior_chi2(e, pr.info, We);
+        double rho, rho1;
+        robustify(chi2, pr.kernel, pr.delta, &rho, &rho1);
+#pragma unroll
+        for (int k = 0; k < 3; k++) { L.err[id * 6 + k] = e[k]; L.err[id * 6 + 3 + k] = 0.0; }
+        L.chi2[id] = chi2; L.rho1[id] = rho1;
+        const double X[9] = {0.0, -m[2], m[1], m[2], 0.0, -m[0], -m[1], m[0], 0.0};
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                Jr[r * 3 + c] = 2.0 * ((Jt[r * 3] * X[c] + Jt[r * 3 + 1] * X[3 + c]) + Jt[r * 3 + 2] * X[6 + c]);
+                Jm[r * 3 + c] = -Jt[r * 3 + c];
+            }
+        }
+        double* bo = L.bi + id * 6;
+        double* mo = mlin + k0 * (uint64_t)kMlinDoubles;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            bo[c] = -((Jt[c] * (rho1 * We[0]) + Jt[3 + c] * (rho1 * We[1])) + Jt[6 + c] * (rho1 * We[2]));
+            bo[3 + c] = -((Jr[c] * (rho1 * We[0]) + Jr[3 + c] * (rho1 * We[1])) + Jr[6 + c] * (rho1 * We[2]));
+            mo[kMlinBm + c] = -((Jm[c] * (rho1 * We[0]) + Jm[3 + c] * (rho1 * We[1])) + Jm[6 + c] * (rho1 * We[2]));
+        }
+        double Tt[9], Tr[9], Tm[9];  // (rho' Omega) Jt, (rho' Omega) Jr, (rho' Omega) Jm
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                Tt[r * 3 + c] = ((rho1 * pr.info[r * 3]) * Jt[c] + (rho1 * pr.info[r * 3 + 1]) * Jt[3 + c]) + (rho1 * pr.info[r * 3 + 2]) * Jt[6 + c];
+                Tr[r * 3 + c] = ((rho1 * pr.info[r * 3]) * Jr[c] + (rho1 * pr.info[r * 3 + 1]) * Jr[3 + c]) + (rho1 * pr.info[r * 3 + 2]) * Jr[6 + c];
+                Tm[r * 3 + c] = ((rho1 * pr.info[r * 3]) * Jm[c] + (rho1 * pr.info[r * 3 + 1]) * Jm[3 + c]) + (rho1 * pr.info[r * 3 + 2]) * Jm[6 + c];
+            }
+        }
+        double* Ho = L.Hii + id * 36;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                Ho[r * 6 + c] = (Jt[r] * Tt[c] + Jt[3 + r] * Tt[3 + c]) + Jt[6 + r] * Tt[6 + c];
+                Ho[r * 6 + 3 + c] = (Jt[r] * Tr[c] + Jt[3 + r] * Tr[3 + c]) + Jt[6 + r] * Tr[6 + c];
+                Ho[(3 + r) * 6 + c] = (Jr[r] * Tt[c] + Jr[3 + r] * Tt[3 + c]) + Jr[6 + r] * Tt[6 + c];
+                Ho[(3 + r) * 6 + 3 + c] = (Jr[r] * Tr[c] + Jr[3 + r] * Tr[3 + c]) + Jr[6 + r] * Tr[6 + c];
+                mo[kMlinHpm + r * 3 + c] = (Jt[r] * Tm[c] + Jt[3 + r] * Tm[3 + c]) + Jt[6 + r] * Tm[6 + c];
+                mo[kMlinHpm + (3 + r) * 3 + c] = (Jr[r] * Tm[c] + Jr[3 + r] * Tm[3 + c]) + Jr[6 + r] * Tm[6 + c];
+                mo[kMlinHmm + r * 3 + c] = (Jm[r] * Tm[c] + Jm[3 + r] * Tm[3 + c]) + Jm[6 + r] * Tm[6 + c];
+            }
+        }
+    }
+}
+
+// the border of the moment stage: Hpm [Na x 18] = per active node the sum of its moment edges' coupling blocks, Hmm [9] and bm [3] = the sums over
+// all moment edges plus the moment's own prior (Omega_m, -Omega_m m).  One lane per entry; mptr / mlist hold prior indices in rising edge id (a
+// prior's index rises with its id), all [n_all] the moment edges of the whole graph, those on fixed nodes included: no atomics
+__global__ void __launch_bounds__(256) graph_assemble_border(const LmState* __restrict__ st, int tag, uint32_t Na, const uint32_t* __restrict__ mptr,
+                                                             const uint32_t* __restrict__ mlist, const uint32_t* __restrict__ all, uint32_t n_all,
+                                                             const double* __restrict__ mlin, const double* __restrict__ mom, double* __restrict__ Hpm,
+                                                             double* __restrict__ Hmm, double* __restrict__ bm) {
+    if (!wanted(st, tag)) return;
+    const uint64_t np = 18ull * Na;
+    for (uint64_t g = blockIdx.x * 256ull + threadIdx.x; g < np + 12; g += gridDim.x * 256ull) {
+        double s = 0.0;
+        if (g < np) {
+            const uint32_t a = (uint32_t)(g / 18), k = (uint32_t)(g % 18);
+            for (uint32_t i = mptr[a]; i < mptr[a + 1]; i++) s += mlin[mlist[i] * (uint64_t)kMlinDoubles + kMlinHpm + k];
+            Hpm[g] = s;
+        } else if (g < np + 9) {
+            const uint32_t k = (uint32_t)(g - np);
+            for (uint32_t i = 0; i < n_all; i++) s += mlin[all[i] * (uint64_t)kMlinDoubles + kMlinHmm + k];
+            Hmm[k] = s + mom[kMomInfo + k];
+        } else {
+            const uint32_t k = (uint32_t)(g - np - 9);
+            for (uint32_t i = 0; i < n_all; i++) s += mlin[all[i] * (uint64_t)kMlinDoubles + kMlinBm + k];
+            const double* W = mom + kMomInfo + k * 3;
+            bm[k] = s - ((W[0] * mom[kMomM] + W[1] * mom[kMomM + 1]) + W[2] * mom[kMomM + 2]);
+        }
+    }
+}
+
 // Hd [Na x 36], Ho [P x 36], b [6 Na]: item = (block, entry); the lists hold (edge << 1 | flag) in rising edge id
 __global__ void __launch_bounds__(256) graph_assemble(const LmState* __restrict__ st, int tag, uint32_t Na, uint32_t P, const uint32_t* __restrict__ dptr,
                                                       const uint32_t* __restrict__ dlist, const uint32_t* __restrict__ pptr, const uint32_t* __restrict__ plist,
@@ -522,40 +652,81 @@ __device__ inline bool inv6_spd(const double* __restrict__ A, double lambda, dou
     return ok;
 }
 
-// one trial's (H + lambda I) d = b by preconditioned conjugate gradients, one workgroup.  vec: x, r, z, p, Ap of 6 Na each
-__global__ void __launch_bounds__(kSolveThreads) graph_solve(LmState* __restrict__ st, int tag, uint32_t Na, const double* __restrict__ Hd, const double* __restrict__ Ho,
-                                                             const double* __restrict__ b, const uint32_t* __restrict__ rptr, const uint32_t* __restrict__ rcol,
-                                                             const uint32_t* __restrict__ rblk, double* __restrict__ Minv, double* __restrict__ vec,
-                                                             double cg_epsilon, int cg_max_iterations) {
+// inverse of the damped SPD 3 x 3 (row-major) by Cholesky, as inv6_spd; false: not positive definite
+__device__ inline bool inv3_spd(const double* __restrict__ A, double lambda, double* __restrict__ out) {
+    bool ok = true;
+    double s = A[0] + lambda;
+    if (!(s > 0)) { ok = false; s = 1.0; }
+    const double l00 = sqrt(s), l10 = A[3] / l00, l20 = A[6] / l00;
+    s = (A[4] + lambda) - l10 * l10;
+    if (!(s > 0)) { ok = false; s = 1.0; }
+    const double l11 = sqrt(s), l21 = (A[7] - l20 * l10) / l11;
+    s = ((A[8] + lambda) - l20 * l20) - l21 * l21;
+    if (!(s > 0)) { ok = false; s = 1.0; }
+    const double l22 = sqrt(s);
+    // the factor's inverse (lower), then Li^T Li
+    const double i00 = 1.0 / l00, i11 = 1.0 / l11, i22 = 1.0 / l22;
+    const double i10 = -(l10 * i00) / l11, i21 = -(l21 * i11) / l22, i20 = -(l20 * i00 + l21 * i10) / l22;
+    out[0] = (i00 * i00 + i10 * i10) + i20 * i20;
+    out[1] = out[3] = i10 * i11 + i20 * i21;
+    out[2] = out[6] = i20 * i22;
+    out[4] = i11 * i11 + i21 * i21;
+    out[5] = out[7] = i21 * i22;
+    out[8] = i22 * i22;
+    return ok;
+}
+
+// the border of the moment stage as graph_solve sees it: three more unknowns behind the 6 Na of the nodes
+struct BorderArgs {
+    const double *Hpm, *Hmm, *bm;  // [Na x 18] coupling blocks (6 x 3 each), the border's 3 x 3, its 3 of b
+    double* Minv3;                 // [9] the inverse of the damped 3 x 3
+};
+
+// one trial's (H + lambda I) d = b by preconditioned conjugate gradients, one workgroup.  vec: x, r, z, p, Ap of n each, n = 6 Na, or 6 Na + 3 with
+// the border (kBorder): rows 6 Na .. 6 Na + 2 are the moment's.  The preconditioner then has the damped 3 x 3's inverse as one more block, a node
+// row of the product adds Hpm[a] p_m, and a border row is Hmm p_m + lambda p_m + sum_a Hpm[a]^T p_a, the sum folded by block_sum.  Without the
+// border every `kBorder &&` branch is compiled away and the text is the solve as it always was
+template <bool kBorder>
+__device__ __forceinline__ void solve_body(LmState* __restrict__ st, int tag, uint32_t Na, const double* __restrict__ Hd, const double* __restrict__ Ho,
+                                           const double* __restrict__ b, const uint32_t* __restrict__ rptr, const uint32_t* __restrict__ rcol,
+                                           const uint32_t* __restrict__ rblk, double* __restrict__ Minv, double* __restrict__ vec, double cg_epsilon,
+                                           int cg_max_iterations, const BorderArgs B) {
     if (!wanted(st, tag)) return;
     __shared__ double sh[kSolveThreads / 64];
-    const uint32_t n6 = 6u * Na, tid = threadIdx.x;
+    const uint32_t n6 = 6u * Na, n = kBorder ? n6 + 3u : n6, tid = threadIdx.x;
     double* x = vec;
-    double* r = vec + n6;
-    double* z = vec + 2ull * n6;
-    double* p = vec + 3ull * n6;
-    double* Ap = vec + 4ull * n6;
+    double* r = vec + n;
+    double* z = vec + 2ull * n;
+    double* p = vec + 3ull * n;
+    double* Ap = vec + 4ull * n;
     double lambda = st->lambda;
     const int need_init = st->need_lambda_init;
     const int cg_total0 = st->cg_total;
     if (need_init) {  // computeLambdaInit: tau max |diag H|
         double m = 0.0;
-        for (uint32_t i = tid; i < n6; i += kSolveThreads) m = fmax(m, fabs(Hd[(i / 6) * 36ull + (i % 6) * 7]));
+        for (uint32_t i = tid; i < n; i += kSolveThreads) m = fmax(m, fabs(kBorder && i >= n6 ? B.Hmm[(i - n6) * 4] : Hd[(i / 6) * 36ull + (i % 6) * 7]));
         lambda = 1e-5 * block_max(m, sh);
     }
     double okf = 1.0;
     for (uint32_t a = tid; a < Na; a += kSolveThreads)
         if (!inv6_spd(Hd + a * 36ull, lambda, Minv + a * 36ull)) okf = 0.0;
+    if (kBorder && tid == kSolveThreads - 1)
+        if (!inv3_spd(B.Hmm, lambda, B.Minv3)) okf = 0.0;
     double bb = 0.0;
-    for (uint32_t i = tid; i < n6; i += kSolveThreads) { const double v = b[i]; bb += v * v; x[i] = 0.0; r[i] = v; }
+    for (uint32_t i = tid; i < n; i += kSolveThreads) { const double v = kBorder && i >= n6 ? B.bm[i - n6] : b[i]; bb += v * v; x[i] = 0.0; r[i] = v; }
     bb = block_sum(bb, sh);  // (its barriers also publish Minv and r)
     const double bad = block_sum(1.0 - okf, sh);
     double rz = 0.0;
-    for (uint32_t i = tid; i < n6; i += kSolveThreads) {
-        const uint32_t a = i / 6, k = i % 6;
+    for (uint32_t i = tid; i < n; i += kSolveThreads) {
         double s = 0.0;
+        if (kBorder && i >= n6) {
+            const uint32_t k = i - n6;
+            s = (B.Minv3[k * 3] * r[n6] + B.Minv3[k * 3 + 1] * r[n6 + 1]) + B.Minv3[k * 3 + 2] * r[n6 + 2];
+        } else {
+            const uint32_t a = i / 6, k = i % 6;
 #pragma unroll
-        for (int c = 0; c < 6; c++) s += Minv[a * 36ull + k * 6 + c] * r[a * 6ull + c];
+            for (int c = 0; c < 6; c++) s += Minv[a * 36ull + k * 6 + c] * r[a * 6ull + c];
+        }
         z[i] = s; p[i] = s;
         rz += r[i] * s;
     }
@@ -565,7 +736,7 @@ __global__ void __launch_bounds__(kSolveThreads) graph_solve(LmState* __restrict
     int it = 0;
     bool ok = bad == 0.0 && bb - bb == 0.0;
     while (ok && it < cg_max_iterations && rr > tol2) {
-        double pAp = 0.0;
+        double pAp = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;  // c: this lane's share of sum_a Hpm[a]^T p_a
         for (uint32_t i = tid; i < n6; i += kSolveThreads) {
             const uint32_t a = i / 6, k = i % 6;
             double s = 0.0;
@@ -574,24 +745,39 @@ __global__ void __launch_bounds__(kSolveThreads) graph_solve(LmState* __restrict
             s += lambda * p[i];
             for (uint32_t e = rptr[a]; e < rptr[a + 1]; e++) {
                 const uint32_t w = rblk[e];
-                const double* B = Ho + (w & 0x7FFFFFFFu) * 36ull;
+                const double* Bk = Ho + (w & 0x7FFFFFFFu) * 36ull;
                 const double* pc = p + rcol[e] * 6ull;
                 if (w >> 31) {
 #pragma unroll
-                    for (int c = 0; c < 6; c++) s += B[c * 6 + k] * pc[c];
+                    for (int c = 0; c < 6; c++) s += Bk[c * 6 + k] * pc[c];
                 } else {
 #pragma unroll
-                    for (int c = 0; c < 6; c++) s += B[k * 6 + c] * pc[c];
+                    for (int c = 0; c < 6; c++) s += Bk[k * 6 + c] * pc[c];
                 }
+            }
+            if (kBorder) {
+                const double* C = B.Hpm + a * 18ull + k * 3;
+                s += (C[0] * p[n6] + C[1] * p[n6 + 1]) + C[2] * p[n6 + 2];
+                c0 += C[0] * p[i]; c1 += C[1] * p[i]; c2 += C[2] * p[i];
             }
             Ap[i] = s;
             pAp += p[i] * s;
+        }
+        if (kBorder) {
+            c0 = block_sum(c0, sh); c1 = block_sum(c1, sh); c2 = block_sum(c2, sh);
+            if (tid < 3) {  // the border's rows
+                const uint32_t i = n6 + tid;
+                const double* H = B.Hmm + tid * 3;
+                const double s = (((H[0] * p[n6] + H[1] * p[n6 + 1]) + H[2] * p[n6 + 2]) + lambda * p[i]) + (tid == 0 ? c0 : tid == 1 ? c1 : c2);
+                Ap[i] = s;
+                pAp += p[i] * s;
+            }
         }
         pAp = block_sum(pAp, sh);
         if (!(pAp > 0)) break;  // (the same bits in every lane: the whole workgroup leaves)
         const double alpha = rz / pAp;
         double rr2 = 0.0;
-        for (uint32_t i = tid; i < n6; i += kSolveThreads) {
+        for (uint32_t i = tid; i < n; i += kSolveThreads) {
             x[i] += alpha * p[i];
             const double v = r[i] - alpha * Ap[i];
             r[i] = v;
@@ -601,23 +787,28 @@ __global__ void __launch_bounds__(kSolveThreads) graph_solve(LmState* __restrict
         it++;
         if (!(rr > tol2)) break;
         double rz2 = 0.0;
-        for (uint32_t i = tid; i < n6; i += kSolveThreads) {
-            const uint32_t a = i / 6, k = i % 6;
+        for (uint32_t i = tid; i < n; i += kSolveThreads) {
             double s = 0.0;
+            if (kBorder && i >= n6) {
+                const uint32_t k = i - n6;
+                s = (B.Minv3[k * 3] * r[n6] + B.Minv3[k * 3 + 1] * r[n6 + 1]) + B.Minv3[k * 3 + 2] * r[n6 + 2];
+            } else {
+                const uint32_t a = i / 6, k = i % 6;
 #pragma unroll
-            for (int c = 0; c < 6; c++) s += Minv[a * 36ull + k * 6 + c] * r[a * 6ull + c];
+                for (int c = 0; c < 6; c++) s += Minv[a * 36ull + k * 6 + c] * r[a * 6ull + c];
+            }
             z[i] = s;
             rz2 += r[i] * s;
         }
         rz2 = block_sum(rz2, sh);
         const double beta = rz2 / rz;
         rz = rz2;
-        for (uint32_t i = tid; i < n6; i += kSolveThreads) p[i] = z[i] + beta * p[i];
+        for (uint32_t i = tid; i < n; i += kSolveThreads) p[i] = z[i] + beta * p[i];
         __syncthreads();
     }
     // computeScale: d^T (lambda d + b)
     double sc = 0.0;
-    for (uint32_t i = tid; i < n6; i += kSolveThreads) sc += x[i] * (lambda * x[i] + b[i]);
+    for (uint32_t i = tid; i < n; i += kSolveThreads) sc += x[i] * (lambda * x[i] + (kBorder && i >= n6 ? B.bm[i - n6] : b[i]));
     sc = block_sum(sc, sh);
     if (tid == 0) {
         st->lambda = lambda;
@@ -628,6 +819,19 @@ __global__ void __launch_bounds__(kSolveThreads) graph_solve(LmState* __restrict
         st->cg_total = cg_total0 + it;
         st->cg_relres = bb > 0 ? sqrt(rr / bb) : 0.0;
     }
+}
+__global__ void __launch_bounds__(kSolveThreads) graph_solve(LmState* __restrict__ st, int tag, uint32_t Na, const double* __restrict__ Hd, const double* __restrict__ Ho,
+                                                             const double* __restrict__ b, const uint32_t* __restrict__ rptr, const uint32_t* __restrict__ rcol,
+                                                             const uint32_t* __restrict__ rblk, double* __restrict__ Minv, double* __restrict__ vec,
+                                                             double cg_epsilon, int cg_max_iterations) {
+    solve_body<false>(st, tag, Na, Hd, Ho, b, rptr, rcol, rblk, Minv, vec, cg_epsilon, cg_max_iterations, BorderArgs{nullptr, nullptr, nullptr, nullptr});
+}
+// the same solve over the bordered system of the moment stage
+__global__ void __launch_bounds__(kSolveThreads) graph_solve_border(LmState* __restrict__ st, int tag, uint32_t Na, const double* __restrict__ Hd,
+                                                                    const double* __restrict__ Ho, const double* __restrict__ b, const uint32_t* __restrict__ rptr,
+                                                                    const uint32_t* __restrict__ rcol, const uint32_t* __restrict__ rblk, double* __restrict__ Minv,
+                                                                    double* __restrict__ vec, double cg_epsilon, int cg_max_iterations, BorderArgs B) {
+    solve_body<true>(st, tag, Na, Hd, Ho, b, rptr, rcol, rblk, Minv, vec, cg_epsilon, cg_max_iterations, B);
 }
 
 // backup + update of the active nodes
@@ -651,18 +855,29 @@ __global__ void __launch_bounds__(256) graph_update(const LmState* __restrict__ 
     for (int k = 0; k < 4; k++) nq[n * 4ull + k] = q[k];
 }
 
-// rho of every edge; one partial per 256 consecutive edge ids.  kPriors: an id may be a prior's placeholder, whose rho is taken from the prior
-template <bool kPriors>
-__global__ void __launch_bounds__(kEdgeThreads) graph_chi2(const LmState* __restrict__ st, int tag, const EdgeDev* __restrict__ edges, uint32_t E,
-                                                           const PriorDev* __restrict__ priors, const double* __restrict__ nt, const double* __restrict__ nq,
-                                                           double* __restrict__ partial) {
+// the moment stage's update, beside graph_update: backup + m <- m + d_m (VertexPointXYZ adds); d_m = the three entries behind the nodes' 6 Na
+__global__ void __launch_bounds__(64) graph_update_moment(const LmState* __restrict__ st, int tag, const double* __restrict__ dm, double* __restrict__ mom) {
+    if (!wanted(st, tag)) return;
+    if (blockIdx.x == 0 && threadIdx.x < 3) {
+        const double m = mom[kMomM + threadIdx.x];
+        mom[kMomBak + threadIdx.x] = m;
+        mom[kMomM + threadIdx.x] = m + dm[threadIdx.x];
+    }
+}
+
+// rho of every edge; one partial per 256 consecutive edge ids.  kPriors: an id may be a prior's placeholder, whose rho is taken from the prior;
+// kMoment: the stage is open and a live XYZ prior is a moment edge at the current m
+template <bool kPriors, bool kMoment>
+__device__ __forceinline__ void chi2_body(const LmState* __restrict__ st, int tag, const EdgeDev* __restrict__ edges, uint32_t E, const PriorDev* __restrict__ priors,
+                                          const double* __restrict__ nt, const double* __restrict__ nq, double* __restrict__ partial, const double* __restrict__ mom) {
     if (!wanted(st, tag)) return;
     __shared__ double sh[kEdgeThreads / 64];
     const uint32_t id = blockIdx.x * kEdgeThreads + threadIdx.x;
     double rho = 0.0;
     if (kPriors && id < E && edges[id].live == kPriorSlot) {
         const PriorDev& pr = priors[edges[id].from];
-        if (pr.live) rho = prior_rho(pr, nt, nq);
+        if (kMoment && pr.live && pr.type == LIO_GRAPH_PRIOR_XYZ) rho = moment_rho(pr, nt, nq, mom);
+        else if (pr.live) rho = prior_rho(pr, nt, nq);
     } else if (id < E && edges[id].live) {
         const EdgeDev& ed = edges[id];
         double ti[3], qi[4], tj[3], qj[4], mt[3], mq[4];
@@ -677,11 +892,24 @@ __global__ void __launch_bounds__(kEdgeThreads) graph_chi2(const LmState* __rest
     const double s = block_sum(rho, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
+template <bool kPriors>
+__global__ void __launch_bounds__(kEdgeThreads) graph_chi2(const LmState* __restrict__ st, int tag, const EdgeDev* __restrict__ edges, uint32_t E,
+                                                           const PriorDev* __restrict__ priors, const double* __restrict__ nt, const double* __restrict__ nq,
+                                                           double* __restrict__ partial) {
+    chi2_body<kPriors, false>(st, tag, edges, E, priors, nt, nq, partial, nullptr);
+}
+__global__ void __launch_bounds__(kEdgeThreads) graph_chi2_moment(const LmState* __restrict__ st, int tag, const EdgeDev* __restrict__ edges, uint32_t E,
+                                                                  const PriorDev* __restrict__ priors, const double* __restrict__ nt, const double* __restrict__ nq,
+                                                                  double* __restrict__ partial, const double* __restrict__ mom) {
+    chi2_body<true, true>(st, tag, edges, E, priors, nt, nq, partial, mom);
+}
 
-// one workgroup: the new chi2 (partials in order), the LM bookkeeping of OptimizationAlgorithmLevenberg::solve, the restore of a rejected trial
-__global__ void __launch_bounds__(256) graph_decide(LmState* __restrict__ st, int tag, const double* __restrict__ partial, uint32_t nb, uint32_t Na,
-                                                    const uint32_t* __restrict__ act, const double* __restrict__ bak, double* __restrict__ nt, double* __restrict__ nq,
-                                                    int max_iterations, double chi2_rel_stop) {
+// one workgroup: the new chi2 (partials in order), the LM bookkeeping of OptimizationAlgorithmLevenberg::solve, the restore of a rejected trial.
+// kMoment: the moment's own prior adds m^T Omega m after the partials, and a rejected trial restores m with the poses
+template <bool kMoment>
+__device__ __forceinline__ void decide_body(LmState* __restrict__ st, int tag, const double* __restrict__ partial, uint32_t nb, uint32_t Na,
+                                            const uint32_t* __restrict__ act, const double* __restrict__ bak, double* __restrict__ nt, double* __restrict__ nq,
+                                            int max_iterations, double chi2_rel_stop, double* __restrict__ mom) {
     __shared__ int s_go, s_accept;
     if (threadIdx.x == 0) s_go = wanted(st, tag) ? 1 : 0;  // (lane 0 rewrites the state below: every wave takes lane 0's answer)
     __syncthreads();
@@ -689,6 +917,7 @@ __global__ void __launch_bounds__(256) graph_decide(LmState* __restrict__ st, in
     if (threadIdx.x == 0) {
         double c = 0.0;
         for (uint32_t k = 0; k < nb; k++) c += partial[k];
+        if (kMoment) c += moment_prior_chi2(mom + kMomM, mom + kMomInfo);
         if (!st->solve_ok) c = DBL_MAX;
         const double rho = (st->chi2 - c) / st->scale;
         const bool accept = rho > 0 && c - c == 0.0 && st->solve_ok;
@@ -736,6 +965,17 @@ __global__ void __launch_bounds__(256) graph_decide(LmState* __restrict__ st, in
 #pragma unroll
         for (int k = 0; k < 4; k++) nq[n * 4ull + k] = bak[a * 7ull + 3 + k];
     }
+    if (kMoment && threadIdx.x < 3) mom[kMomM + threadIdx.x] = mom[kMomBak + threadIdx.x];
+}
+__global__ void __launch_bounds__(256) graph_decide(LmState* __restrict__ st, int tag, const double* __restrict__ partial, uint32_t nb, uint32_t Na,
+                                                    const uint32_t* __restrict__ act, const double* __restrict__ bak, double* __restrict__ nt, double* __restrict__ nq,
+                                                    int max_iterations, double chi2_rel_stop) {
+    decide_body<false>(st, tag, partial, nb, Na, act, bak, nt, nq, max_iterations, chi2_rel_stop, nullptr);
+}
+__global__ void __launch_bounds__(256) graph_decide_moment(LmState* __restrict__ st, int tag, const double* __restrict__ partial, uint32_t nb, uint32_t Na,
+                                                           const uint32_t* __restrict__ act, const double* __restrict__ bak, double* __restrict__ nt,
+                                                           double* __restrict__ nq, int max_iterations, double chi2_rel_stop, double* __restrict__ mom) {
+    decide_body<true>(st, tag, partial, nb, Na, act, bak, nt, nq, max_iterations, chi2_rel_stop, mom);
 }
 
 }  // namespace graph
@@ -782,6 +1022,16 @@ struct lio_graph {
     LmState *d_state = nullptr, *h_state = nullptr;
     lio_graph_report rep{};
     double t_lin = 0, t_asm = 0, t_solve = 0, t_update = 0;
+    // the moment stage, between lio_graph_moment_begin and _end: every live XYZ prior is an edge to one shared 3-DoF vertex, a border on the system
+    bool moment_open = false, border_stale = true;
+    double moment_info[9] = {};
+    double* d_mom = nullptr;     // kMomDoubles; kept from the first begin on
+    double* d_border = nullptr;  // Hmm, bm, Minv3, Hpm [18 Na], vec [5 (6 Na + 3)], mlin [kMlinDoubles per prior]
+    uint64_t border_cap = 0;
+    double *d_Hmm = nullptr, *d_bm = nullptr, *d_Minv3 = nullptr, *d_Hpm = nullptr, *d_bvec = nullptr, *d_mlin = nullptr;
+    uint32_t* d_btopo = nullptr;  // mptr [Na + 1], mlist, all
+    uint64_t btopo_cap = 0;
+    uint32_t *d_mptr = nullptr, *d_mlist = nullptr, *d_mall = nullptr, n_mall = 0;
 };
 
 namespace {
@@ -966,6 +1216,56 @@ int build_topology(lio_graph* g) {
     g->d_bak = q;
     g->Na = Na; g->P = P; g->nnz = 2 * P;
     g->topo_dirty = false;
+    g->border_stale = true;
+    return LIO_OK;
+}
+
+// the border's lists and buffers over the current topology: per active node its live XYZ priors, and all of them, by prior index (= rising id)
+int build_border(lio_graph* g) {
+    const uint32_t Na = g->Na, NP = (uint32_t)g->priors.size();
+    std::vector<int32_t> aidx(num_nodes(g), -1);
+    for (uint32_t a = 0; a < Na; a++) aidx[g->act[a]] = (int32_t)a;
+    std::vector<std::vector<uint32_t>> ml(Na);
+    std::vector<uint32_t> all;
+    for (uint32_t k = 0; k < NP; k++) {
+        const PriorDev& p = g->priors[k];
+        if (!p.live || p.type != LIO_GRAPH_PRIOR_XYZ) continue;
+        all.push_back(k);
+        if (aidx[p.node] >= 0) ml[aidx[p.node]].push_back(k);
+    }
+    std::vector<uint32_t> host(Na + 1, 0);
+    for (uint32_t a = 0; a < Na; a++) host[a + 1] = host[a] + (uint32_t)ml[a].size();
+    for (uint32_t a = 0; a < Na; a++) host.insert(host.end(), ml[a].begin(), ml[a].end());
+    const uint64_t off_all = host.size();
+    host.insert(host.end(), all.begin(), all.end());
+    if (host.size() > g->btopo_cap) {
+        uint64_t c = g->btopo_cap ? g->btopo_cap : 1024;
+        while (c < host.size()) c *= 2;
+        if (g->d_btopo) hipFree(g->d_btopo);
+        g->d_btopo = nullptr; g->btopo_cap = 0;
+        LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->d_btopo), c * sizeof(uint32_t)));
+        g->btopo_cap = c;
+    }
+    LIO_HIP_TRY(hipMemcpy(g->d_btopo, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    g->d_mptr = g->d_btopo; g->d_mlist = g->d_btopo + (Na + 1); g->d_mall = g->d_btopo + off_all;
+    g->n_mall = (uint32_t)all.size();
+    const uint64_t nvec = 6ull * Na + 3, dbl = 9 + 3 + 9 + 18ull * Na + 5 * nvec + (uint64_t)kMlinDoubles * NP + 16;
+    if (dbl > g->border_cap) {
+        uint64_t c = g->border_cap ? g->border_cap : 4096;
+        while (c < dbl) c *= 2;
+        if (g->d_border) hipFree(g->d_border);
+        g->d_border = nullptr; g->border_cap = 0;
+        LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->d_border), c * sizeof(double)));
+        g->border_cap = c;
+    }
+    double* q = g->d_border;
+    g->d_Hmm = q; q += 9;
+    g->d_bm = q; q += 3;
+    g->d_Minv3 = q; q += 9;
+    g->d_Hpm = q; q += 18ull * Na;
+    g->d_bvec = q; q += 5 * nvec;
+    g->d_mlin = q;
+    g->border_stale = false;
     return LIO_OK;
 }
 
@@ -973,7 +1273,16 @@ int prepare(lio_graph* g) {
     hipSetDevice(g->device);
     int rc = flush(g);
     if (rc != LIO_OK) return rc;
-    return build_topology(g);
+    rc = build_topology(g);
+    if (rc == LIO_OK && g->moment_open && g->border_stale) rc = build_border(g);
+    return rc;
+}
+
+// between lio_graph_moment_begin and _end the graph's topology is closed
+bool moment_refuses(const lio_graph* g, const char* who) {
+    if (!g->moment_open) return false;
+    set_error("%s: refused between lio_graph_moment_begin and lio_graph_moment_end", who);
+    return true;
 }
 
 uint32_t grid_for(uint64_t items, uint32_t threads) {
@@ -991,15 +1300,27 @@ int launch_linearize(lio_graph* g, int tag) {
         hipLaunchKernelGGL(graph_linearize_prior, grid_for(NP, kEdgeThreads), kEdgeThreads, 0, g->st, g->d_priors, NP, g->d_t, g->d_q, g->d_state, tag, g->lin);
         LIO_HIP_TRY(hipGetLastError());
     }
+    if (NP && g->moment_open) {  // after graph_linearize_prior: a live XYZ prior's slots are taken again as a moment edge's
+        hipLaunchKernelGGL(graph_linearize_moment, grid_for(NP, kEdgeThreads), kEdgeThreads, 0, g->st, g->d_priors, NP, g->d_t, g->d_q, g->d_state, tag, g->lin, g->d_mom,
+                           g->d_mlin);
+        LIO_HIP_TRY(hipGetLastError());
+    }
     return LIO_OK;
 }
 void launch_chi2(lio_graph* g, int tag, uint32_t nb, uint32_t E) {
-    if (g->priors.empty())
+    if (g->moment_open)
+        hipLaunchKernelGGL(graph_chi2_moment, nb, kEdgeThreads, 0, g->st, g->d_state, tag, g->d_edges, E, g->d_priors, g->d_t, g->d_q, g->d_partial, g->d_mom);
+    else if (g->priors.empty())
         hipLaunchKernelGGL(graph_chi2<false>, nb, kEdgeThreads, 0, g->st, g->d_state, tag, g->d_edges, E, g->d_priors, g->d_t, g->d_q, g->d_partial);
     else
         hipLaunchKernelGGL(graph_chi2<true>, nb, kEdgeThreads, 0, g->st, g->d_state, tag, g->d_edges, E, g->d_priors, g->d_t, g->d_q, g->d_partial);
 }
 int launch_assemble(lio_graph* g, int tag) {
+    if (g->moment_open) {
+        hipLaunchKernelGGL(graph_assemble_border, grid_for(18ull * g->Na + 12, 256), 256, 0, g->st, g->d_state, tag, g->Na, g->d_mptr, g->d_mlist, g->d_mall, g->n_mall,
+                           g->d_mlin, g->d_mom, g->d_Hpm, g->d_Hmm, g->d_bm);
+        LIO_HIP_TRY(hipGetLastError());
+    }
     if (!g->Na) return LIO_OK;
     const uint64_t items = 36ull * g->Na + 36ull * g->P + 6ull * g->Na;
     hipLaunchKernelGGL(graph_assemble, grid_for(items, 256), 256, 0, g->st, g->d_state, tag, g->Na, g->P, g->d_dptr, g->d_dlist, g->d_pptr, g->d_plist, g->lin, g->d_Hd,
@@ -1018,6 +1339,12 @@ int chi2_now(lio_graph* g, double* out) {
         LIO_HIP_TRY(hipMemcpyAsync(g->h_partial, g->d_partial, nb * sizeof(double), hipMemcpyDeviceToHost, g->st));
         LIO_HIP_TRY(hipStreamSynchronize(g->st));
         for (uint32_t k = 0; k < nb; k++) c += g->h_partial[k];
+    }
+    if (g->moment_open) {  // the moment's own prior, after the partials as graph_decide adds it
+        double m[3];
+        LIO_HIP_TRY(hipMemcpyAsync(m, g->d_mom + kMomM, sizeof(m), hipMemcpyDeviceToHost, g->st));
+        LIO_HIP_TRY(hipStreamSynchronize(g->st));
+        c += moment_prior_chi2(m, g->moment_info);
     }
     *out = c;
     return LIO_OK;
@@ -1045,6 +1372,7 @@ int prior_set(lio_graph* g, uint32_t slot, int kernel, double delta, int live) {
 
 void free_all(lio_graph* g) {
     hipFree(g->d_t); hipFree(g->d_q); hipFree(g->d_edges); hipFree(g->d_priors); hipFree(g->d_lin); hipFree(g->d_topo); hipFree(g->d_sys); hipFree(g->d_partial); hipFree(g->d_state);
+    hipFree(g->d_mom); hipFree(g->d_border); hipFree(g->d_btopo);
     if (g->h_partial) hipHostFree(g->h_partial);
     if (g->h_state) hipHostFree(g->h_state);
 }
@@ -1114,6 +1442,7 @@ void lio_graph_destroy(lio_graph* g) {
 
 int lio_graph_reset(lio_graph* g) {
     if (!g) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_reset")) return LIO_E_STATE;
     hipSetDevice(g->device);
     LIO_HIP_TRY(hipStreamSynchronize(g->st));
     g->from.clear(); g->to.clear(); g->pslot.clear(); g->live.clear(); g->fixed.clear(); g->gone.clear(); g->rec.clear(); g->pend_nodes.clear(); g->pend_edges.clear(); g->priors.clear();
@@ -1127,6 +1456,7 @@ int lio_graph_reset(lio_graph* g) {
 
 int lio_graph_add_node(lio_graph* g, const double pose16[16]) {
     if (!g || !pose16 || !pose_ok(pose16)) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_add_node")) return LIO_E_STATE;
     double t[3], q[4];
     T_to_tq(pose16, t, q);
     g->pend_nodes.insert(g->pend_nodes.end(), t, t + 3);
@@ -1160,6 +1490,7 @@ int lio_graph_set_estimate(lio_graph* g, int id, const double pose16[16]) {
 
 int lio_graph_add_edge(lio_graph* g, int from, int to, const double M16[16], const double info36[36], int kernel, double delta) {
     if (!g || !M16 || !info36 || !node_ok(g, from) || !node_ok(g, to) || !pose_ok(M16)) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_add_edge")) return LIO_E_STATE;
     if (from == to) { set_error("lio_graph_add_edge: an edge from node %d to itself", from); return LIO_E_INVALID; }
     if (!kernel_ok("lio_graph_add_edge", kernel, delta)) return LIO_E_INVALID;
     double amax = 0.0;
@@ -1186,6 +1517,7 @@ int lio_graph_add_edge(lio_graph* g, int from, int to, const double M16[16], con
 
 int lio_graph_add_prior(lio_graph* g, int node, int type, const double m4[4], const double plane4[4], const double info9[9], int kernel, double delta) {
     if (!g || !m4 || !info9 || !node_ok(g, node)) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_add_prior")) return LIO_E_STATE;
     if (type != LIO_GRAPH_PRIOR_XYZ && type != LIO_GRAPH_PRIOR_QUAT && type != LIO_GRAPH_PRIOR_PLANE) { set_error("lio_graph_add_prior: unknown type %d", type); return LIO_E_INVALID; }
     if (type == LIO_GRAPH_PRIOR_PLANE && !plane4) { set_error("lio_graph_add_prior: a PLANE prior needs its world plane"); return LIO_E_INVALID; }
     if (!kernel_ok("lio_graph_add_prior", kernel, delta) || !(delta - delta == 0.0)) return LIO_E_INVALID;
@@ -1294,6 +1626,7 @@ int lio_graph_prior_error(const double X16[16], int type, const double m4[4], co
 
 int lio_graph_remove_edge(lio_graph* g, int id) {
     if (!g || id < 0 || (uint32_t)id >= num_edges(g) || !g->live[id]) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_remove_edge")) return LIO_E_STATE;
     g->live[id] = 0;
     g->topo_dirty = true;
     if (g->pslot[id] >= 0) {  // the placeholder stays; the prior's own record goes dead
@@ -1310,6 +1643,7 @@ int lio_graph_remove_edge(lio_graph* g, int id) {
 
 int lio_graph_remove_node(lio_graph* g, int id) {
     if (!g || !node_ok(g, id)) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_remove_node")) return LIO_E_STATE;
     for (uint32_t e = 0; e < num_edges(g); e++) {  // g2o's removeVertex: every edge and prior on the node goes with it
         if (!g->live[e] || (g->from[e] != id && g->to[e] != id)) continue;
         const int rc = lio_graph_remove_edge(g, (int)e);
@@ -1430,6 +1764,8 @@ int lio_graph_optimize(lio_graph* g, int max_iterations, lio_graph_report* repor
     if (!g) return LIO_E_INVALID;
     uint32_t n_live = 0;
     for (uint32_t e = 0; e < num_edges(g); e++) n_live += g->live[e];
+    const bool border = g->moment_open;
+    if (border) n_live++;  // the moment's own prior is a live edge
     if ((int64_t)n_live < (int64_t)g->par.min_edges) return -1;  // GraphSLAM::optimize: nothing is touched
     int rc = prepare(g);
     if (rc != LIO_OK) return rc;
@@ -1442,13 +1778,14 @@ int lio_graph_optimize(lio_graph* g, int max_iterations, lio_graph_report* repor
     rc = chi2_now(g, &c0);
     if (rc != LIO_OK) return rc;
     R.chi2_initial = R.chi2_final = c0;
-    if (max_iterations <= 0 || g->Na == 0) { if (report) *report = R; return 0; }
+    if (max_iterations <= 0 || (g->Na == 0 && !border) || num_edges(g) == 0) { if (report) *report = R; return 0; }
     LmState& S = *g->h_state;
     memset(&S, 0, sizeof(S));
     S.chi2 = c0; S.nu = 2.0; S.need_lambda_init = 1;
     LIO_HIP_TRY(hipMemcpyAsync(g->d_state, g->h_state, sizeof(LmState), hipMemcpyHostToDevice, g->st));
     const uint32_t E = num_edges(g), nb = (E + kEdgeThreads - 1) / kEdgeThreads, Na = g->Na;
-    const int cg_max = g->par.cg_max_iterations > 0 ? g->par.cg_max_iterations : (int)(12u * Na);
+    const int cg_max = g->par.cg_max_iterations > 0 ? g->par.cg_max_iterations : (Na ? (int)(12u * Na) : 3);  // (Na = 0: the border's three unknowns alone)
+    const BorderArgs B{g->d_Hpm, g->d_Hmm, g->d_bm, g->d_Minv3};
     for (int it = 0; it < max_iterations; it++) {
         int ne = 0;
         hipEventRecord(g->ev[ne++], g->st);
@@ -1458,7 +1795,18 @@ int lio_graph_optimize(lio_graph* g, int max_iterations, lio_graph_report* repor
         rc = launch_assemble(g, it);
         if (rc != LIO_OK) return rc;
         hipEventRecord(g->ev[ne++], g->st);
-        for (int trial = 0; trial < kMaxTrials; trial++) {
+        for (int trial = 0; border && trial < kMaxTrials; trial++) {  // the same trial over the bordered system
+            hipLaunchKernelGGL(graph_solve_border, 1, kSolveThreads, 0, g->st, g->d_state, it, Na, g->d_Hd, g->d_Ho, g->d_b, g->d_rptr, g->d_rcol, g->d_rblk, g->d_Minv,
+                               g->d_bvec, g->par.cg_epsilon, cg_max, B);
+            hipEventRecord(g->ev[ne++], g->st);
+            if (Na) hipLaunchKernelGGL(graph_update, (Na + 255) / 256, 256, 0, g->st, g->d_state, it, Na, g->d_act, g->d_bvec, g->d_t, g->d_q, g->d_bak);
+            hipLaunchKernelGGL(graph_update_moment, 1, 64, 0, g->st, g->d_state, it, g->d_bvec + 6ull * Na, g->d_mom);
+            launch_chi2(g, it, nb, E);
+            hipLaunchKernelGGL(graph_decide_moment, 1, 256, 0, g->st, g->d_state, it, g->d_partial, nb, Na, g->d_act, g->d_bak, g->d_t, g->d_q, max_iterations,
+                               g->par.chi2_rel_stop, g->d_mom);
+            hipEventRecord(g->ev[ne++], g->st);
+        }
+        for (int trial = 0; !border && trial < kMaxTrials; trial++) {
             hipLaunchKernelGGL(graph_solve, 1, kSolveThreads, 0, g->st, g->d_state, it, Na, g->d_Hd, g->d_Ho, g->d_b, g->d_rptr, g->d_rcol, g->d_rblk, g->d_Minv, g->d_vec,
                                g->par.cg_epsilon, cg_max);
             hipEventRecord(g->ev[ne++], g->st);
@@ -1494,6 +1842,7 @@ int lio_graph_optimize(lio_graph* g, int max_iterations, lio_graph_report* repor
 
 int lio_graph_remove_gnss_outliers(lio_graph* g, double max_distance_error, int max_iterations, int32_t* removed_ids, uint32_t cap, lio_graph_report* report) {
     if (!g || !(max_distance_error > 0)) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_remove_gnss_outliers")) return LIO_E_STATE;
     uint32_t n_live = 0;
     for (uint32_t e = 0; e < num_edges(g); e++) n_live += g->live[e];
     if ((int64_t)n_live < (int64_t)g->par.min_edges) return -1;
@@ -1531,6 +1880,121 @@ int lio_graph_remove_gnss_outliers(lio_graph* g, double max_distance_error, int 
     rc = lio_graph_optimize(g, max_iterations, report);
     if (rc < -1) return rc;
     return removed;
+}
+
+int lio_graph_moment_begin(lio_graph* g, const double m0[3], const double info9[9]) {
+    if (!g) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_moment_begin")) return LIO_E_STATE;
+    double mom[kMomDoubles] = {};
+    const double ref[9] = {1.0 / 2000.0, 0, 0, 0, 1.0 / 2000.0, 0, 0, 0, 1.0 / 200.0};  // hdl_graph_slam_nodelet.cpp:1041-1043
+    for (int k = 0; k < 3; k++) mom[kMomM + k] = mom[kMomBak + k] = m0 ? m0[k] : 0.0;
+    double amax = 0.0;
+    for (int k = 0; k < 9; k++) { mom[kMomInfo + k] = info9 ? info9[k] : ref[k]; amax = fmax(amax, fabs(mom[kMomInfo + k])); }
+    for (int k = 0; k < kMomDoubles; k++)
+        if (!(mom[k] - mom[k] == 0.0)) { set_error("lio_graph_moment_begin: the moment or its information is not finite"); return LIO_E_INVALID; }
+    for (int r = 0; r < 3; r++)
+        for (int c = r + 1; c < 3; c++)
+            if (fabs(mom[kMomInfo + r * 3 + c] - mom[kMomInfo + c * 3 + r]) > 1e-9 * amax) { set_error("lio_graph_moment_begin: the information matrix is not symmetric"); return LIO_E_INVALID; }
+    hipSetDevice(g->device);
+    if (!g->d_mom) LIO_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g->d_mom), kMomDoubles * sizeof(double)));
+    LIO_HIP_TRY(hipMemcpy(g->d_mom, mom, sizeof(mom), hipMemcpyHostToDevice));
+    memcpy(g->moment_info, mom + kMomInfo, sizeof(g->moment_info));
+    g->moment_open = true;
+    g->border_stale = true;
+    const int rc = prepare(g);
+    if (rc != LIO_OK) g->moment_open = false;
+    return rc;
+}
+
+int lio_graph_moment_get(lio_graph* g, double m3[3]) {
+    if (!g || !m3) return LIO_E_INVALID;
+    if (!g->moment_open) { set_error("lio_graph_moment_get: no moment stage is open"); return LIO_E_STATE; }
+    hipSetDevice(g->device);
+    LIO_HIP_TRY(hipStreamSynchronize(g->st));
+    LIO_HIP_TRY(hipMemcpy(m3, g->d_mom + kMomM, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return LIO_OK;
+}
+
+int lio_graph_moment_end(lio_graph* g, int apply) {
+    if (!g) return LIO_E_INVALID;
+    if (!g->moment_open) { set_error("lio_graph_moment_end: no moment stage is open"); return LIO_E_STATE; }
+    int moved = 0;
+    if (apply) {  // every moment edge is an XYZ prior again: z' = z + R_node m, in place (its id, information and kernel stay)
+        double m[3];
+        int rc = lio_graph_moment_get(g, m);
+        if (rc != LIO_OK) return rc;
+        const uint32_t N = num_nodes(g), NP = (uint32_t)g->priors.size();
+        std::vector<double> q(4ull * N);
+        if (N) LIO_HIP_TRY(hipMemcpy(q.data(), g->d_q, q.size() * sizeof(double), hipMemcpyDeviceToHost));
+        uint32_t first = NP;
+        for (uint32_t k = 0; k < NP; k++) {
+            PriorDev& p = g->priors[k];
+            if (!p.live || p.type != LIO_GRAPH_PRIOR_XYZ) continue;
+            double R[9];
+            q_to_R(&q[4ull * p.node], R);
+            for (int r = 0; r < 3; r++) p.m[r] = p.m[r] + ((R[r * 3] * m[0] + R[r * 3 + 1] * m[1]) + R[r * 3 + 2] * m[2]);
+            if (first == NP) first = k;
+            moved++;
+        }
+        if (moved) LIO_HIP_TRY(hipMemcpy(g->d_priors + first, g->priors.data() + first, (NP - first) * sizeof(PriorDev), hipMemcpyHostToDevice));
+    }
+    g->moment_open = false;
+    return moved;
+}
+
+int lio_graph_moment_linearize(lio_graph* g, double bm3[3], double Hmm9[9], double* Hpm, uint32_t node_cap) {
+    if (!g) return LIO_E_INVALID;
+    if (!g->moment_open) { set_error("lio_graph_moment_linearize: no moment stage is open"); return LIO_E_STATE; }
+    const uint32_t N = num_nodes(g);
+    if (Hpm && N > node_cap) return LIO_E_CAPACITY;
+    int rc = prepare(g);
+    if (rc != LIO_OK) return rc;
+    rc = launch_linearize(g, -1);
+    if (rc == LIO_OK) rc = launch_assemble(g, -1);
+    if (rc != LIO_OK) return rc;
+    LIO_HIP_TRY(hipStreamSynchronize(g->st));
+    if (bm3) LIO_HIP_TRY(hipMemcpy(bm3, g->d_bm, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (Hmm9) LIO_HIP_TRY(hipMemcpy(Hmm9, g->d_Hmm, 9 * sizeof(double), hipMemcpyDeviceToHost));
+    if (Hpm) {
+        memset(Hpm, 0, 18ull * N * sizeof(double));
+        if (g->Na) {
+            std::vector<double> h(18ull * g->Na);
+            LIO_HIP_TRY(hipMemcpy(h.data(), g->d_Hpm, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (uint32_t a = 0; a < g->Na; a++) memcpy(Hpm + 18ull * g->act[a], &h[18ull * a], 18 * sizeof(double));
+        }
+    }
+    return (int)g->n_mall;
+}
+
+int lio_graph_estimate_gnss_moment(lio_graph* g, double max_distance_error, int max_iterations, const double* prior_info9, double moment3[3], lio_graph_report* report) {
+    if (!g || !(max_distance_error > 0)) return LIO_E_INVALID;
+    if (moment_refuses(g, "lio_graph_estimate_gnss_moment")) return LIO_E_STATE;
+    std::vector<uint32_t> gnss;
+    for (uint32_t k = 0; k < g->priors.size(); k++) {
+        const PriorDev& p = g->priors[k];
+        if (!p.live || p.type != LIO_GRAPH_PRIOR_XYZ) continue;
+        if (!(max_distance_error * max_distance_error * p.info[0] > 0)) { set_error("lio_graph_estimate_gnss_moment: prior %d has no positive information(0, 0)", p.id); return LIO_E_INVALID; }
+        gnss.push_back(k);
+    }
+    if (moment3) moment3[0] = moment3[1] = moment3[2] = 0.0;
+    if (gnss.empty()) return 0;  // nothing to estimate from: nothing is touched
+    uint32_t n_live = 1;  // the moment's own prior
+    for (uint32_t e = 0; e < num_edges(g); e++) n_live += g->live[e];
+    if ((int64_t)n_live < (int64_t)g->par.min_edges) { set_error("lio_graph_estimate_gnss_moment: fewer than min_edges live edges"); return LIO_E_STATE; }
+    hipSetDevice(g->device);
+    for (uint32_t k : gnss) {
+        const int rc = prior_set(g, k, LIO_GRAPH_KERNEL_DCS2, max_distance_error * max_distance_error * g->priors[k].info[0], 1);
+        if (rc != LIO_OK) return rc;
+    }
+    int rc = lio_graph_moment_begin(g, nullptr, prior_info9);
+    if (rc != LIO_OK) return rc;
+    rc = lio_graph_optimize(g, max_iterations, report);
+    if (rc < 0) { lio_graph_moment_end(g, 0); return rc == -1 ? LIO_E_STATE : rc; }
+    if (moment3) {
+        rc = lio_graph_moment_get(g, moment3);
+        if (rc != LIO_OK) { lio_graph_moment_end(g, 0); return rc; }
+    }
+    return lio_graph_moment_end(g, 1);
 }
 
 int lio_graph_last_times(lio_graph* g, double* linearize_us, double* assemble_us, double* solve_us, double* update_us) {

@@ -275,6 +275,12 @@ struct Slam {
     // set_gnss(true) / LSD_AMD_GNSS=1.  On: the first valid fix sets the map origin, every valid fix goes to the graph's GNSS queue, and
     // update_odom() flushes the queue against the graph's key frames into priors.  The queue is guarded by kf_mtx
     bool gnss = false;
+    // the GNSS moment stage of run_robust_graph_optimization("mapping") (hdl_graph_slam_nodelet.cpp:1037-1081): off unless set_gnss_moment(true) /
+    // LSD_AMD_GNSS_MOMENT=1.  What the last stage found, for _last_gnss_moment(); guarded by kf_mtx
+    bool gnss_moment = false, moment_ran = false;
+    double moment_last[3] = {0, 0, 0};
+    int moment_priors = 0;
+    lio_graph_report moment_report{};
     int ins_dim = 2;                      // SLAM::mInsDim (set_ins_config's ins_type)
     lio_gnss_queue* gnss_queue = nullptr;
     // method = "RTKM" (slam/mapping/rtkm/src/rtkm.cpp): poses straight from the RTK track, the lidars merged into one frame on the device;
@@ -956,6 +962,8 @@ py::list init_slam(const std::string mode, const std::string map_path, const std
     g->rtkm = !localization && method == "RTKM";
     const char* gnss_env = std::getenv("LSD_AMD_GNSS");
     g->gnss = gnss_env && gnss_env[0] == '1';
+    const char* moment_env = std::getenv("LSD_AMD_GNSS_MOMENT");
+    g->gnss_moment = moment_env && moment_env[0] == '1';
     g->mode = localization ? "localization" : mode;
     g->method = method;
     g->map_path = map_path;
@@ -2075,6 +2083,39 @@ void set_gnss(bool enable) {
     std::lock_guard<std::mutex> kl(g->kf_mtx);
     g->gnss = enable;
 }
+// not in the reference's module (whose mapping mode always runs the stage): the GNSS moment stage of run_robust_graph_optimization("mapping") --
+// the constant offset between the antenna and the lidar frame estimated as one shared vertex, every GNSS prior moved by it -- off by default;
+// LSD_AMD_GNSS_MOMENT=1 at init_slam switches it on for an unchanged slam.py.  Off: run_robust_graph_optimization answers as it always has
+void set_gnss_moment(bool enable) {
+    require((bool)g, "init_slam first");
+    py::gil_scoped_release rel;
+    std::lock_guard<std::mutex> kl(g->kf_mtx);
+    g->gnss_moment = enable;
+}
+// test visibility: what the moment stage of the last run_robust_graph_optimization found; {} when it did not run
+py::dict _last_gnss_moment() {
+    py::dict d;
+    if (!g) return d;
+    double m[3];
+    int priors;
+    bool ran;
+    lio_graph_report rep;
+    {
+        py::gil_scoped_release rel;
+        std::lock_guard<std::mutex> kl(g->kf_mtx);
+        ran = g->moment_ran;
+        std::memcpy(m, g->moment_last, sizeof(m));
+        priors = g->moment_priors;
+        rep = g->moment_report;
+    }
+    if (!ran) return d;
+    d["moment"] = std::vector<double>{m[0], m[1], m[2]};
+    d["priors"] = priors;
+    d["iterations"] = rep.iterations;
+    d["chi2_initial"] = rep.chi2_initial;
+    d["chi2_final"] = rep.chi2_final;
+    return d;
+}
 // test visibility: what process() does with a fix (the validity filter, the origin, the method's feedInsData, FastLIO's velocity hand-over when
 // there is an engine) and nothing else; the frame's timestamp is the fix's own
 void _push_gnss(py::dict rtk_dict) {
@@ -2931,15 +2972,22 @@ py::dict run_graph_optimization() {
 }
 // robust_graph_optimize (hdl_graph_slam_nodelet.cpp:1000-1038): the GNSS outlier stage at 1.0 m (DCS2 on every GNSS prior, optimise, drop the
 // priors whose scale fell below 0.1, optimise), then what run_graph_optimization does; {} without a graph.  The "GNSS moment" stage of mode
-// "mapping" (:1039-1081) needs a 3-DoF point vertex and is not built: both modes run the same stage
+// "mapping" (:1037-1081, lio_graph_estimate_gnss_moment) runs after it under set_gnss_moment(true) and never in mode "localization"; a graph
+// below min_edges, which the outlier stage left untouched, skips it as well
 py::dict run_robust_graph_optimization(std::string mode) {
-    (void)mode;
     std::vector<std::pair<int, Mat4>> odoms;
     if (g) {
         py::gil_scoped_release rel;
         std::lock_guard<std::mutex> kl(g->kf_mtx);
+        g->moment_ran = false;
         if (g->graph && !g->graph_odom.empty()) {
-            require(lio_graph_remove_gnss_outliers(g->graph, 1.0, 1024, nullptr, 0, nullptr) >= -1, "run_robust_graph_optimization: lio_graph_remove_gnss_outliers failed");
+            const int removed = lio_graph_remove_gnss_outliers(g->graph, 1.0, 1024, nullptr, 0, nullptr);
+            require(removed >= -1, "run_robust_graph_optimization: lio_graph_remove_gnss_outliers failed");
+            if (g->gnss_moment && mode == "mapping" && removed >= 0) {
+                const int n = lio_graph_estimate_gnss_moment(g->graph, 1.0, 1024, nullptr, g->moment_last, &g->moment_report);
+                require(n >= 0, "run_robust_graph_optimization: lio_graph_estimate_gnss_moment failed");
+                if (n > 0) { g->moment_ran = true; g->moment_priors = n; }
+            }
             graph_optimize_locked(g.get(), "run_robust_graph_optimization");
             for (size_t k = 0; k < g->graph_pose.size(); k++)
                 if (!g->graph_gone[k]) odoms.emplace_back((int)k, g->graph_pose[k]);
@@ -4129,6 +4177,8 @@ PYBIND11_MODULE(slam_wrapper, m) {
           "both maps' GNSS priors",
           py::arg("enable"));
     m.def("_push_gnss", &_push_gnss, "test hook: what process() does with a fix", py::arg("rtk_dict"));
+    m.def("set_gnss_moment", &set_gnss_moment, "the GNSS moment stage of run_robust_graph_optimization(\"mapping\") (off by default)", py::arg("enable"));
+    m.def("_last_gnss_moment", &_last_gnss_moment, "test hook: the moment, the priors moved and the report of the last moment stage; {} when it did not run");
     m.def("_last_merged", &_last_merged, "test hook: points and stamps of the last RTKM frame");
     m.def("_gnss_state", &_gnss_state, "test hook: the state of the GNSS side");
     m.def("set_loop_config", &set_loop_config, "LoopDetector thresholds", py::arg("dict"));

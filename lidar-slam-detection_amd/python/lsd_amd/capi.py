@@ -71,6 +71,7 @@ SYMBOLS = [
     "lio_graph_chi2", "lio_graph_linearize", "lio_graph_last_times", "lio_se3_from_mqt", "lio_se3_to_mqt", "lio_graph_edge_error",
     "lio_graph_add_prior", "lio_graph_set_kernel", "lio_graph_priors", "lio_graph_prior_error", "lio_graph_remove_gnss_outliers",
     "lio_graph_remove_node", "lio_graph_node_live", "lio_graph_edge_records", "lio_loop_retire",
+    "lio_graph_estimate_gnss_moment", "lio_graph_moment_begin", "lio_graph_moment_end", "lio_graph_moment_get", "lio_graph_moment_linearize",
     "lio_render_create", "lio_render_destroy", "lio_render_clear", "lio_render_set_cameras", "lio_render_set_active", "lio_render_frame", "lio_render_size",
     "lio_render_download", "lio_render_download_voxels", "lio_render_download_points", "lio_render_download_last_image", "lio_render_last_times",
     "lio_utm_create", "lio_utm_destroy", "lio_utm_zone", "lio_utm_forward", "lio_utm_inverse", "lio_utm_longitude0", "lio_grid_convergence",
@@ -614,6 +615,11 @@ def lib():
     sig("lio_graph_remove_node", cint, vp, cint)
     sig("lio_graph_node_live", cint, vp, u8p, u32)
     sig("lio_graph_edge_records", cint, vp, i32p, i32p, i32p, f64p, f64p, i32p, f64p, u32)
+    sig("lio_graph_estimate_gnss_moment", cint, vp, dbl, cint, f64p, f64p, gr)
+    sig("lio_graph_moment_begin", cint, vp, f64p, f64p)
+    sig("lio_graph_moment_end", cint, vp, cint)
+    sig("lio_graph_moment_get", cint, vp, f64p)
+    sig("lio_graph_moment_linearize", cint, vp, f64p, f64p, f64p, u32)
     sig("lio_loop_retire", cint, vp, cint)
     sig("lio_render_create", vp, cint, u64, u64)
     sig("lio_render_destroy", None, vp)

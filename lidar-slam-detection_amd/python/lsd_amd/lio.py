@@ -1209,6 +1209,43 @@ class PoseGraph:
         d["stop"] = self.STOPS.get(rep.stop_reason, str(rep.stop_reason))
         return [int(x) for x in ids[:n]], d
 
+    def _report(self, rep):
+        d = {k: getattr(rep, k) for k, _ in capi.GraphReport._fields_}
+        d["lambda"] = d.pop("lambda_")
+        d["stop"] = self.STOPS.get(rep.stop_reason, str(rep.stop_reason))
+        return d
+
+    def estimate_gnss_moment(self, max_distance_error=1.0, max_iterations=1024, prior_information=None):
+        """the GNSS moment stage -> (the number of XYZ priors re-anchored, the moment (3,), the stage's report); (0, zeros, {}) with nothing
+        touched when there is no live XYZ prior.  With fixes z = t + R l the moment comes out near -l"""
+        W = f64(prior_information).reshape(3, 3) if prior_information is not None else None
+        m, rep = np.zeros(3), capi.GraphReport()
+        n = check(lib().lio_graph_estimate_gnss_moment(self.h, float(max_distance_error), int(max_iterations), ptr(W, C.c_double) if W is not None else None,
+                                                       ptr(m, C.c_double), C.byref(rep)), "graph estimate_gnss_moment")
+        return n, m, (self._report(rep) if n else {})
+
+    def moment_begin(self, m0=None, prior_information=None):
+        """opens the moment stage: until moment_end, optimize / chi2 / linearize run over the bordered system"""
+        m = f64(m0).ravel() if m0 is not None else None
+        W = f64(prior_information).reshape(3, 3) if prior_information is not None else None
+        check(lib().lio_graph_moment_begin(self.h, ptr(m, C.c_double) if m is not None else None, ptr(W, C.c_double) if W is not None else None), "graph moment_begin")
+
+    def moment_end(self, apply=True):
+        """closes the stage; apply: every live XYZ prior's measurement moves to z + R m -> their number"""
+        return check(lib().lio_graph_moment_end(self.h, int(bool(apply))), "graph moment_end")
+
+    def moment(self):
+        m = np.zeros(3)
+        check(lib().lio_graph_moment_get(self.h, ptr(m, C.c_double)), "graph moment")
+        return m
+
+    def linearize_moment(self):
+        """one linearisation of the open stage -> b_m (3,), H_mm (3, 3), H_pm (N, 6, 3): zeros for a node that is fixed or has no moment edge"""
+        N = self.num_nodes
+        bm, Hmm, Hpm = np.zeros(3), np.zeros((3, 3)), np.zeros((max(N, 1), 6, 3))
+        check(lib().lio_graph_moment_linearize(self.h, ptr(bm, C.c_double), ptr(Hmm, C.c_double), ptr(Hpm, C.c_double), len(Hpm)), "graph moment_linearize")
+        return bm, Hmm, Hpm[:N]
+
     @property
     def num_nodes(self):
         return check(lib().lio_graph_num_nodes(self.h), "graph num_nodes")
