@@ -92,8 +92,10 @@ int lio_device_count(void);
  * 24 = lio_calib_* / lio_se3f_* / lio_dfo_* (the lidar-INS calibration: Scan's subsampling, the f32 Transform, the odometry interpolation and
  *      two derivative-free minimisers on the host; the capped k-NN cost of all key scans and Aligner::lidarOdomTransform on the device).
  * 25 = lio_graph_estimate_gnss_moment / lio_graph_moment_begin / _end / _get / _linearize (the GNSS moment stage of robust_graph_optimize's mode
- *      `mapping`: one shared 3-DoF vertex, the offset between the antenna and the lidar frame, bordered onto the pose graph's system). */
-#define LIO_ABI_VERSION 25
+ *      `mapping`: one shared 3-DoF vertex, the offset between the antenna and the lidar frame, bordered onto the pose graph's system).
+ * 26 = lio_calib_ground_* (the lidar ground calibration: the polygon crop, fit_plane's RANSAC scored a batch of planes per pass over the
+ *      points, the loop replayed on the host). */
+#define LIO_ABI_VERSION 26
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -2005,6 +2007,75 @@ int lio_calib_ins_progress(lio_calib_ins*, int32_t* evals, double* best_err, int
 int lio_calib_ins_result(lio_calib_ins*, float T[16]);
 /* device time (HIP events) of the last evaluation */
 int lio_calib_ins_last_times(lio_calib_ins*, double* assemble_us, double* build_us, double* terms_us);
+
+/* -------------------------------------------------------------------------------------------------------------
+ * Lidar ground calibration on the device (csrc/calib_ground.hip): crop_points / test_point_in_polygon of calibration/lidar_calibration/
+ * filter.py and is_colinear / get_plane_coefficient / fit_plane of fit.py, as calibration.py:calibrate_ground reaches them through
+ * align_points_to_xyplane.  The rules are restated here; where the reference cannot be followed the rule is THE PROJECT'S and is marked so.
+ * NULL from lio_calib_ground_create without a device: there is no CPU fallback.
+ *   crop     everything in f64, the point's x and y widened from f32, the polygon's vertices f64 pairs.  Edge e runs from vertex p = e to
+ *            q = e + 1, the last one back to vertex 0.  `up` is the vertex of the two with the strictly larger y, on equal y up = q; `down`
+ *            is the other.  The edge counts iff down.y < y and y < up.y (both strict) and xi > x with
+ *              xi = down.x + ((up.x - down.x) * (y - down.y)) / (up.y - down.y)            (in exactly this order, no fused multiply-add).
+ *            A point is kept iff the number of counting edges is odd; a NaN x or y therefore drops the point, a NaN z does not.  The kept
+ *            points keep their input order.  PROJECT: at most LIO_CALIB_GROUND_MAX_VERTICES vertices (the reference has no limit).
+ *   planes   for a triple (i, j, k) into the cropped cloud, p1 = point i, p2 = point j, p3 = point k, all f32, every operation rounded to
+ *            nearest on its own: u = p2 - p1, v = p3 - p1,
+ *              a = u.y*v.z - v.y*u.z;  b = u.z*v.x - v.z*u.x;  c = u.x*v.y - v.x*u.y;
+ *            colinear iff (|a| + |b|) + |c| < (float)1e-5;  norm = sqrtf((a*a + b*b) + c*c);  d = -((a*p1.x + b*p1.y) + c*p1.z);
+ *            the plane is (a, b, c, d) / norm, all four negated when !(c > 0).  A colinear attempt has no plane (NaN in the log).
+ *   score    the count of a plane is the number of cropped points with |((a*x + b*y) + c*z) + d| < (float)sigma in f32; a NaN distance
+ *            does not count.  The device scores up to 128 attempts in one pass over the points.
+ *   loop     fit_plane's, replayed on the host over the counts, attempts consumed in order: a colinear attempt is skipped and costs no
+ *            iteration; an accepted attempt is one iteration: if (double)count > thresh * (double)n that plane wins and the loop ends (early
+ *            exit), else a count strictly larger than the best so far (which starts at 0) makes it the best, the first of equal counts
+ *            staying; the loop ends after num_iteration iterations.  Nothing found: every accepted count was 0, or every attempt colinear.
+ *   draws    PROJECT (np.random.choice on numpy's global generator cannot be restated): attempt j is lio_ground_draw(seed, j, n), or, when
+ *            the caller gives triples, triple j of that list; when the list is used up the loop ends with what it has.
+ *            PROJECT: the loop gives up after 11 * num_iteration attempts (the reference loops forever over a cloud whose triples are all
+ *            colinear).
+ *   above    the ABI, in lsd_amd/calib_lidar.py (host, f64): the transform is the Rodrigues rotation of (a, b, c) onto (0, 0, 1) and the
+ *            translation (0, 0, d / c), the quotient in f64 of the f32 coefficients.  PROJECT: parallel vectors give the identity (the
+ *            reference divides 0 by 0 and returns NaN); ValueError names the reason for no plane found, fewer than 3 cropped points, fewer
+ *            than 3 vertices and a winning plane with c == 0 (the reference fails by accident or answers with non-finite numbers).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define LIO_CALIB_GROUND_MAX_VERTICES 256
+typedef struct lio_calib_ground lio_calib_ground;
+typedef struct lio_calib_ground_params {
+    double sigma;          /* 0.05, compared as f32 */
+    int32_t num_iteration; /* 100; 1 .. 10^6 */
+    double thresh;         /* 0.9: the share of the cropped points that ends the loop early */
+    uint32_t seed;         /* of the draws */
+} lio_calib_ground_params;
+/* the values align_points_to_xyplane passes (calib.py:25-27), seed 0 */
+void lio_calib_ground_default_params(lio_calib_ground_params*);
+lio_calib_ground* lio_calib_ground_create(int device);
+void lio_calib_ground_destroy(lio_calib_ground*);
+/* crop_points: n host points, stride_floats (>= 3) apart, x y z first, against the polygon of n_vertices (x, y) f64 pairs; the handle then
+ * holds the kept points and *n_kept (may be NULL) their number, which may be 0.  LIO_E_INVALID for fewer than 3 or more than
+ * LIO_CALIB_GROUND_MAX_VERTICES vertices or a stride below 3: nothing is touched, the previous crop stays downloadable */
+int lio_calib_ground_crop_host(lio_calib_ground*, const float* xyz, uint64_t n, uint32_t stride_floats, const double* poly_xy, int n_vertices,
+                               uint32_t* n_kept);
+/* adopts a cloud as already cropped (fit_plane on its own): every point is held, position i is i */
+int lio_calib_ground_set_points_host(lio_calib_ground*, const float* xyz, uint64_t n, uint32_t stride_floats);
+/* fit_plane over the points the handle holds.  params NULL = the defaults.  triples NULL: the seeded draws; else n_triples x 3 indices into
+ * the held points, consumed in order.  *found = 1 and coef = (a, b, c, d) of the winner, or *found = 0 and zeros (fit_plane's np.zeros(4)).
+ * LIO_E_INVALID, the handle and the log of the last fit as they were: fewer than 3 points held, num_iteration outside 1 .. 10^6, a triple
+ * with an index out of range or repeated */
+int lio_calib_ground_fit(lio_calib_ground*, const lio_calib_ground_params* params, const uint32_t* triples, uint64_t n_triples, int* found,
+                         float coef[4]);
+/* each returns the number of items, or -(items) when cap is too small.  indices: the kept points' positions in the cropped cloud's input,
+ * ascending; points: the held points, n x 3; draws: every attempt the device scored in the last fit (lio_calib_ground_last_run tells how many
+ * the loop consumed): its triple, 1 if colinear, its count (0 if colinear) and its plane (NaN if colinear); any of the four may be NULL */
+int64_t lio_calib_ground_download_indices(lio_calib_ground*, uint32_t* out, uint64_t cap);
+int64_t lio_calib_ground_download_points(lio_calib_ground*, float* xyz, uint64_t cap);
+int64_t lio_calib_ground_download_draws(lio_calib_ground*, uint32_t* triples, uint32_t* colinear, uint32_t* counts, float* planes, uint64_t cap);
+/* the replay of the last fit: iterations (accepted attempts), attempts consumed, colinear attempts skipped, the winning attempt (-1: none) and
+ * whether it won by the early exit */
+int lio_calib_ground_last_run(lio_calib_ground*, int* iterations, int* attempts, int* skipped, int* winner, int* early_exit);
+/* device time (HIP events on the handle's stream): the last crop's two kernels and scan; the last fit from its first launch to its last copy
+ * (the host's replay between the batches included), and within it the plane and the score kernels summed over the batches */
+int lio_calib_ground_last_times(lio_calib_ground*, double* crop_us, double* fit_us, double* planes_us, double* score_us);
 
 #ifdef __cplusplus
 }

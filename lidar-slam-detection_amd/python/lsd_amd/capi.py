@@ -87,6 +87,9 @@ SYMBOLS = [
     "lio_calib_ins_create", "lio_calib_ins_destroy", "lio_calib_ins_reset", "lio_calib_ins_add_scan", "lio_calib_ins_add_odom", "lio_calib_ins_counts",
     "lio_calib_ins_set_transform", "lio_calib_ins_scan_matrices", "lio_calib_ins_combined", "lio_calib_ins_error", "lio_calib_ins_error_terms",
     "lio_calib_ins_calibrate", "lio_calib_ins_progress", "lio_calib_ins_result", "lio_calib_ins_last_times",
+    "lio_calib_ground_default_params", "lio_calib_ground_create", "lio_calib_ground_destroy", "lio_calib_ground_crop_host",
+    "lio_calib_ground_set_points_host", "lio_calib_ground_fit", "lio_calib_ground_download_indices", "lio_calib_ground_download_points",
+    "lio_calib_ground_download_draws", "lio_calib_ground_last_run", "lio_calib_ground_last_times",
 ]
 ABI_VERSION = 22  # kept at 22 for callers that compare against it; the revision the binding needs is ABI_REQUIRED
 ABI_REQUIRED = 23  # the oldest library revision that has every symbol above; lib() refuses an older one
@@ -282,6 +285,12 @@ class CalibParams(C.Structure):  # lio_calib_params
                 ("knn_batch_size", C.c_int32), ("xtol", C.c_double), ("local_knn_k", C.c_int32), ("global_knn_k", C.c_int32),
                 ("local_knn_max_dist", C.c_float), ("global_knn_max_dist", C.c_float), ("direct_epsilon", C.c_double), ("nm_step", C.c_double * 7)]
 
+
+class CalibGroundParams(C.Structure):  # lio_calib_ground_params
+    _fields_ = [("sigma", C.c_double), ("num_iteration", C.c_int32), ("thresh", C.c_double), ("seed", C.c_uint32)]
+
+
+CALIB_GROUND_MAX_VERTICES = 256  # LIO_CALIB_GROUND_MAX_VERTICES
 
 DFO_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_int, C.c_void_p)  # lio_dfo_fn
 DFO_HOOK = C.CFUNCTYPE(C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_void_p)  # lio_dfo_hook
@@ -703,6 +712,18 @@ def lib():
     sig("lio_calib_ins_progress", cint, vp, i32p, f64p, i32p)
     sig("lio_calib_ins_result", cint, vp, f32p)
     sig("lio_calib_ins_last_times", cint, vp, f64p, f64p, f64p)
+    cgp, cip = C.POINTER(CalibGroundParams), C.POINTER(cint)
+    sig("lio_calib_ground_default_params", None, cgp)
+    sig("lio_calib_ground_create", vp, cint)
+    sig("lio_calib_ground_destroy", None, vp)
+    sig("lio_calib_ground_crop_host", cint, vp, f32p, u64, u32, f64p, cint, u32p)
+    sig("lio_calib_ground_set_points_host", cint, vp, f32p, u64, u32)
+    sig("lio_calib_ground_fit", cint, vp, cgp, u32p, u64, cip, f32p)
+    sig("lio_calib_ground_download_indices", i64, vp, u32p, u64)
+    sig("lio_calib_ground_download_points", i64, vp, f32p, u64)
+    sig("lio_calib_ground_download_draws", i64, vp, u32p, u32p, u32p, f32p, u64)
+    sig("lio_calib_ground_last_run", cint, vp, cip, cip, cip, cip, cip)
+    sig("lio_calib_ground_last_times", cint, vp, f64p, f64p, f64p, f64p)
     _lib = L
     return L
 

@@ -2860,3 +2860,108 @@ class InsCalib:
         a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
         check(lib().lio_calib_ins_last_times(self.h, C.byref(a), C.byref(b), C.byref(c)), "calib times")
         return a.value, b.value, c.value
+
+
+class GroundCalib:
+    """lio_calib_ground: the lidar ground calibration's crop_points and fit_plane (calibration/lidar_calibration/filter.py, fit.py) on the
+    device; include/lio_hip.h states every rule.  crop() or set_points() gives the handle its cloud, fit() replays fit_plane's loop over counts
+    the device scored a batch of planes at a time.  The draws are this project's (`lio_ground_draw` of (seed, attempt)) or the caller's list."""
+
+    MAX_VERTICES = capi.CALIB_GROUND_MAX_VERTICES
+
+    def __init__(self, device=0):
+        self.h = lib().lio_calib_ground_create(device)
+        if not self.h:
+            raise capi.LioError("lio_calib_ground_create failed: " + lib().lio_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_calib_ground_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def params(**over):
+        """lio_calib_ground_params (sigma 0.05, num_iteration 100, thresh 0.9, seed 0), fields overridden by name"""
+        p = capi.CalibGroundParams()
+        lib().lio_calib_ground_default_params(C.byref(p))
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise ValueError(f"lio_calib_ground_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _cloud(points):
+        pts = f32(points)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError("points: n x (3 or more) is required")
+        return pts
+
+    def crop(self, points, polygon):
+        """crop_points: the number of the n x (>= 3) f32 points that lie inside the polygon (m x 2, taken as f64); they stay on the device"""
+        pts, poly = self._cloud(points), f64(np.asarray(polygon, np.float64).reshape(-1, 2))
+        n = C.c_uint32(0)
+        check(lib().lio_calib_ground_crop_host(self.h, ptr(pts, C.c_float), len(pts), pts.shape[1], ptr(poly, C.c_double), len(poly), C.byref(n)),
+              "calib ground crop")
+        return int(n.value)
+
+    def set_points(self, points):
+        """adopts n x (>= 3) f32 points as already cropped"""
+        pts = self._cloud(points)
+        check(lib().lio_calib_ground_set_points_host(self.h, ptr(pts, C.c_float), len(pts), pts.shape[1]), "calib ground set_points")
+        return len(pts)
+
+    def fit(self, params=None, draws=None):
+        """fit_plane over the held points: (found, coef f32[4]); draws None: the seeded draws, else m x 3 indices consumed in order"""
+        p = params if params is not None else self.params()
+        found, co = C.c_int(0), np.zeros(4, np.float32)
+        if draws is None:
+            tp, nt = None, 0
+        else:
+            d = np.asarray(draws).reshape(-1, 3)
+            if d.size and (d.min() < 0 or d.max() > 0xFFFFFFFF):
+                raise ValueError("draws: indices outside 0 .. 2^32 - 1")
+            t = np.ascontiguousarray(d, dtype=np.uint32)
+            keep = np.zeros(3, np.uint32)  # a pointer even for an empty list: NULL means the seeded draws
+            tp, nt = ptr(t if len(t) else keep, C.c_uint32), len(t)
+        check(lib().lio_calib_ground_fit(self.h, C.byref(p), tp, nt, C.byref(found), ptr(co, C.c_float)), "calib ground fit")
+        return bool(found.value), co
+
+    def indices(self):
+        """positions in the cropped cloud's input of the kept points, ascending"""
+        n = max(-lib().lio_calib_ground_download_indices(self.h, None, 0), 0)
+        out = np.zeros(n, np.uint32)
+        if n > 0:
+            check(int(lib().lio_calib_ground_download_indices(self.h, ptr(out, C.c_uint32), n)), "calib ground indices")
+        return out
+
+    def points(self):
+        """the held points, n x 3 f32"""
+        n = max(-lib().lio_calib_ground_download_points(self.h, None, 0), 0)
+        out = np.zeros((n, 3), np.float32)
+        if n > 0:
+            check(int(lib().lio_calib_ground_download_points(self.h, ptr(out, C.c_float), n)), "calib ground points")
+        return out
+
+    def draws(self):
+        """(triples n x 3 u32, colinear n bool, counts n u32, planes n x 4 f32 (NaN where colinear)) of every attempt the last fit scored"""
+        n = max(-lib().lio_calib_ground_download_draws(self.h, None, None, None, None, 0), 0)
+        t, col, c, pl = np.zeros((n, 3), np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 4), np.float32)
+        if n > 0:
+            check(int(lib().lio_calib_ground_download_draws(self.h, ptr(t, C.c_uint32), ptr(col, C.c_uint32), ptr(c, C.c_uint32), ptr(pl, C.c_float), n)),
+                  "calib ground draws")
+        return t, col.astype(bool), c, pl
+
+    def last_run(self):
+        """dict(iterations, attempts, skipped, winner, early_exit) of fit_plane's loop as the last fit replayed it"""
+        v = [C.c_int(0) for _ in range(5)]
+        check(lib().lio_calib_ground_last_run(self.h, *[C.byref(x) for x in v]), "calib ground last_run")
+        return dict(iterations=v[0].value, attempts=v[1].value, skipped=v[2].value, winner=v[3].value, early_exit=bool(v[4].value))
+
+    def last_times(self):
+        """(crop_us, fit_us, planes_us, score_us): device time of the last crop, of the last fit, and of its plane and score kernels"""
+        v = [C.c_double(0) for _ in range(4)]
+        check(lib().lio_calib_ground_last_times(self.h, *[C.byref(x) for x in v]), "calib ground times")
+        return tuple(x.value for x in v)
