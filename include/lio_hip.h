@@ -94,8 +94,10 @@ int lio_device_count(void);
  * 25 = lio_graph_estimate_gnss_moment / lio_graph_moment_begin / _end / _get / _linearize (the GNSS moment stage of robust_graph_optimize's mode
  *      `mapping`: one shared 3-DoF vertex, the offset between the antenna and the lidar frame, bordered onto the pose graph's system).
  * 26 = lio_calib_ground_* (the lidar ground calibration: the polygon crop, fit_plane's RANSAC scored a batch of planes per pass over the
- *      points, the loop replayed on the host). */
-#define LIO_ABI_VERSION 26
+ *      points, the loop replayed on the host).
+ * 27 = lio_calib_imu_* (the lidar-IMU calibration: gyro integration, time alignment and the quaternion hand-eye solve on the host; the tool's
+ *      own lidar odometry -- voxel filter, FAST_VGICP against a local map that stays in HBM -- on the device). */
+#define LIO_ABI_VERSION 27
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -2076,6 +2078,76 @@ int lio_calib_ground_last_run(lio_calib_ground*, int* iterations, int* attempts,
 /* device time (HIP events on the handle's stream): the last crop's two kernels and scan; the last fit from its first launch to its last copy
  * (the host's replay between the batches included), and within it the plane and the score kernels summed over the batches */
 int lio_calib_ground_last_times(lio_calib_ground*, double* crop_us, double* fit_us, double* planes_us, double* score_us);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Lidar-IMU calibration: the IMU's mounting rotation from gyroscope samples and lidar rotations -- the reference's CalibLidarImu
+ * (sensor_driver/calibration/lidar_imu/src/calib_lidar_imu.cpp) behind calib_imu_* (calib_wrapper.cpp:131-251).
+ *
+ * Host half (f64, no device; quaternions are (w, x, y, z); Eigen's rules restated, csrc/calib_imu_host.cpp):
+ *   integrate    calib():291-301: rot[0] = I, rot[i] = rot[i-1] * (1, a/2), a = (g[i-1] + g[i]) / 2 * (t[i] - t[i-1]); neither the increment
+ *                nor the product is normalised
+ *   interpolate  getInterpolatedAttitude: scale == 0 or > 1 gives the identity; else q_s^-1 q_e normalised -> angle-axis -> the scaled angle
+ *                through a rotation matrix back to a quaternion -> q_s * that, normalised
+ *   time_align   calib():303-346: frames stamped before the first IMU sample are erased (*first_kept = how many); the walking IMU iterator
+ *                (first sample not before the frame, one step back unless at the begin, kept across frames) gives the pair to interpolate
+ *                between; the loop stops at the first frame whose second sample does not exist.  Frames first_kept .. first_kept +
+ *                n_aligned - 1 get an attitude (quat_wxyz_out, n_frames x 4 is enough).  n_imu == 0: LIO_E_STATE
+ *   solve        pairs: n x 8 (q_lidar, q_imu).  Each pair a 4 x 4 block huber * (L(q_imu) - R(q_lidar)), huber = 2 / angle_deg where
+ *                angularDistance in degrees is above 2, else 1; the answer is the right singular vector of the smallest singular value of
+ *                the 4n x 4 matrix (one-sided Jacobi on the matrix itself: the condition number is not squared).  Its sign is free: compare
+ *                rotation matrices.  n == 0: the identity
+ * The object:
+ *   create       never touches the device: it is opened by the first call that handles a cloud (lio_calib_imu_lidar_pose, or add_frame with
+ *                the flag set); LIO_E_DEVICE there when there is none (no CPU fallback).  max_scan_points bounds one frame, max_map_points
+ *                the local map
+ *   add_imu      n rows of 7 doubles (stamp us, gyro deg/s x 3, acc g x 3): / 1e6, / 180 * pi, * 9.81
+ *   add_frame    addLidarData: (stamp / 1e6, global_T, delta_T) joins the frames; ignored (LIO_OK) from the 200th frame on.  With the "no RTK"
+ *                flag set (lidar_pose was called) the rows are moved by global_T (f64, terms left to right, cast to f32: lio_cloud_append_*'s
+ *                rule), filtered at 0.2 and appended to the map; the WHOLE map is filtered at 0.2 out of place into the target staging (the
+ *                map itself is never replaced) and handed to lio_gicp_set_target_device.  Flag set and no map yet (the reference
+ *                dereferences null): LIO_E_STATE.  More than max_scan_points rows, or a map past max_map_points: LIO_E_CAPACITY.  A point
+ *                that is not finite: LIO_E_INVALID.  A refused call leaves the object as it was (the frame is not added either).  Without
+ *                the flag (the RTK path) rows are not read and may be NULL
+ *   lidar_pose   get_lidar_T_R: sets the flag.  n == 0: I and nothing else.  A kernel stages the strided rows (x y z intensity first,
+ *                stride_floats >= 4) as float4 and counts the points whose x, y or z is not finite: any -> LIO_E_INVALID, nothing changed, the
+ *                flag included.  The frame is filtered at 0.2 (lio_scan_voxel_downsample's semantics, intensity averaged).  First call: the map
+ *                and the target are the RAW scan, the last pose and the answer are I.  Later: the filtered scan is the source
+ *                (lio_gicp_set_source_device's rules: fewer than 20 points LIO_E_INVALID), the guess is the last pose rounded to f32,
+ *                FAST_VGICP (voxel mode 1.0, DIRECT1, lio_estimate_matcher_params); not converged: I and the last pose stays; converged: the
+ *                answer and the last pose are the result rounded to f32 (getFinalTransformation is a Matrix4f).  out_T row-major.
+ *                No cloud crosses the link between the upload of the rows and out_T; the host reads back counts (the finite check, the
+ *                filter's grid and voxel count) and the matcher's own round records
+ *   calibrate    calib(true): integrate, time_align, pairs from delta_T's rotation of aligned frame i and the attitudes i-1, i, solve; R = the
+ *                normalised result's matrix, row-major 3 x 3.  A second call without reset appends the aligned pairs again; erased frames
+ *                stay erased.  No IMU sample, or no frame left: LIO_E_STATE (the reference reads past the end), R untouched
+ *   lidar_poses / imu_poses  getLidarPose / getImuPose: the running products over the aligned frames from the second on, 16 doubles each;
+ *                they return the number of poses, or -(poses) when cap is too small
+ *   map_download / target_download  test visibility: the map in append order; the matcher's target in lio_gicp_download's internal order
+ *   counts       frames held, IMU samples, aligned entries, map points, target points, the flag
+ *   last_times   HIP events: staging, frame filter and matcher (set_source + align) of the last lidar_pose; the map update of the last add_frame
+ *   set_max_iterations  a test hook: the matcher's iteration limit (64)
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct lio_calib_imu lio_calib_imu;
+int lio_calib_imu_integrate(const double* stamps_s, const double* gyr_rad, uint32_t n, double* quat_wxyz_out);
+int lio_calib_imu_interpolate(const double q_s[4], const double q_e[4], double scale, double out[4]);
+int lio_calib_imu_time_align(const double* imu_stamps_s, const double* imu_quat_wxyz, uint32_t n_imu, const double* frame_stamps_s, uint32_t n_frames,
+                             uint32_t* first_kept, uint32_t* n_aligned, double* quat_wxyz_out);
+int lio_calib_imu_solve(const double* pairs, uint32_t n, double quat_wxyz_out[4]);
+lio_calib_imu* lio_calib_imu_create(int device, uint32_t max_scan_points, uint32_t max_map_points);
+void lio_calib_imu_destroy(lio_calib_imu*);
+int lio_calib_imu_reset(lio_calib_imu*);
+int lio_calib_imu_add_imu(lio_calib_imu*, const double* rows7, uint32_t n);
+int lio_calib_imu_add_frame(lio_calib_imu*, uint64_t stamp_us, const float* rows, uint32_t n, uint32_t stride_floats, const double global_T[16],
+                            const double delta_T[16]);
+int lio_calib_imu_lidar_pose(lio_calib_imu*, const float* rows, uint32_t n, uint32_t stride_floats, double out_T[16]);
+int lio_calib_imu_calibrate(lio_calib_imu*, double R[9]);
+int64_t lio_calib_imu_lidar_poses(lio_calib_imu*, double* out, uint64_t cap);
+int64_t lio_calib_imu_imu_poses(lio_calib_imu*, double* out, uint64_t cap);
+int64_t lio_calib_imu_map_download(lio_calib_imu*, float* xyzi, uint64_t cap);
+int64_t lio_calib_imu_target_download(lio_calib_imu*, float* xyzi, uint64_t cap);
+int lio_calib_imu_counts(lio_calib_imu*, uint32_t* frames, uint32_t* imus, uint32_t* aligned, uint32_t* map_points, uint32_t* target_points, int* no_rtk);
+int lio_calib_imu_last_times(lio_calib_imu*, double* stage_us, double* filter_us, double* align_us, double* map_update_us);
+int lio_calib_imu_set_max_iterations(lio_calib_imu*, int max_iterations);
 
 #ifdef __cplusplus
 }

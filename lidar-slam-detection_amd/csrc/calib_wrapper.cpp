@@ -1,7 +1,7 @@
 // calib_wrapper.cpp -- the reference's outer boundary of the lidar-INS calibration: the pybind11 module `calib_driver_ext` with the six
 // calib_ins_* functions of sensor_driver/calibration/calib_wrapper.cpp:41-115 (names, argument names, behaviour), over the C ABI's
-// lio_calib_ins_* (include/lio_hip.h).  The seven calib_imu_* names of the reference's module are NOT defined: that is the lidar-IMU
-// calibration, which this project does not have; a missing name is more honest than a no-op.
+// lio_calib_ins_* (include/lio_hip.h).  The seven calib_imu_* names of the reference's module are NOT defined here: the lidar-IMU
+// calibration has a module of its own, calib_imu_ext (calib_imu_wrapper.cpp).
 //
 //   calib_ins_reset                      joins a running optimisation, drops scans and odometry, current = best = Transform(initArray)
 //   calib_ins_set_points                 ignored with a warning while an optimisation thread exists; ignored from the 21st scan on; N x >= 3

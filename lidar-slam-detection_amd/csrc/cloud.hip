@@ -681,6 +681,80 @@ int cloud_append(lio_cloud* c, const float4* in, uint64_t n, const XformArgs& a)
 
 }  // namespace
 
+namespace lio {
+namespace cloud {
+
+uint64_t voxel_filter_words(uint64_t n) { return n ? vg_layout(n).total : 0; }
+
+// the launches of lio_cloud_voxel_downsample over n points at `in` (1 <= n <= 2^31 - 1), the centroids written to `out`: `in` itself (the
+// in-place form: the points are read from the sorted copy only) or another buffer of n points, in which case `in` is left as it was
+// (lio_calib_imu's target staging).  PCL's overflow guard returns the input: out of place that is a device-to-device copy.  The last
+// launches are enqueued, not waited for; the two words the host needs (the grid, the voxel count) are.
+int voxel_filter(hipStream_t st, const float4* in, uint32_t n, float leaf, float4* out, uint32_t* base, uint64_t* n_out) {
+    const float inv = 1.0f / leaf;
+    const uint32_t ntiles = (uint32_t)tiles_of(n);
+    const VgLayout L = vg_layout(n);
+    uint32_t *ka = base + L.keys_a, *kb = base + L.keys_b, *va = base + L.vals_a, *vb = base + L.vals_b, *table = base + L.table, *aux = base + L.aux;
+    float4* sorted = reinterpret_cast<float4*>(base + L.sorted);
+    Grid* g = reinterpret_cast<Grid*>(base + L.grid);
+    const uint64_t tab = 256ull * ntiles;
+    Grid hg;
+    uint64_t result = n;
+    {
+        const uint32_t nb = std::min<uint32_t>(ntiles, kBboxBlocks);
+        cl_bbox_part<<<dim3(nb), dim3(kThreads), 0, st>>>(in, n, base + L.parts);
+        cl_bbox_fold<<<dim3(1), dim3(kThreads), 0, st>>>(base + L.parts, nb, inv, g);
+        LIO_HIP_TRY(hipGetLastError());
+        LIO_HIP_TRY(hipMemcpyAsync(&hg, g, sizeof(Grid), hipMemcpyDeviceToHost, st));
+        LIO_HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (hg.pass) {
+        result = n;  // PCL's overflow guard: the output is the input, non-finite points included
+        if (out != in) LIO_HIP_TRY(hipMemcpyAsync(out, in, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    } else if (hg.n_valid == 0) {
+        result = 0;
+    } else {
+        const int passes = (int)((hg.nbits + 7u) >> 3);
+        cl_keys<<<dim3(ntiles), dim3(kThreads), 0, st>>>(in, n, inv, g, ka, va, table, ntiles);
+        LIO_HIP_TRY(hipGetLastError());
+        for (int p = 0; p < passes; p++) {
+            const uint32_t* kin = (p & 1) ? kb : ka;
+            const uint32_t* vin = (p & 1) ? vb : va;
+            uint32_t* kout = (p & 1) ? ka : kb;
+            uint32_t* vout = (p & 1) ? va : vb;
+            if (p > 0) cl_hist<<<dim3(ntiles), dim3(kThreads), 0, st>>>(kin, n, 8 * p, table, ntiles);
+            const int rc = exclusive_scan(st, table, tab, aux);
+            if (rc != LIO_OK) return rc;
+            cl_scatter<<<dim3(ntiles), dim3(kThreads), 0, st>>>(kin, vin, kout, vout, n, 8 * p, table, ntiles);
+            LIO_HIP_TRY(hipGetLastError());
+        }
+        const bool odd = passes & 1;
+        const uint32_t* keys = odd ? kb : ka;
+        const uint32_t* vals = odd ? vb : va;
+        uint32_t* hpos = odd ? ka : kb;     // the free key buffer (n + 1 words)
+        uint32_t* longlist = odd ? va : vb;  // the free value buffer (n words)
+        cl_head_count<<<dim3(ntiles), dim3(kThreads), 0, st>>>(keys, n, hg.total, table);
+        const uint32_t* d_nvox = compact_finish(st, table, n);
+        if (!d_nvox) return LIO_E_DEVICE;
+        cl_head_write<<<dim3(ntiles), dim3(kThreads), 0, st>>>(in, keys, vals, n, hg.n_valid, hg.total, table, ntiles, hpos, sorted);
+        LIO_HIP_TRY(hipGetLastError());
+        uint32_t nvox = 0;
+        LIO_HIP_TRY(hipMemcpyAsync(&nvox, d_nvox, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        LIO_HIP_TRY(hipStreamSynchronize(st));
+        if (nvox) {
+            cl_centroid<<<dim3((nvox + kThreads - 1) / kThreads), dim3(kThreads), 0, st>>>(sorted, hpos, nvox, out, longlist, g);
+            cl_long<<<dim3(kLongBlocks), dim3(64), 0, st>>>(sorted, hpos, longlist, g, out);
+            LIO_HIP_TRY(hipGetLastError());
+        }
+        result = nvox;
+    }
+    *n_out = result;
+    return LIO_OK;
+}
+
+}  // namespace cloud
+}  // namespace lio
+
 extern "C" {
 
 lio_cloud* lio_cloud_create(int device, uint64_t reserve_points) {
@@ -768,88 +842,22 @@ int lio_cloud_voxel_downsample(lio_cloud* c, float leaf, uint64_t* n_out) {
         if (n_out) *n_out = 0;
         return LIO_OK;
     }
-    const float inv = 1.0f / leaf;
-    const uint32_t ntiles = (uint32_t)tiles_of(n);
-    const VgLayout L = vg_layout(n);
+    const uint64_t words = voxel_filter_words(n);
     uint32_t* base = nullptr;
-    if (hipMalloc(&base, L.total * sizeof(uint32_t)) != hipSuccess) {
+    if (hipMalloc(&base, words * sizeof(uint32_t)) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("lio_cloud_voxel_downsample: %llu bytes of sort scratch not available", (unsigned long long)(L.total * sizeof(uint32_t)));
+        set_error("lio_cloud_voxel_downsample: %llu bytes of sort scratch not available", (unsigned long long)(words * sizeof(uint32_t)));
         return LIO_E_DEVICE;
     }
-    uint32_t *ka = base + L.keys_a, *kb = base + L.keys_b, *va = base + L.vals_a, *vb = base + L.vals_b, *table = base + L.table, *aux = base + L.aux;
-    float4* sorted = reinterpret_cast<float4*>(base + L.sorted);
-    Grid* g = reinterpret_cast<Grid*>(base + L.grid);
-    const uint64_t tab = 256ull * ntiles;
-    int rc = LIO_OK;
-    Grid hg;
     uint64_t result = n;
-    auto fail = [&](int r) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(base);
-        return r;
-    };
-#define CL_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e__));           \
-            return fail(LIO_E_DEVICE);                                                                 \
-        }                                                                                              \
-    } while (0)
-    CL_TRY(hipEventRecord(c->ev[2], c->stream));
-    {
-        const uint32_t nb = std::min<uint32_t>(ntiles, kBboxBlocks);
-        cl_bbox_part<<<dim3(nb), dim3(kThreads), 0, c->stream>>>(c->pts, n, base + L.parts);
-        cl_bbox_fold<<<dim3(1), dim3(kThreads), 0, c->stream>>>(base + L.parts, nb, inv, g);
-        CL_TRY(hipGetLastError());
-        CL_TRY(hipMemcpyAsync(&hg, g, sizeof(Grid), hipMemcpyDeviceToHost, c->stream));
-        CL_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (hg.pass) {
-        result = n;  // PCL's overflow guard: the output is the input, non-finite points included
-    } else if (hg.n_valid == 0) {
-        result = 0;
-    } else {
-        const int passes = (int)((hg.nbits + 7u) >> 3);
-        cl_keys<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(c->pts, n, inv, g, ka, va, table, ntiles);
-        CL_TRY(hipGetLastError());
-        for (int p = 0; p < passes; p++) {
-            const uint32_t* kin = (p & 1) ? kb : ka;
-            const uint32_t* vin = (p & 1) ? vb : va;
-            uint32_t* kout = (p & 1) ? ka : kb;
-            uint32_t* vout = (p & 1) ? va : vb;
-            if (p > 0) cl_hist<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(kin, n, 8 * p, table, ntiles);
-            rc = exclusive_scan(c->stream, table, tab, aux);
-            if (rc != LIO_OK) return fail(rc);
-            cl_scatter<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(kin, vin, kout, vout, n, 8 * p, table, ntiles);
-            CL_TRY(hipGetLastError());
-        }
-        const bool odd = passes & 1;
-        const uint32_t* keys = odd ? kb : ka;
-        const uint32_t* vals = odd ? vb : va;
-        uint32_t* hpos = odd ? ka : kb;     // the free key buffer (n + 1 words)
-        uint32_t* longlist = odd ? va : vb;  // the free value buffer (n words)
-        cl_head_count<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(keys, n, hg.total, table);
-        const uint32_t* d_nvox = compact_finish(c->stream, table, n);
-        if (!d_nvox) return fail(LIO_E_DEVICE);
-        cl_head_write<<<dim3(ntiles), dim3(kThreads), 0, c->stream>>>(c->pts, keys, vals, n, hg.n_valid, hg.total, table, ntiles, hpos, sorted);
-        CL_TRY(hipGetLastError());
-        uint32_t nvox = 0;
-        CL_TRY(hipMemcpyAsync(&nvox, d_nvox, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        CL_TRY(hipStreamSynchronize(c->stream));
-        if (nvox) {
-            cl_centroid<<<dim3((nvox + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream>>>(sorted, hpos, nvox, c->pts, longlist, g);
-            cl_long<<<dim3(kLongBlocks), dim3(64), 0, c->stream>>>(sorted, hpos, longlist, g, c->pts);
-            CL_TRY(hipGetLastError());
-        }
-        result = nvox;
-    }
-    CL_TRY(hipEventRecord(c->ev[3], c->stream));
-    CL_TRY(hipStreamSynchronize(c->stream));
-#undef CL_TRY
-    c->voxel_us = elapsed_us(c->ev[2], c->ev[3]);
+    int rc = LIO_OK;
+    if (hipEventRecord(c->ev[2], c->stream) != hipSuccess) { set_error("lio_cloud_voxel_downsample: event record failed"); rc = LIO_E_DEVICE; }
+    if (rc == LIO_OK) rc = voxel_filter(c->stream, c->pts, n, leaf, c->pts, base, &result);
+    if (rc == LIO_OK && hipEventRecord(c->ev[3], c->stream) != hipSuccess) { set_error("lio_cloud_voxel_downsample: event record failed"); rc = LIO_E_DEVICE; }
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == LIO_OK) { set_error("lio_cloud_voxel_downsample: the stream failed"); rc = LIO_E_DEVICE; }
     (void)hipFree(base);
+    if (rc != LIO_OK) return rc;
+    c->voxel_us = elapsed_us(c->ev[2], c->ev[3]);
     c->n = result;
     if (n_out) *n_out = result;
     return LIO_OK;

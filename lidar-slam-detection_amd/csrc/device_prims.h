@@ -29,6 +29,12 @@ int exclusive_scan(hipStream_t st, uint32_t* data, uint64_t m, uint32_t* aux);
 uint64_t radix_scratch_words(uint64_t n);
 int radix_pass(hipStream_t st, const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout, uint32_t n, int shift, uint32_t* scratch);
 
+// pcl::VoxelGrid over n device points (lio_cloud_voxel_downsample's launches and semantics) from `in` to `out`: the same buffer (in place) or
+// another of n points (`in` is then left as it was).  scratch holds voxel_filter_words(n) words; the centroid launches are enqueued on st,
+// not waited for
+uint64_t voxel_filter_words(uint64_t n);
+int voxel_filter(hipStream_t st, const float4* in, uint32_t n, float leaf, float4* out, uint32_t* scratch, uint64_t* n_out);
+
 // the points of a cloud as they lie on the device, and the stream its appends and voxel grid run on
 struct CloudView {
     const float4* pts;

@@ -90,6 +90,10 @@ SYMBOLS = [
     "lio_calib_ground_default_params", "lio_calib_ground_create", "lio_calib_ground_destroy", "lio_calib_ground_crop_host",
     "lio_calib_ground_set_points_host", "lio_calib_ground_fit", "lio_calib_ground_download_indices", "lio_calib_ground_download_points",
     "lio_calib_ground_download_draws", "lio_calib_ground_last_run", "lio_calib_ground_last_times",
+    "lio_calib_imu_integrate", "lio_calib_imu_interpolate", "lio_calib_imu_time_align", "lio_calib_imu_solve", "lio_calib_imu_create",
+    "lio_calib_imu_destroy", "lio_calib_imu_reset", "lio_calib_imu_add_imu", "lio_calib_imu_add_frame", "lio_calib_imu_lidar_pose",
+    "lio_calib_imu_calibrate", "lio_calib_imu_lidar_poses", "lio_calib_imu_imu_poses", "lio_calib_imu_map_download",
+    "lio_calib_imu_target_download", "lio_calib_imu_counts", "lio_calib_imu_last_times", "lio_calib_imu_set_max_iterations",
 ]
 ABI_VERSION = 22  # kept at 22 for callers that compare against it; the revision the binding needs is ABI_REQUIRED
 ABI_REQUIRED = 23  # the oldest library revision that has every symbol above; lib() refuses an older one
@@ -724,6 +728,25 @@ def lib():
     sig("lio_calib_ground_download_draws", i64, vp, u32p, u32p, u32p, f32p, u64)
     sig("lio_calib_ground_last_run", cint, vp, cip, cip, cip, cip, cip)
     sig("lio_calib_ground_last_times", cint, vp, f64p, f64p, f64p, f64p)
+    if L.lio_abi_version() >= 27:  # (ABI_REQUIRED stays where callers pin it: an older library simply lacks the lidar-IMU calibration)
+        sig("lio_calib_imu_integrate", cint, f64p, f64p, u32, f64p)
+        sig("lio_calib_imu_interpolate", cint, f64p, f64p, dbl, f64p)
+        sig("lio_calib_imu_time_align", cint, f64p, f64p, u32, f64p, u32, u32p, u32p, f64p)
+        sig("lio_calib_imu_solve", cint, f64p, u32, f64p)
+        sig("lio_calib_imu_create", vp, cint, u32, u32)
+        sig("lio_calib_imu_destroy", None, vp)
+        sig("lio_calib_imu_reset", cint, vp)
+        sig("lio_calib_imu_add_imu", cint, vp, f64p, u32)
+        sig("lio_calib_imu_add_frame", cint, vp, u64, f32p, u32, u32, f64p, f64p)
+        sig("lio_calib_imu_lidar_pose", cint, vp, f32p, u32, u32, f64p)
+        sig("lio_calib_imu_calibrate", cint, vp, f64p)
+        sig("lio_calib_imu_lidar_poses", i64, vp, f64p, u64)
+        sig("lio_calib_imu_imu_poses", i64, vp, f64p, u64)
+        sig("lio_calib_imu_map_download", i64, vp, f32p, u64)
+        sig("lio_calib_imu_target_download", i64, vp, f32p, u64)
+        sig("lio_calib_imu_counts", cint, vp, u32p, u32p, u32p, u32p, u32p, cip)
+        sig("lio_calib_imu_last_times", cint, vp, f64p, f64p, f64p, f64p)
+        sig("lio_calib_imu_set_max_iterations", cint, vp, cint)
     _lib = L
     return L
 

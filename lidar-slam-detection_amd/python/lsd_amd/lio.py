@@ -2965,3 +2965,93 @@ class GroundCalib:
         v = [C.c_double(0) for _ in range(4)]
         check(lib().lio_calib_ground_last_times(self.h, *[C.byref(x) for x in v]), "calib ground times")
         return tuple(x.value for x in v)
+
+
+class ImuCalib:
+    """lio_calib_imu: the lidar-IMU calibration (the reference's CalibLidarImu); include/lio_hip.h states every rule.  The host half (add_imu,
+    add_frame without the flag, calibrate, the pose lists) needs no device; lidar_pose and the map update of add_frame open it on first use."""
+
+    def __init__(self, device=0, max_scan_points=1 << 18, max_map_points=1 << 21):
+        self.h = lib().lio_calib_imu_create(int(device), int(max_scan_points), int(max_map_points))
+        if not self.h:
+            raise capi.LioError("lio_calib_imu_create failed: " + lib().lio_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_calib_imu_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _rows(points):
+        if points is None:
+            return None, 0, 4
+        pts = f32(points)
+        if pts.ndim != 2 or (len(pts) and pts.shape[1] < 4):
+            raise ValueError("points: n x (4 or more) is required")
+        return pts, len(pts), max(pts.shape[1], 4)
+
+    def reset(self):
+        check(lib().lio_calib_imu_reset(self.h), "calib imu reset")
+
+    def add_imu(self, rows):
+        """n x 7: stamp us, gyro deg/s x 3, acc g x 3"""
+        r = f64(np.asarray(rows, np.float64).reshape(-1, 7))
+        check(lib().lio_calib_imu_add_imu(self.h, ptr(r, C.c_double), len(r)), "calib imu add_imu")
+
+    def add_frame(self, stamp_us, global_T, delta_T, points=None):
+        pts, n, stride = self._rows(points)
+        g, d = f64(np.asarray(global_T, np.float64).reshape(4, 4)), f64(np.asarray(delta_T, np.float64).reshape(4, 4))
+        check(lib().lio_calib_imu_add_frame(self.h, int(stamp_us), ptr(pts, C.c_float) if n else None, n, stride, ptr(g, C.c_double), ptr(d, C.c_double)),
+              "calib imu add_frame")
+
+    def lidar_pose(self, points):
+        """get_lidar_T_R: the 4 x 4 f64 pose of the frame against the local map"""
+        pts, n, stride = self._rows(points)
+        T = np.zeros((4, 4), np.float64)
+        check(lib().lio_calib_imu_lidar_pose(self.h, ptr(pts, C.c_float) if n else None, n, stride, ptr(T, C.c_double)), "calib imu lidar_pose")
+        return T
+
+    def calibrate(self):
+        R = np.zeros((3, 3), np.float64)
+        check(lib().lio_calib_imu_calibrate(self.h, ptr(R, C.c_double)), "calib imu calibrate")
+        return R
+
+    def _poses(self, fn, what):
+        n = self.counts()["aligned"]
+        out = np.zeros((max(n, 1), 4, 4), np.float64)
+        m = check(fn(self.h, ptr(out, C.c_double), len(out)), what)
+        return out[:m].copy()
+
+    def lidar_poses(self):
+        return self._poses(lib().lio_calib_imu_lidar_poses, "calib imu lidar_poses")
+
+    def imu_poses(self):
+        return self._poses(lib().lio_calib_imu_imu_poses, "calib imu imu_poses")
+
+    def counts(self):
+        v = [C.c_uint32(0) for _ in range(5)]
+        flag = C.c_int(0)
+        check(lib().lio_calib_imu_counts(self.h, *[C.byref(x) for x in v], C.byref(flag)), "calib imu counts")
+        return dict(zip(("frames", "imus", "aligned", "map_points", "target_points"), (int(x.value) for x in v)), no_rtk=bool(flag.value))
+
+    def _download(self, fn, n, what):
+        out = np.zeros((max(n, 1), 4), np.float32)
+        m = check(fn(self.h, ptr(out, C.c_float), len(out)), what)
+        return out[:m].copy()
+
+    def map_download(self):
+        return self._download(lib().lio_calib_imu_map_download, self.counts()["map_points"], "calib imu map_download")
+
+    def target_download(self):
+        """the matcher's target in its internal order"""
+        return self._download(lib().lio_calib_imu_target_download, self.counts()["target_points"], "calib imu target_download")
+
+    def last_times(self):
+        v = [C.c_double(0) for _ in range(4)]
+        check(lib().lio_calib_imu_last_times(self.h, *[C.byref(x) for x in v]), "calib imu last_times")
+        return dict(zip(("stage_us", "filter_us", "align_us", "map_update_us"), (x.value for x in v)))
+
+    def set_max_iterations(self, n):
+        check(lib().lio_calib_imu_set_max_iterations(self.h, int(n)), "calib imu set_max_iterations")
