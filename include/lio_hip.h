@@ -96,8 +96,10 @@ int lio_device_count(void);
  * 26 = lio_calib_ground_* (the lidar ground calibration: the polygon crop, fit_plane's RANSAC scored a batch of planes per pass over the
  *      points, the loop replayed on the host).
  * 27 = lio_calib_imu_* (the lidar-IMU calibration: gyro integration, time alignment and the quaternion hand-eye solve on the host; the tool's
- *      own lidar odometry -- voxel filter, FAST_VGICP against a local map that stays in HBM -- on the device). */
-#define LIO_ABI_VERSION 27
+ *      own lidar odometry -- voxel filter, FAST_VGICP against a local map that stays in HBM -- on the device).
+ * 28 = lio_boxes_* (detection boxes: rotated BEV overlap, convex hull area, BEV IoU and GIoU3D of box pairs, rotated NMS with the sweep on
+ *      the device, and the detector's post-process -- filter, order, NMS, gather -- as one call). */
+#define LIO_ABI_VERSION 28
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -2148,6 +2150,62 @@ int64_t lio_calib_imu_target_download(lio_calib_imu*, float* xyzi, uint64_t cap)
 int lio_calib_imu_counts(lio_calib_imu*, uint32_t* frames, uint32_t* imus, uint32_t* aligned, uint32_t* map_points, uint32_t* target_points, int* no_rtk);
 int lio_calib_imu_last_times(lio_calib_imu*, double* stage_us, double* filter_us, double* align_us, double* map_update_us);
 int lio_calib_imu_set_max_iterations(lio_calib_imu*, int max_iterations);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Detection boxes: the geometry around the reference's detection network -- the pybind11 module iou3d_nms_ext
+ * (sensor_driver/inference/iou3d_nms/: iou3d_cpu.cpp, iou3d_nms_kernel.cu, iou3d_nms_api.cpp), sensor_driver/inference/iou3d_nms.py over it, and
+ * the detector's post-process (sensor_inference/utils/model_nms_utils.py:4-22).  Boxes are rows of 7 f32: x y z dx dy dz heading.
+ *
+ *   pair      box_overlap, box_union and iou_bev of iou3d_cpu.cpp:118-312, statement for statement in f32 without contraction: corners rotated
+ *             about the centre; the 16 edge-pair intersection tests in (i, j) order (check_rect_cross, the strict s1 * s2 > 0 && s3 * s4 > 0,
+ *             the two formulas on either side of fabs(s5 - s1) > 1e-8); check_in_box2d with MARGIN 1e-2 and strict <, b's corners in a and a's
+ *             in b interleaved per k; the centre is the f32 sum in insertion order over cnt; the points ascend by atan2f about it, equal keys
+ *             in insertion order; the fan from point 0, fabs(area) / 2; cnt == 0 gives 0.  The hull: the eight corners under the bubble
+ *             sort's exact passes with operator< (descending x then y, >=), the two monotone-chain passes with <= 0 pops and used[], the fan
+ *             from hull point 0.  iou = overlap / fmaxf(dx_a dy_a + dx_b dy_b - overlap, 1e-8).  The device's cosf, sinf and atan2f are not
+ *             glibc's: results differ from the reference's build by what last-bit differences of the three move (docs/kernels.md, "boxes")
+ *   giou3d    boxes_giou3d_gpu of iou3d_nms.py:20-62 operation for operation in f32 (the tracker's matrix, sensor_fusion/MOT3D/model.py:44)
+ *   nms       nms_gpu of iou3d_nms_api.cpp:49-85 with the sweep on the device: box i (in order) is kept when no kept box before it has
+ *             iou_bev(kept, i) > thresh.  With scores the order is PROJECT's: descending score, ties to the smaller index, NaN last in index
+ *             order -- np.argsort(-scores, kind="stable") (the reference's np.argsort(-scores) leaves ties to numpy's unstable default).
+ *             LIO_BOXES_NMS_AABB_GATE ANDs in the gate of nms_cpu (iou3d_nms.py:78-129): the axis-aligned extents x -+ dx / 2, y -+ dy / 2,
+ *             z -+ dz / 2 of the two boxes overlap strictly (min of the maxima > max of the minima) in all three
+ *   post      class_agnostic_nms: box i passes when its label c (1-based) has an entry and score >= class_thresh[c - 1] (a negative entry
+ *             means none; NaN never passes); the passing boxes in the order above through nms, the first post_max of the kept gathered.
+ *             No host synchronisation between the upload and the one download (count and kept rows)
+ * Errors: NULL from create without a device (no CPU fallback) or for max_boxes outside 1 .. 16384; LIO_E_INVALID for a NULL handle, a NULL
+ * array with n > 0, more than max_boxes boxes on either side, an unknown mode.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define LIO_BOXES_NMS_ROTATED 0
+#define LIO_BOXES_NMS_AABB_GATE 1
+typedef struct lio_boxes lio_boxes;
+/* max_boxes: the most boxes on either side of any call */
+lio_boxes* lio_boxes_create(int device, uint32_t max_boxes);
+void lio_boxes_destroy(lio_boxes*);
+/* host rows a (na x 7) and b (nb x 7); each output is row-major (na, nb) or NULL (not computed); na == 0 or nb == 0 writes nothing.
+ * Replaces boxes_overlap_bev_gpu, boxes_union_bev_gpu, boxes_iou_bev_cpu (iou3d_nms_api.cpp:26-47, 87-143) and iou3d_nms.py:20-62 */
+int lio_boxes_pairwise(lio_boxes*, const float* a, uint32_t na, const float* b, uint32_t nb, float* overlap, float* hull, float* iou_bev,
+                       float* giou3d);
+/* the number kept, their indices into the caller's arrays in keep (room for min(max_out, n)); scores NULL: the boxes are already in order;
+ * max_out 0: no cap.  Replaces iou3d_nms_api.cpp:49-85 and the argsort / gather of iou3d_nms.py:64-76 (mode 0), iou3d_nms.py:78-129 (gate) */
+int64_t lio_boxes_nms(lio_boxes*, const float* boxes, const float* scores, uint32_t n, float thresh, int mode, uint32_t max_out, int64_t* keep);
+/* the mode of the two post-process entries below (NMS_TYPE nms_gpu = LIO_BOXES_NMS_ROTATED, the default; nms_cpu = LIO_BOXES_NMS_AABB_GATE) */
+int lio_boxes_set_gate(lio_boxes*, int mode);
+/* the number kept (at most post_max; 0 = no cap) and their rows, scores and labels in the outputs (room for min(post_max, n) each).
+ * Replaces model_nms_utils.py:4-22 */
+int64_t lio_boxes_postprocess(lio_boxes*, const float* boxes, const float* scores, const int32_t* labels, uint32_t n, const float* class_thresh,
+                              int n_class, float nms_thresh, uint32_t post_max, float* out_boxes, float* out_scores, int32_t* out_labels);
+/* the same with the three inputs in device memory (a network's heads never cross the link); the caller has finished writing them.  The
+ * outputs are host arrays */
+int64_t lio_boxes_postprocess_device(lio_boxes*, const float* d_boxes, const float* d_scores, const int32_t* d_labels, uint32_t n,
+                                     const float* class_thresh, int n_class, float nms_thresh, uint32_t post_max, float* out_boxes,
+                                     float* out_scores, int32_t* out_labels);
+/* the positions in the caller's arrays of the boxes the last post-process kept, in its output order (from the same download: no device
+ * traffic): their number, or -(number) when cap is too small; 0 after any other call */
+int64_t lio_boxes_last_indices(lio_boxes*, uint32_t* out, uint64_t cap);
+/* device time (HIP events) of the last nms or post-process: filter and order; prepare and mask; sweep; first launch to last.  After pairwise:
+ * the total alone */
+int lio_boxes_last_times(lio_boxes*, double* order_us, double* mask_us, double* sweep_us, double* total_us);
 
 #ifdef __cplusplus
 }

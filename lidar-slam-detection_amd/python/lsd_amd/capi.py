@@ -94,6 +94,8 @@ SYMBOLS = [
     "lio_calib_imu_destroy", "lio_calib_imu_reset", "lio_calib_imu_add_imu", "lio_calib_imu_add_frame", "lio_calib_imu_lidar_pose",
     "lio_calib_imu_calibrate", "lio_calib_imu_lidar_poses", "lio_calib_imu_imu_poses", "lio_calib_imu_map_download",
     "lio_calib_imu_target_download", "lio_calib_imu_counts", "lio_calib_imu_last_times", "lio_calib_imu_set_max_iterations",
+    "lio_boxes_create", "lio_boxes_destroy", "lio_boxes_pairwise", "lio_boxes_nms", "lio_boxes_set_gate", "lio_boxes_postprocess",
+    "lio_boxes_postprocess_device", "lio_boxes_last_indices", "lio_boxes_last_times",
 ]
 ABI_VERSION = 22  # kept at 22 for callers that compare against it; the revision the binding needs is ABI_REQUIRED
 ABI_REQUIRED = 23  # the oldest library revision that has every symbol above; lib() refuses an older one
@@ -295,6 +297,8 @@ class CalibGroundParams(C.Structure):  # lio_calib_ground_params
 
 
 CALIB_GROUND_MAX_VERTICES = 256  # LIO_CALIB_GROUND_MAX_VERTICES
+BOXES_NMS_ROTATED, BOXES_NMS_AABB_GATE = 0, 1  # LIO_BOXES_NMS_*
+BOXES_MAX = 16384  # the most boxes a lio_boxes handle takes
 
 DFO_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_int, C.c_void_p)  # lio_dfo_fn
 DFO_HOOK = C.CFUNCTYPE(C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_void_p)  # lio_dfo_hook
@@ -747,6 +751,16 @@ def lib():
         sig("lio_calib_imu_counts", cint, vp, u32p, u32p, u32p, u32p, u32p, cip)
         sig("lio_calib_imu_last_times", cint, vp, f64p, f64p, f64p, f64p)
         sig("lio_calib_imu_set_max_iterations", cint, vp, cint)
+    if L.lio_abi_version() >= 28:  # the detection boxes
+        sig("lio_boxes_create", vp, cint, u32)
+        sig("lio_boxes_destroy", None, vp)
+        sig("lio_boxes_pairwise", cint, vp, f32p, u32, f32p, u32, f32p, f32p, f32p, f32p)
+        sig("lio_boxes_nms", i64, vp, f32p, f32p, u32, flt, cint, u32, i64p)
+        sig("lio_boxes_set_gate", cint, vp, cint)
+        sig("lio_boxes_postprocess", i64, vp, f32p, f32p, i32p, u32, f32p, cint, flt, u32, f32p, f32p, i32p)
+        sig("lio_boxes_postprocess_device", i64, vp, vp, vp, vp, u32, f32p, cint, flt, u32, f32p, f32p, i32p)
+        sig("lio_boxes_last_indices", i64, vp, u32p, u64)
+        sig("lio_boxes_last_times", cint, vp, f64p, f64p, f64p, f64p)
     _lib = L
     return L
 

@@ -2967,6 +2967,97 @@ class GroundCalib:
         return tuple(x.value for x in v)
 
 
+class Boxes:
+    """lio_boxes: the geometry around the reference's detection network on the device -- rotated BEV overlap, hull area, BEV IoU and GIoU3D of
+    box pairs, rotated NMS with the sweep on the device, and the detector's post-process as one call; include/lio_hip.h states every rule.
+    Boxes are (N, 7) f32 rows [x, y, z, dx, dy, dz, heading]; at most max_boxes on either side of a call."""
+
+    WHAT = ("overlap", "hull", "iou_bev", "giou3d")
+
+    def __init__(self, max_boxes=2048, device=0):
+        self.h = lib().lio_boxes_create(device, max_boxes)
+        if not self.h:
+            raise capi.LioError("lio_boxes_create failed: " + lib().lio_last_error().decode())
+        self.max_boxes = max_boxes
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_boxes_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _rows(boxes):
+        b = f32(boxes)
+        if b.ndim != 2 or b.shape[1] != 7:
+            raise ValueError("boxes: (N, 7) is required")
+        return b
+
+    def pairwise(self, a, b, what=WHAT):
+        """dict of (len(a), len(b)) f32 matrices, one per name in `what` (of "overlap", "hull", "iou_bev", "giou3d"), from one pass"""
+        a, b = self._rows(a), self._rows(b)
+        for w in what:
+            if w not in self.WHAT:
+                raise ValueError(f"pairwise: {w!r} is not one of {self.WHAT}")
+        out = {w: np.zeros((len(a), len(b)), np.float32) for w in what}
+        ps = [ptr(out[w], C.c_float) if w in out else None for w in self.WHAT]
+        check(lib().lio_boxes_pairwise(self.h, ptr(a, C.c_float), len(a), ptr(b, C.c_float), len(b), *ps), "boxes pairwise")
+        return out
+
+    def nms(self, boxes, scores, thresh, mode=0, max_out=None):
+        """indices (int64) into `boxes` of the kept ones, best first; scores None: the boxes are already in order.  With scores the order is
+        np.argsort(-scores, kind="stable").  mode capi.BOXES_NMS_AABB_GATE: the gate of the reference's nms_cpu"""
+        b = self._rows(boxes)
+        sc = None if scores is None else f32(np.asarray(scores).reshape(-1))
+        if sc is not None and len(sc) != len(b):
+            raise ValueError("nms: one score per box")
+        keep = np.zeros(max(len(b), 1), np.int64)
+        if max_out is not None and max_out <= 0:
+            return keep[:0]
+        n = check(int(lib().lio_boxes_nms(self.h, ptr(b, C.c_float), None if sc is None else ptr(sc, C.c_float), len(b), float(thresh), int(mode),
+                                          0 if max_out is None else min(int(max_out), 0xFFFFFFFF), ptr(keep, C.c_int64))), "boxes nms")
+        return keep[:n]
+
+    def _post(self, fn, pb, ps, pl, n, class_thresh, nms_thresh, post_max, mode):
+        ct = f32(np.asarray(class_thresh).reshape(-1))
+        room = n if not post_max or post_max > n else int(post_max)
+        ob, osc, ol = np.zeros((max(room, 1), 7), np.float32), np.zeros(max(room, 1), np.float32), np.zeros(max(room, 1), np.int32)
+        check(lib().lio_boxes_set_gate(self.h, int(mode)), "boxes gate")
+        k = check(int(fn(self.h, pb, ps, pl, n, ptr(ct, C.c_float), len(ct), float(nms_thresh), room, ptr(ob, C.c_float), ptr(osc, C.c_float),
+                         ptr(ol, C.c_int32))), "boxes postprocess")
+        return ob[:k], osc[:k], ol[:k]
+
+    def postprocess(self, boxes, scores, labels, class_thresh, nms_thresh, post_max=None, mode=0):
+        """(boxes (K, 7), scores (K,), labels (K,) int32) of the detector's post-process: box i passes when class_thresh[label - 1] is not
+        negative and score >= it; the passing boxes through NMS in descending score (ties to the smaller index); the first post_max kept"""
+        b = self._rows(boxes)
+        sc, lb = f32(np.asarray(scores).reshape(-1)), np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
+        if len(sc) != len(b) or len(lb) != len(b):
+            raise ValueError("postprocess: one score and one label per box")
+        return self._post(lib().lio_boxes_postprocess, ptr(b, C.c_float), ptr(sc, C.c_float), ptr(lb, C.c_int32), len(b), class_thresh, nms_thresh,
+                          post_max, mode)
+
+    def postprocess_device(self, d_boxes, d_scores, d_labels, n, class_thresh, nms_thresh, post_max=None, mode=0):
+        """postprocess over device addresses (ints: a tensor's data_ptr()) of n x 7 f32, n f32 and n int32 the caller has finished writing"""
+        return self._post(lib().lio_boxes_postprocess_device, C.c_void_p(int(d_boxes)), C.c_void_p(int(d_scores)), C.c_void_p(int(d_labels)), int(n),
+                          class_thresh, nms_thresh, post_max, mode)
+
+    def last_indices(self):
+        """positions in the caller's arrays of the boxes the last postprocess kept, in its output order (uint32)"""
+        n = max(-lib().lio_boxes_last_indices(self.h, None, 0), 0)
+        out = np.zeros(n, np.uint32)
+        if n > 0:
+            check(int(lib().lio_boxes_last_indices(self.h, ptr(out, C.c_uint32), n)), "boxes last_indices")
+        return out
+
+    def last_times(self):
+        """(order_us, mask_us, sweep_us, total_us): device time of the last nms or post-process by stage; after pairwise the total alone"""
+        v = [C.c_double(0) for _ in range(4)]
+        check(lib().lio_boxes_last_times(self.h, *[C.byref(x) for x in v]), "boxes times")
+        return tuple(x.value for x in v)
+
+
 class ImuCalib:
     """lio_calib_imu: the lidar-IMU calibration (the reference's CalibLidarImu); include/lio_hip.h states every rule.  The host half (add_imu,
     add_frame without the flag, calibrate, the pose lists) needs no device; lidar_pose and the map update of add_frame open it on first use."""
