@@ -98,8 +98,10 @@ int lio_device_count(void);
  * 27 = lio_calib_imu_* (the lidar-IMU calibration: gyro integration, time alignment and the quaternion hand-eye solve on the host; the tool's
  *      own lidar odometry -- voxel filter, FAST_VGICP against a local map that stays in HBM -- on the device).
  * 28 = lio_boxes_* (detection boxes: rotated BEV overlap, convex hull area, BEV IoU and GIoU3D of box pairs, rotated NMS with the sweep on
- *      the device, and the detector's post-process -- filter, order, NMS, gather -- as one call). */
-#define LIO_ABI_VERSION 28
+ *      the device, and the detector's post-process -- filter, order, NMS, gather -- as one call).
+ * 29 = lio_voxelizer_* / lio_voxelize_grid_size (the detection front end: the sliding window of sweeps, the hash voxeliser and the mean VFE to
+ *      f16, pinned to the reference's kernels run one thread after another in index order). */
+#define LIO_ABI_VERSION 29
 int lio_abi_version(void);
 /* page-locked host memory for clouds handed over with LIO_JOB_HOST_RAW (or lio_scan_upload): copies from it run at the link's rate and
  * overlap with kernels; NULL on failure.  Any hipHostMalloc'ed / hipHostRegister'ed range serves as well. */
@@ -2206,6 +2208,77 @@ int64_t lio_boxes_last_indices(lio_boxes*, uint32_t* out, uint64_t cap);
 /* device time (HIP events) of the last nms or post-process: filter and order; prepare and mask; sweep; first launch to last.  After pairwise:
  * the total alone */
 int lio_boxes_last_times(lio_boxes*, double* order_us, double* mask_us, double* sweep_us, double* total_us);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Detection front end: what LidarInference::forward (sensor_driver/inference/tensorRT/lidar_inference.cpp:81-85) runs on every lidar frame
+ * before the network -- the sliding window of sweeps (sensor_driver/inference/voxelize/preprocess_kernel.cu) and the hash voxeliser with its
+ * mean VFE (voxelization_kernel.cu).  Rows are 5 f32: x y z intensity time.  The result is the reference's kernels run ONE THREAD AFTER
+ * ANOTHER IN INDEX ORDER (one valid execution of the reference, and the only reproducible one), bit for bit.
+ *
+ *   grid      compute_grid_size (voxelization_kernel.cu:182-189): (int)std::round((max - min) / size) per axis in f32.  The product of the
+ *             three must be below 2^32 - 1 (keys are 32 bits and 2^32 - 1 marks an empty slot)
+ *   window    PreprocessImplement::forward (preprocess_kernel.cu:56-101) with num_feature 5: up to max_frame_num sweeps, newest first.  The
+ *             caller's n is clamped to max_points (lidar_inference.cpp:81).  A realtime call drops the oldest sweep's count, clamps n to
+ *             max(min(n, max_points - total), 1), shifts the counts, rewrites every remaining row behind the room of the new sweep
+ *             (transform_kernel, :6-20): x y z = m[4r] * x + m[4r + 1] * y + m[4r + 2] * z + m[4r + 3] in f32, left to right, no contraction;
+ *             channel 3 copied; channel 4 = (float)((double)t + 0.1); then the new sweep is copied to the front.  A non-realtime call empties
+ *             the window and stores the sweep alone.  A call into a full window stores one row beyond max_points, as the reference does (its
+ *             buffer has no room for it; the buffers here hold max_points + max_frame_num rows, the most that rule can reach)
+ *   voxels    a point's coordinates are floorf((p - min) / size) per axis in IEEE f32; it counts when min <= p < max on all axes and the three
+ *             indices are inside the grid (voxelization_kernel, :118-134).  Key (iz * gy + iy) * gx + ix.  A voxel's id is the rank of its
+ *             first point in window order; voxels with id >= max_voxels and all their points vanish, num_voxels = min(real, max_voxels).  A
+ *             voxel keeps its first max_points_per_voxel points in window order and its count is clamped to that
+ *   features  reduce_mean_kernel (:158-180): per channel slot 0's value plus the others in slot order in f32, over (float)count, rounded to
+ *             nearest-even f16 (subnormals kept, overflow to inf)
+ *   indices   (0, z, y, x) for LIO_VOXEL_ORDER_ZYX (CenterPoint, the reference's call site), (0, x, y, z) for LIO_VOXEL_ORDER_XYZ
+ * Deviations from the reference: a voxel exists only if a point passes BOTH tests (build_hash_table_kernel, :73-92, tests the
+ * grid alone and creates voxels without points); points with a non-finite x, y or z are dropped before both passes (undefined there); a
+ * non-realtime call zeroes the sweep counts (preprocess_kernel.cu:90 keeps stale ones).
+ * Errors: NULL from create without a device (no CPU fallback) or on bad params (voxel size <= 0, max <= min, the grid's product too large,
+ * max_points_per_voxel outside 1 .. 32, an unknown order, a zero max_voxels / max_points / max_frame_num); LIO_E_INVALID for a NULL handle
+ * and for n == 0.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define LIO_VOXEL_ORDER_XYZ 1
+#define LIO_VOXEL_ORDER_ZYX 2
+typedef struct lio_voxelizer_params {
+    float min_range[3];
+    float max_range[3];
+    float voxel_size[3];
+    uint32_t max_voxels;
+    uint32_t max_points_per_voxel; /* 1 .. 32 */
+    uint32_t max_points;           /* rows the window holds */
+    uint32_t max_frame_num;        /* sweeps the window holds, >= 1 */
+    int32_t order;                 /* LIO_VOXEL_ORDER_* */
+} lio_voxelizer_params;
+typedef struct lio_voxelizer lio_voxelizer;
+/* host only: the grid of a range and a voxel size; LIO_E_INVALID for a size <= 0, max <= min or a non-finite value */
+int lio_voxelize_grid_size(const float min_range[3], const float max_range[3], const float voxel_size[3], int out[3]);
+lio_voxelizer* lio_voxelizer_create(int device, const lio_voxelizer_params*);
+void lio_voxelizer_destroy(lio_voxelizer*);
+/* forgets the window and the last result (inference_reset) */
+int lio_voxelizer_reset(lio_voxelizer*);
+/* one frame: host rows points (n x 5), the row-major 4 x 4 motion that takes the previous frame's coordinates to this frame's (read by
+ * realtime calls only).  Returns the number of voxels.  One host wait.  Replaces lidar_inference.cpp:83-85 */
+int64_t lio_voxelizer_forward(lio_voxelizer*, const float* points, uint32_t n, const float motion[16], int realtime);
+/* the same with the rows in device memory (the caller has finished writing them): nothing is uploaded */
+int64_t lio_voxelizer_forward_device(lio_voxelizer*, const float* d_points, uint32_t n, const float motion[16], int realtime);
+/* the last result to host arrays with room for cap voxels: features (V x 5 f16 bit patterns), indices (V x 4), counts (V, clamped); each may
+ * be NULL.  Returns V, or -V when cap is too small */
+int64_t lio_voxelizer_output(lio_voxelizer*, uint16_t* features, int32_t* indices, uint32_t* counts, uint64_t cap);
+/* the device addresses of the last result, valid until the next forward: what a sparse-convolution engine takes.  Returns V */
+int64_t lio_voxelizer_output_device(lio_voxelizer*, const void** d_features, const int32_t** d_indices);
+/* the window as it stands (rows x 5 f32, newest sweep first): the rows, or -(rows) when cap rows are too few */
+int64_t lio_voxelizer_window(lio_voxelizer*, float* rows, uint64_t cap);
+/* the rows of every sweep, newest first: max_frame_num, or -(max_frame_num) when cap is too small */
+int64_t lio_voxelizer_window_counts(lio_voxelizer*, int32_t* per_frame, uint32_t cap);
+/* the device address of the window's rows (rows x 5 f32), valid until the next forward or reset: the rows */
+int64_t lio_voxelizer_window_device(lio_voxelizer*, const float** d_rows);
+/* of the last forward: the voxels before the cap, the points that passed the tests, the points left in kept voxels' slots */
+int lio_voxelizer_last_counts(lio_voxelizer*, uint64_t* real_voxels, uint64_t* points_in_range, uint64_t* points_kept);
+/* device time (HIP events) of the last forward by stage: window move and sweep copy; table clear and insert; head ranking; slots; means; first
+ * launch to last */
+int lio_voxelizer_last_times(lio_voxelizer*, double* window_us, double* insert_us, double* rank_us, double* slots_us, double* mean_us,
+                             double* total_us);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,9 @@ SYMBOLS = [
     "lio_calib_imu_target_download", "lio_calib_imu_counts", "lio_calib_imu_last_times", "lio_calib_imu_set_max_iterations",
     "lio_boxes_create", "lio_boxes_destroy", "lio_boxes_pairwise", "lio_boxes_nms", "lio_boxes_set_gate", "lio_boxes_postprocess",
     "lio_boxes_postprocess_device", "lio_boxes_last_indices", "lio_boxes_last_times",
+    "lio_voxelize_grid_size", "lio_voxelizer_create", "lio_voxelizer_destroy", "lio_voxelizer_reset", "lio_voxelizer_forward",
+    "lio_voxelizer_forward_device", "lio_voxelizer_output", "lio_voxelizer_output_device", "lio_voxelizer_window",
+    "lio_voxelizer_window_counts", "lio_voxelizer_window_device", "lio_voxelizer_last_counts", "lio_voxelizer_last_times",
 ]
 ABI_VERSION = 22  # kept at 22 for callers that compare against it; the revision the binding needs is ABI_REQUIRED
 ABI_REQUIRED = 23  # the oldest library revision that has every symbol above; lib() refuses an older one
@@ -296,9 +299,15 @@ class CalibGroundParams(C.Structure):  # lio_calib_ground_params
     _fields_ = [("sigma", C.c_double), ("num_iteration", C.c_int32), ("thresh", C.c_double), ("seed", C.c_uint32)]
 
 
+class VoxelizerParams(C.Structure):  # lio_voxelizer_params
+    _fields_ = [("min_range", C.c_float * 3), ("max_range", C.c_float * 3), ("voxel_size", C.c_float * 3), ("max_voxels", C.c_uint32),
+                ("max_points_per_voxel", C.c_uint32), ("max_points", C.c_uint32), ("max_frame_num", C.c_uint32), ("order", C.c_int32)]
+
+
 CALIB_GROUND_MAX_VERTICES = 256  # LIO_CALIB_GROUND_MAX_VERTICES
 BOXES_NMS_ROTATED, BOXES_NMS_AABB_GATE = 0, 1  # LIO_BOXES_NMS_*
 BOXES_MAX = 16384  # the most boxes a lio_boxes handle takes
+VOXEL_ORDER_XYZ, VOXEL_ORDER_ZYX = 1, 2  # LIO_VOXEL_ORDER_*
 
 DFO_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_int, C.c_void_p)  # lio_dfo_fn
 DFO_HOOK = C.CFUNCTYPE(C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_void_p)  # lio_dfo_hook
@@ -761,6 +770,21 @@ def lib():
         sig("lio_boxes_postprocess_device", i64, vp, vp, vp, vp, u32, f32p, cint, flt, u32, f32p, f32p, i32p)
         sig("lio_boxes_last_indices", i64, vp, u32p, u64)
         sig("lio_boxes_last_times", cint, vp, f64p, f64p, f64p, f64p)
+    if L.lio_abi_version() >= 29:  # the detection front end
+        u16p, u64p = C.POINTER(C.c_uint16), C.POINTER(u64)
+        sig("lio_voxelize_grid_size", cint, f32p, f32p, f32p, i32p)
+        sig("lio_voxelizer_create", vp, cint, C.POINTER(VoxelizerParams))
+        sig("lio_voxelizer_destroy", None, vp)
+        sig("lio_voxelizer_reset", cint, vp)
+        sig("lio_voxelizer_forward", i64, vp, f32p, u32, f32p, cint)
+        sig("lio_voxelizer_forward_device", i64, vp, vp, u32, f32p, cint)
+        sig("lio_voxelizer_output", i64, vp, u16p, i32p, u32p, u64)
+        sig("lio_voxelizer_output_device", i64, vp, C.POINTER(vp), C.POINTER(vp))
+        sig("lio_voxelizer_window", i64, vp, f32p, u64)
+        sig("lio_voxelizer_window_counts", i64, vp, i32p, u32)
+        sig("lio_voxelizer_window_device", i64, vp, C.POINTER(vp))
+        sig("lio_voxelizer_last_counts", cint, vp, u64p, u64p, u64p)
+        sig("lio_voxelizer_last_times", cint, vp, f64p, f64p, f64p, f64p, f64p, f64p)
     _lib = L
     return L
 

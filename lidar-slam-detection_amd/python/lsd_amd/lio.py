@@ -3058,6 +3058,122 @@ class Boxes:
         return tuple(x.value for x in v)
 
 
+class Voxelizer:
+    """lio_voxelizer: the front end of the reference's detection network on the device -- the sliding window of sweeps, the hash voxeliser and
+    the mean VFE to f16; include/lio_hip.h states every rule.  Rows are (N, 5) f32 [x, y, z, intensity, time]."""
+
+    def __init__(self, min_range, max_range, voxel_size, max_voxels, max_points_per_voxel=5, max_points=500_000, max_frame_num=1,
+                 order=capi.VOXEL_ORDER_ZYX, device=0):
+        p = capi.VoxelizerParams()
+        for name, v in (("min_range", min_range), ("max_range", max_range), ("voxel_size", voxel_size)):
+            v = [float(x) for x in np.asarray(v).reshape(-1)]
+            if len(v) != 3:
+                raise ValueError(f"{name}: three values are required")
+            setattr(p, name, (C.c_float * 3)(*v))
+        for name, v in (("max_voxels", max_voxels), ("max_points_per_voxel", max_points_per_voxel), ("max_points", max_points),
+                        ("max_frame_num", max_frame_num)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name}: {v} is not an unsigned 32-bit count")
+            setattr(p, name, int(v))
+        p.order = int(order)
+        self.params = p
+        self.h = lib().lio_voxelizer_create(device, C.byref(p))
+        if not self.h:
+            raise capi.LioError("lio_voxelizer_create failed: " + lib().lio_last_error().decode())
+        self.num_voxels = 0
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib().lio_voxelizer_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    @staticmethod
+    def grid_size(min_range, max_range, voxel_size):
+        """[gx, gy, gz] of the reference's compute_grid_size (host only)"""
+        a = [f32(np.asarray(v).reshape(-1)) for v in (min_range, max_range, voxel_size)]
+        if any(len(v) != 3 for v in a):
+            raise ValueError("grid_size: three values each are required")
+        out = np.zeros(3, np.int32)
+        check(lib().lio_voxelize_grid_size(ptr(a[0], C.c_float), ptr(a[1], C.c_float), ptr(a[2], C.c_float), ptr(out, C.c_int32)), "voxelize grid_size")
+        return [int(v) for v in out]
+
+    @staticmethod
+    def _motion(motion):
+        m = np.eye(4, dtype=np.float32) if motion is None else f32(np.asarray(motion).reshape(-1))
+        if m.size != 16:
+            raise ValueError("motion: a 4 x 4 matrix is required")
+        return np.ascontiguousarray(m.reshape(-1))
+
+    def forward(self, points, motion=None, realtime=True):
+        """one frame of (N, 5) rows and the 4 x 4 motion from the previous frame to this one: the number of voxels"""
+        pts = f32(points)
+        if pts.ndim != 2 or pts.shape[1] != 5:
+            raise ValueError("points: (N, 5) is required")
+        m = self._motion(motion)
+        self.num_voxels = check(int(lib().lio_voxelizer_forward(self.h, ptr(pts, C.c_float), len(pts), ptr(m, C.c_float), int(bool(realtime)))),
+                                "voxelizer forward")
+        return self.num_voxels
+
+    def forward_device(self, d_points, n, motion=None, realtime=True):
+        """forward over the device address (an int: a tensor's data_ptr()) of n x 5 f32 the caller has finished writing; nothing is uploaded"""
+        m = self._motion(motion)
+        self.num_voxels = check(int(lib().lio_voxelizer_forward_device(self.h, C.c_void_p(int(d_points)), int(n), ptr(m, C.c_float), int(bool(realtime)))),
+                                "voxelizer forward_device")
+        return self.num_voxels
+
+    def output(self):
+        """(features (V, 5) float16, indices (V, 4) int32, counts (V,) uint32) of the last forward"""
+        v = self.num_voxels
+        feat, idx, cnt = np.zeros((v, 5), np.uint16), np.zeros((v, 4), np.int32), np.zeros(v, np.uint32)
+        if v > 0:
+            check(int(lib().lio_voxelizer_output(self.h, ptr(feat, C.c_uint16), ptr(idx, C.c_int32), ptr(cnt, C.c_uint32), v)), "voxelizer output")
+        return feat.view(np.float16), idx, cnt
+
+    def output_device(self):
+        """(address of the f16 features, address of the int32 indices, V): device memory, valid until the next forward"""
+        a, b = C.c_void_p(0), C.c_void_p(0)
+        v = check(int(lib().lio_voxelizer_output_device(self.h, C.byref(a), C.byref(b))), "voxelizer output_device")
+        return a.value or 0, b.value or 0, v
+
+    def window(self):
+        """the window's rows (total, 5) f32, newest sweep first"""
+        n = max(-int(lib().lio_voxelizer_window(self.h, None, 0)), 0)
+        rows = np.zeros((n, 5), np.float32)
+        if n > 0:
+            check(int(lib().lio_voxelizer_window(self.h, ptr(rows, C.c_float), n)), "voxelizer window")
+        return rows
+
+    def window_counts(self):
+        """rows per sweep, newest first (max_frame_num int32)"""
+        out = np.zeros(self.params.max_frame_num, np.int32)
+        check(int(lib().lio_voxelizer_window_counts(self.h, ptr(out, C.c_int32), len(out))), "voxelizer window_counts")
+        return out
+
+    def window_device(self):
+        """(address of the window's rows on the device, rows): valid until the next forward or reset"""
+        a = C.c_void_p(0)
+        n = check(int(lib().lio_voxelizer_window_device(self.h, C.byref(a))), "voxelizer window_device")
+        return a.value or 0, n
+
+    def reset(self):
+        check(lib().lio_voxelizer_reset(self.h), "voxelizer reset")
+        self.num_voxels = 0
+
+    def last_counts(self):
+        """(real_voxels, points_in_range, points_kept) of the last forward: real_voxels above max_voxels means the cap bit"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        check(lib().lio_voxelizer_last_counts(self.h, *[C.byref(x) for x in v]), "voxelizer counts")
+        return tuple(int(x.value) for x in v)
+
+    def last_times(self):
+        """(window_us, insert_us, rank_us, slots_us, mean_us, total_us): device time of the last forward by stage"""
+        v = [C.c_double(0) for _ in range(6)]
+        check(lib().lio_voxelizer_last_times(self.h, *[C.byref(x) for x in v]), "voxelizer times")
+        return tuple(x.value for x in v)
+
+
 class ImuCalib:
     """lio_calib_imu: the lidar-IMU calibration (the reference's CalibLidarImu); include/lio_hip.h states every rule.  The host half (add_imu,
     add_frame without the flag, calibrate, the pose lists) needs no device; lidar_pose and the map update of add_frame open it on first use."""
